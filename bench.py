@@ -2,7 +2,7 @@
 """bench.py -- BN254 MSM 2^26 (primary, BASELINE.json configs[1]) + BabyBear NTT 2^24 x 64
 (secondary, configs[2]) on N MI355X, one process per GPU.
 
-  python bench.py --gpus 1 --steps K --warmup W
+  python bench.py --gpus 1 --steps K --warmup W [--dump-outputs DIR]
   python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
   python bench.py --gpus N ...      (no WORLD_SIZE in the environment: re-launches itself under torch.distributed.run;
                                      on a box with fewer than N GPUs it prints a JSON line with an "error" key, exit 0)
@@ -25,6 +25,9 @@ run), "cpu_baseline" (the reference CPU backend from oracle/_ref timed on this b
 the full workload when the host grants >= 16 cores of CPU time), "ntt" (secondary metric with its own
 roofline/cpu_baseline).  --size-log2 / --ntt-log2 shrink the workload for quick checks; the
 JSON then names the reduced workload (never reported as the headline config).
+
+--dump-outputs DIR writes, after the timed steps, what the last timed step computed (dump_outputs() below), so that two
+builds can be compared output for output: the inputs are seeded, identical from run to run for the same arguments.
 """
 import argparse
 import ctypes
@@ -61,7 +64,12 @@ def parse():
     ap.add_argument("--inproc-only", action="store_true", help=argparse.SUPPRESS)  # internal: the launcher's second leg
     ap.add_argument("--scaling", choices=["weak", "strong"], default="weak",
                     help="weak: one 2^size MSM per GPU (the N shards form one 2^size*N MSM); strong: ONE 2^size MSM cut over the N GPUs")
-    return ap.parse_args()
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the outputs of the last timed MSM and NTT step as DIR/<name>.npy (float64, at most 64 MB)")
+    args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    return args
 
 
 def synth_scalars(n, device, seed):
@@ -76,6 +84,48 @@ def synth_scalars(n, device, seed):
         s[lo:hi, 7] = torch.randint(0, BN254_R_TOP, (hi - lo,), dtype=torch.int32, device=device, generator=g)
     return s
 
+
+DUMP_LIMIT_BYTES = 64 << 20
+NTT_DUMP_SAMPLE = 1 << 20  # elements of the NTT outputs dumped: a fixed, seeded sample of the batch
+NTT_DUMP_SEED = 2024
+
+
+def msm_dump_arrays(res):
+    """--dump-outputs, MSM: the result point in affine form ([1, 16] words x, y; (0, 0) = identity). The projective words a caller
+    receives name the same point, but their representative (the Z) changes from run to run with the order in which the sort's
+    atomic slot reservation lines up the points of a bucket, so they cannot be compared output for output; the affine form can"""
+    from oracle import pyref
+
+    proj = res.cpu().numpy().view(np.uint32).reshape(1, -1)
+    x, y, z = (sum(int(w) << (32 * k) for k, w in enumerate(proj[0, 8 * i:8 * (i + 1)])) for i in range(3))
+    aff = pyref.proj_to_affine(pyref.BN254, x, y, z)
+    words = [(v >> (32 * k)) & 0xFFFFFFFF for v in aff for k in range(8)]
+    return {"msm_result_affine": np.array([words], dtype=np.uint32)}
+
+
+def ntt_dump_arrays(y, z):
+    """--dump-outputs, NTT: the forward (y) and inverse (z) outputs of the last step at a fixed, seeded sample of flat positions
+    (all of them when the batch is small enough), and the positions themselves"""
+    total = y.numel()
+    if total <= NTT_DUMP_SAMPLE:
+        idx = np.arange(total, dtype=np.int64)
+    else:
+        idx = np.unique(np.random.default_rng(NTT_DUMP_SEED).integers(0, total, size=NTT_DUMP_SAMPLE, dtype=np.int64))
+    ti = torch.from_numpy(idx).to(y.device)
+    return {"ntt_sample_index": idx, "ntt_forward_sample": y.reshape(-1)[ti].cpu().numpy(), "ntt_inverse_sample": z.reshape(-1)[ti].cpu().numpy()}
+
+
+def dump_outputs(d, arrays):
+    """DIR/<name>.npy in float64: every value dumped is an integer below 2^53 (32-bit words, field elements, positions), so the
+    conversion is exact"""
+    arrays = {k: np.asarray(v).astype(np.float64) for k, v in arrays.items()}
+    total = sum(a.nbytes for a in arrays.values())
+    if total > DUMP_LIMIT_BYTES:
+        raise ValueError(f"--dump-outputs: {total} bytes exceed the {DUMP_LIMIT_BYTES}-byte limit")
+    os.makedirs(d, exist_ok=True)
+    for k, a in arrays.items():
+        np.save(os.path.join(d, f"{k}.npy"), a)
+    return {"dir": os.path.abspath(d), "files": sorted(f"{k}.npy" for k in arrays), "bytes": total}
 
 
 REHEARSAL = os.environ.get("ICICLE_BENCH_GLOO_REHEARSAL", "0") == "1"
@@ -428,6 +478,7 @@ def main():
     lib.icicle_hip_kernel_timing(0, True, ctypes.byref(tot), ctypes.byref(cnt))
     lib.icicle_hip_enable_kernel_timing(False)
     msm_ms = dt / args.steps * 1e3
+    dumps = msm_dump_arrays(res) if args.dump_outputs and rank == 0 else None  # the last timed step's result
     # ---- what the collectives layer saw: recorded in the line, and the gathered result must be the SAME bytes
     # on every rank (each rank sums the all-gathered partials itself: same inputs, same deterministic kernel)
     collectives = {"world_size": world, "backend": None, "rccl_version": None}
@@ -633,6 +684,8 @@ def main():
         lib.icicle_hip_kernel_timing(1, True, ctypes.byref(tot), ctypes.byref(cnt))
         lib.icicle_hip_enable_kernel_timing(False)
         roundtrip_ok = bool(torch.equal(x, z))  # after the timed region: z is the inverse of the last forward transform
+        if dumps is not None:
+            dumps.update(ntt_dump_arrays(y, z))
         ntt_call_ms = tot.value / max(1, cnt.value)  # one direction, `rows` transforms
         ntt_bytes = 2 * rows * nn * 4  # 2*batch*N*sizeof(elem) per direction
         ntts = 2 * rows * world * args.steps  # forward + inverse each count
@@ -900,6 +953,8 @@ def main():
                 out["inproc"] = _last_json_line(r2.stdout) or {"error": f"rc {r2.returncode}: " + (r2.stderr or r2.stdout)[-1500:]}
         except Exception as e:
             out["inproc"] = {"error": repr(e)}
+    if dumps is not None:
+        out["dump_outputs"] = dump_outputs(args.dump_outputs, dumps)
     if rank == 0:
         print(json.dumps(out))
     if world > 1:

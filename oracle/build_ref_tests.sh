@@ -9,7 +9,7 @@
 #   test_modarith_{babybear,koalabear,goldilocks,bn254,bls12_381,bls12_377,stark252}  icicle/tests/test_mod_arithmetic_api.h via oracle/shim/tests/modarith_main.cpp
 #   example_msm, example_ntt             examples/c++/{msm,ntt}/example.cpp (bn254), run as `example_msm HIP`
 #   example_best_practice_ntt            examples/c++/best-practice-ntt/example.cpp (three streams)
-# Run with ICICLE_BACKEND_INSTALL_DIR=plugin/lib/backend so that the reference runtime loads the HIP plugin and makes
+# Run with ICICLE_BACKEND_INSTALL_DIR=oracle/_ref/backend so that the reference runtime loads the HIP plugin and makes
 # "HIP" the main device (icicle/tests/test_base.h:37-46): tests/test_gpu_reference_suite.py.
 set -euo pipefail
 HERE="$(cd "$(dirname "$0")" && pwd)"

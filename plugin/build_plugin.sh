@@ -1,7 +1,8 @@
 #!/usr/bin/env bash
 # Builds the reference-runtime plugin DSOs (the drop-in form of this backend) against the reference
-# headers and the reference libraries built by oracle/build_ref.sh. Needs /root/reference; outputs
-# travel to the GPU box under plugin/lib/backend/hip/ (git-ignored; nothing the product ships lives under oracle/):
+# headers and the reference libraries built by oracle/build_ref.sh. Needs /root/reference, so the outputs go where
+# everything else built from it goes, next to the reference runtime that loads them: oracle/_ref/backend/hip/
+# (git-ignored; the release layout lib/ + lib/backend/hip/). A checkout without the reference tree uses them prebuilt:
 #   libicicle_backend_hip_device.so           "HIP" DeviceAPI            (RTLD_GLOBAL by name)
 #   libicicle_backend_hip_curve_<c>.so        msm + msm_precompute_bases
 #   libicicle_backend_hip_field_<f>.so        ntt family + extension ntt
@@ -10,8 +11,7 @@ HERE="$(cd "$(dirname "$0")" && pwd)"
 ROOT="$(dirname "$HERE")"
 R="${ICICLE_REFERENCE_DIR:-/root/reference}/icicle"
 REF="$ROOT/oracle/_ref"
-OUT="$HERE/lib/backend/hip"
-rm -rf "$REF/backend" # (rounds 1-3 installed the plugin inside the oracle tree)
+OUT="$REF/backend/hip"
 HIPLIB="$ROOT/icicle_amd/lib"
 HIPCC="${HIPCC:-/opt/rocm/bin/hipcc}"
 if [ ! -d "$R" ]; then echo "build_plugin: $R not present -- using prebuilt plugin if any" >&2; exit 0; fi

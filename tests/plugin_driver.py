@@ -22,7 +22,7 @@ def main():
     field = ref.RefNttField("babybear")
     koala = ref.RefNttField("koalabear")
     assert "HIP" not in rt.registered_devices()
-    assert rt.load_backend(os.path.join(ROOT, "plugin", "lib", "backend", "hip")) == 0
+    assert rt.load_backend(os.path.join(ROOT, "oracle", "_ref", "backend", "hip")) == 0
     devs = rt.registered_devices()
     assert "HIP" in devs and "CPU" in devs, devs
 

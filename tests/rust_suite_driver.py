@@ -486,7 +486,7 @@ def main():
     if os.environ.get("RUST_REPLAY_MAIN") == "CPU":  # self-test of the replay code without a GPU: main == ref == "CPU"
         R.MAIN_DEVICE = ("CPU", 0)
     else:
-        R.test_load_and_init_devices(os.path.join(ROOT, "plugin", "lib", "backend", "hip"))
+        R.test_load_and_init_devices(os.path.join(ROOT, "oracle", "_ref", "backend", "hip"))
     R.test_set_main_device()
     kw = {} if reps is None else {"reps": reps}
     if check in MSM_CHECKS:

@@ -77,3 +77,41 @@ def test_bench_one_process_per_gpu_leg_rehearsed_with_two_ranks():
     assert out["ntt"]["roundtrip_ok"] is True and out["ntt"]["value"] > 0
     assert out["ntt_split"]["roundtrip_ok"] is True, out.get("ntt_split")
     assert out["inproc"]["result_ok"] is True and out["inproc"]["n_gpus"] == 2, out.get("inproc")
+
+
+@pytest.mark.gpu
+def test_bench_dump_outputs_are_the_last_steps_results_and_repeat(tmp_path):
+    """`--dump-outputs DIR`: after the timed steps the MSM result (affine) and a seeded sample of the
+    NTT's forward / inverse outputs land in DIR as float64 .npy files of at most 64 MB; the line still reports exactly --steps
+    timed steps with ms_per_step; and a second run with the same arguments dumps the same values (seeded inputs)."""
+    import numpy as np
+
+    from oracle import pyref
+
+    env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT")}
+    dumped = []
+    for run in range(2):
+        d = tmp_path / f"run{run}"
+        r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1", "--size-log2", "16",
+                            "--ntt-log2", "14", "--ntt-batch", "4", "--no-cpu-baseline", "--dump-outputs", str(d)],
+                           capture_output=True, text=True, env=env, timeout=600)
+        assert r.returncode == 0, r.stderr[-3000:]
+        out = json.loads([ln for ln in r.stdout.strip().splitlines() if ln.startswith("{")][-1])
+        assert "error" not in out, out
+        assert out["steps"] == 3 and out["ms_per_step"] > 0 and out["ntt"]["roundtrip_ok"] is True
+        names = {"msm_result_affine.npy", "ntt_sample_index.npy", "ntt_forward_sample.npy", "ntt_inverse_sample.npy"}
+        assert set(out["dump_outputs"]["files"]) == names == set(os.listdir(d))
+        arrs = {n: np.load(d / n) for n in names}
+        assert all(a.dtype == np.float64 for a in arrs.values())
+        assert sum(os.path.getsize(d / n) for n in names) <= 64 << 20
+        dumped.append(arrs)
+    a = dumped[0]
+    C = pyref.BN254
+    w = [int(v) for v in a["msm_result_affine.npy"][0]]
+    x, y = (sum(v << (32 * k) for k, v in enumerate(w[8 * i:8 * (i + 1)])) for i in range(2))
+    assert (x, y) != pyref.INF and pyref.on_curve(C, (x, y))
+    assert a["msm_result_affine.npy"].shape == (1, 16) and a["ntt_forward_sample.npy"].shape == (4 << 14,)  # 2^16 elements: all of them
+    assert np.array_equal(a["ntt_sample_index.npy"], np.arange(4 << 14))
+    assert a["ntt_forward_sample.npy"].max() < pyref.BABYBEAR.p and a["ntt_inverse_sample.npy"].max() < pyref.BABYBEAR.p
+    for n in sorted(a):
+        assert np.array_equal(a[n], dumped[1][n]), n

@@ -21,7 +21,7 @@ import pytest
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 TESTS = os.path.join(ROOT, "oracle", "_ref", "tests")
-BACKEND = os.path.join(ROOT, "plugin", "lib", "backend")
+BACKEND = os.path.join(ROOT, "oracle", "_ref", "backend")
 
 
 def _run(binary, gfilter, repeat=1, timeout=900):

@@ -19,7 +19,7 @@ import pytest
 
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-PLUG = os.path.join(ROOT, "plugin", "lib", "backend", "hip", "libicicle_backend_hip_device.so")
+PLUG = os.path.join(ROOT, "oracle", "_ref", "backend", "hip", "libicicle_backend_hip_device.so")
 
 CASES = [
     ("check_msm", "bn254", 50), ("check_msm", "bls12_381", 5),
