@@ -520,20 +520,9 @@ namespace icicle_hip {
       return ICICLE_SUCCESS;
     }
     int parts[3], P;
-    // sub-transforms of 2^8 points (three passes at 2^24). Two passes of 2^12 (1024-thread blocks, 4-column tiles)
-    // and 64-column tiles were built and measured in round 1 and lost: profiles/r01_notes.md.
-    split_logn(logn, 8, parts, &P);
     {
-      // Which pass takes the extra bit of a size that is not a multiple of three: split_logn gives it to the first ones (9,8,8 at
-      // 2^25). Measured (profiles/r05_ntt_big_parts.txt, ICICLE_HIP_NTT_PARTS_ORDER = 0 / 1 / 2 = first / last / middle): at 2^25 the
-      // MIDDLE pass is the place for the 512-row sub-transform, 8,9,8: 6.48 -> 6.02 ms (x 32 rows); every other size measured
-      // (2^20, 2^22, 2^26, 2^27) is best or within 3 % with the default, so only 2^25 changes.
       static const int order = getenv("ICICLE_HIP_NTT_PARTS_ORDER") ? atoi(getenv("ICICLE_HIP_NTT_PARTS_ORDER")) : -1;
-      if (P == 3 && (order == 1)) std::swap(parts[0], parts[2]);
-      if (P == 3 && (order == 2 || (order < 0 && logn == 25))) {
-        std::swap(parts[0], parts[1]);
-        if (parts[0] > parts[2]) std::swap(parts[0], parts[2]);
-      }
+      ntt_split_parts(logn, order, parts, &P); // (ntt_plan.h: 8,9,8 at 2^25)
     }
     // P >= 2: passes 0..P-2 run in a work buffer (the last pass permutes across tiles, so it can
     // never be in place; this also makes input == output legal, test_mod_arithmetic_api.h:627,679)
@@ -545,9 +534,13 @@ namespace icicle_hip {
     // kRN: the passes consume the bit-reversed rows as they lie (ntt_fast.hpp RN, in place behind pass 0); kRR and forward cosets
     // still reorder first. ICICLE_HIP_NTT_RN_NATIVE=0: the pre-pass for every reversed input (rounds 1-4).
     static const bool rn_on = !(getenv("ICICLE_HIP_NTT_RN_NATIVE") && atoi(getenv("ICICLE_HIP_NTT_RN_NATIVE")) == 0);
-    const bool rn_native = rn_on && nl.in_rev && !nl.out_rev && !(nl.coset && !nl.inverse);
-    const bool prerev = nl.in_rev && P >= 2 && !rn_native;
-    const bool fast = !nl.in_rev || prerev || rn_native;
+    // Interleaved transforms (columns_batch, extension field): lane-native tiles, see ntt_fast.hpp. ltot transforms sit
+    // word by word at element stride es = ltot; one row group per batch row (row-major) or a single one (columns_batch).
+    static const bool lanes_on = !(getenv("ICICLE_HIP_NTT_LANES") && atoi(getenv("ICICLE_HIP_NTT_LANES")) == 0);
+    // ICICLE_HIP_NTT_PAD_LANES=0: no padded work buffer for ragged interleaved layouts (A/B, ntt_plan.h ntt_plan_flags)
+    static const bool pad_on = !(getenv("ICICLE_HIP_NTT_PAD_LANES") && atoi(getenv("ICICLE_HIP_NTT_PAD_LANES")) == 0);
+    const NttPlanFlags pf = ntt_plan_flags(P, nl.in_rev, nl.out_rev, nl.coset, nl.inverse, cfg->columns_batch, (uint32_t)batch, lanes, nl.es, rn_on, lanes_on, pad_on);
+    const bool rn_native = pf.rn_native, prerev = pf.prerev, fast = pf.fast, lane_native = pf.lane_native, pad_w = pf.pad_w;
     TempBuf d_ctab;
     if (nl.coset && fast) { // two-level table, 4096 + N/4096 entries
       const uint32_t nhi = (uint32_t)std::max<uint64_t>(1, n >> 12);
@@ -574,24 +567,8 @@ namespace icicle_hip {
       }
     }
     const bool grouped = rows_per_group < nl.nbatch;
-    // Interleaved transforms (columns_batch, extension field): lane-native tiles, see ntt_fast.hpp. ltot transforms sit
-    // word by word at element stride es = ltot; one row group per batch row (row-major) or a single one (columns_batch).
-    static const bool lanes_on = !(getenv("ICICLE_HIP_NTT_LANES") && atoi(getenv("ICICLE_HIP_NTT_LANES")) == 0);
-    // (A ragged lane count -- 100 columns -- is NOT slow because of its masked last slice: with the 4 surplus lanes split off into a
-    //  row-major side batch the three full slices took as long as the four did, 0.85 vs 0.84 ms at 2^20 x 100. Rows of 100 words are
-    //  400 bytes apart, so every 128-byte access straddles three 64-byte sectors instead of two: 2.9 TB/s per pass against 4.8 for the
-    //  row batch. Built, measured, removed: profiles/r05_notes.md.)
-    const uint32_t ltot = cfg->columns_batch ? (uint32_t)batch * lanes : lanes;
-    const bool lane_native = lanes_on && fast && ltot > 1;
-    const uint32_t row_groups = cfg->columns_batch ? 1u : (uint32_t)batch;
-    // Ragged interleaved layouts (columns_batch with a lane count that is not a multiple of 32 words: the Rust suite's 100
-    // columns): the WORK buffer pads the lane count to the next multiple of 32, so that only the two passes that touch the
-    // caller's buffers see rows that straddle sectors (ntt_plan.h NttLaunch::es_out). ICICLE_HIP_NTT_PAD_LANES=0: off (A/B).
-    static const bool pad_on = !(getenv("ICICLE_HIP_NTT_PAD_LANES") && atoi(getenv("ICICLE_HIP_NTT_PAD_LANES")) == 0);
-    const bool pad_w = pad_on && lane_native && cfg->columns_batch && P >= 2 && !prerev && !rn_native && !grouped && ltot > 32 && ltot % 32 != 0;
-    const uint64_t es_w = pad_w ? (uint64_t)((ltot + 31) / 32) * 32 : nl.es;
     if (P >= 2 && !rn_native) {
-      HIP_TRY(d_work.alloc(pad_w ? (size_t)n * es_w * 4 : (grouped ? (size_t)rows_per_group * n * 4 : bytes), st), ICICLE_ALLOCATION_FAILED);
+      HIP_TRY(d_work.alloc(pad_w ? (size_t)n * pf.es_w * 4 : (grouped ? (size_t)rows_per_group * n * 4 : bytes), st), ICICLE_ALLOCATION_FAILED);
       W = d_work.as<uint32_t>();
     }
     KernelTimer::begin(1, st);
@@ -614,89 +591,19 @@ namespace icicle_hip {
       nl.src_rel = (grouped && p != 0) ? 1 : 0;
       nl.dst_rel = (grouped && p != P - 1) ? 1 : 0;
       const uint64_t L = (uint64_t)1 << parts[p];
-      // fast path: block = T * L/16 threads (<= 512), LDS = 2 buffers of L*(T+1) words (<= 160 KiB)
       const uint64_t epb = L >= 16 ? 16 : L;
-      // column passes of 512 / 1024 rows (transforms of 2^25 points and more): 1024-thread blocks, twice the tile width
+      // per-pass launch geometry (ntt_plan.h fast_pass_geometry: tile width, lane slices, column / outer-index groups, strides)
       static const bool big_on = !(getenv("ICICLE_HIP_NTT_BIG") && atoi(getenv("ICICLE_HIP_NTT_BIG")) == 0);
-      const bool cvar_p = nl.coset && (nl.inverse ? p == P - 1 : p == 0);
-      // Measured (profiles/r03_notes.md section 9): 2^27 x 4 5.63 -> 5.18 ms, 2^27 x 8 9.74 -> 9.15, but 2^26 x 16 7.25 -> 7.52 and
-      // 2^25 x 32 unchanged (one 16-wave block per CU hides less latency than two 8-wave ones): only from 2^27 up.
-      const bool big = big_on && fast && !rn_native && !lane_native && logn >= 27 && p < P - 1 && P >= 2 && (parts[p] == 9 || parts[p] == 10) && !cvar_p;
-      uint32_t tmax = (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>(32, (big ? 1024 : 512) * epb / L));
-      while (tmax > 1 && 2 * L * (tmax + 1) * 4 > 160 * 1024)
-        tmax >>= 1;
-      const int rn_mode = !rn_native ? 0 : ((p == 0 && !lane_native) ? 2 : 1);
-      while (rn_mode == 2 && tmax > 1 && 2 * (L + (L >> 4)) * tmax * 4 > 160 * 1024)
-        tmax >>= 1;
-      // lane-native: the tile's tmax word-columns are (tmax >> lsh) logical columns x 2^lsh interleaved transforms. A lane count
-      // that is not a multiple of the widest slice keeps a masked last slice (running the remainder as a second launch on
-      // narrower slices -- 100 columns = 3 x 32 + a launch of 4-lane tiles -- was built and measured SLOWER, 2^20 x 100:
-      // 0.79 -> 0.99 ms: the tail's logical columns are es * 4 bytes apart, 16-byte runs; profiles/r04_notes.md section 1).
-      uint32_t lsh = 0;
-      if (lane_native)
-        while ((2u << lsh) <= tmax && (1u << lsh) < ltot)
-          lsh++;
-      PassDesc pd = rn_native ? make_pass_rn(parts, P, p, dom.log_max, tmax >> lsh) : make_pass(parts, P, p, n, dom.log_max, tmax >> lsh);
-      // Few launch rows (16-64 interleaved transforms = one or two slices): adjacent logical columns that share a twiddle set
-      // run as launch rows of one block -- pass 0 (its inter-pass factor depends on column / cprime only) and the last pass
-      // (none at all); not the coset / bit-reversed-output variants, whose per-block constants depend on the column.
-      uint32_t cg = 1, ag_for_pass = 1;
-      const uint32_t tcl = (uint32_t)pd.T; // logical columns in the LDS tile
-      {
-        static const uint32_t cg_max = getenv("ICICLE_HIP_NTT_COLUMN_GROUP") ? (uint32_t)std::max(1, atoi(getenv("ICICLE_HIP_NTT_COLUMN_GROUP"))) : 8u;
-        const bool cvar_here = nl.coset && (nl.inverse ? p == P - 1 : p == 0);
-        // (only with full slices: grouping multiplies the mostly idle rows of a ragged last slice as well -- 2^20 x 100: 0.84 -> 0.89 ms)
-        const bool full = lane_native && fast && ltot % (1u << lsh) == 0;
-        // (RN: every pass can group adjacent logical columns -- the factor behind a pass is rebuilt per row, ntt_fast.hpp rn_rowfac)
-        const bool allowed = full && !cvar_here && (rn_native ? P >= 2 : ((p == 0 && P >= 2) || p == P - 1)); // (round 5: the bit-reversed-output store too)
-        const bool middle = full && !rn_native && P == 3 && p == 1; // groups over the outer index instead (ntt_plan.h agrp)
-        const uint32_t rows_now = row_groups * ((ltot + (1u << lsh) - 1) >> lsh);
-        uint32_t want = 1;
-        while ((allowed || middle) && want * 2 <= cg_max && rows_now * want * 2 <= 8)
-          want *= 2;
-        uint32_t ag = 1;
-        if (middle) {
-          while (want > 1 && ((uint64_t)1 << parts[0]) % want != 0)
-            want >>= 1;
-          ag = want;
-          want = 1;
-          pd.ntiles /= ag; // tiles enumerate (a / ag, ct)
-          ag_for_pass = ag;
-        }
-        while (want > 1) {
-          const PassDesc pg = rn_native ? make_pass_rn(parts, P, p, dom.log_max, tcl * want) : make_pass(parts, P, p, n, dom.log_max, tcl * want);
-          if ((uint32_t)pg.T == tcl * want && (rn_native || pg.is_last || (uint32_t)pg.T <= pg.cprime)) {
-            pd = pg;
-            cg = want;
-            break;
-          }
-          want >>= 1;
-        }
-      }
-      const uint32_t tw = tcl << lsh; // word-columns per tile
-      const uint32_t ag_rows = ag_for_pass;
+      static const uint32_t cg_max = getenv("ICICLE_HIP_NTT_COLUMN_GROUP") ? (uint32_t)std::max(1, atoi(getenv("ICICLE_HIP_NTT_COLUMN_GROUP"))) : 8u;
+      const FastPass fp = fast_pass_geometry(nl, FastPassIn{parts, P, p, n, (int)dom.log_max, pf, lanes, src == W, dst == W, big_on, cg_max});
+      PassDesc pd = fp.pd;
+      const bool big = fp.big;
+      const int rn_mode = fp.rn_mode;
+      const uint32_t tw = fp.tcl << fp.lsh; // word-columns per tile
       static const bool xcd_on = !(getenv("ICICLE_HIP_NTT_XCD") && atoi(getenv("ICICLE_HIP_NTT_XCD")) == 0);
       pd.xcd_remap = (xcd_on && fast && tw < 32 && pd.ntiles >= 64 && pd.ntiles % 8 == 0) ? 1 : 0;
       if (fast) {
-        NttLaunch nlp = nl;
-        if (pad_w) { // the work buffer's rows are es_w words apart, the caller's ltot
-          nlp.es = (src == W) ? es_w : nl.es;
-          nlp.es_out = (dst == W) ? es_w : nl.es;
-        }
-        if (lane_native) { // launch rows = slices of 2^lsh transforms
-          nlp.lsh = lsh;
-          nlp.ltot = ltot;
-          nlp.lanes = (ltot + (1u << lsh) - 1) >> lsh;
-          nlp.bs = n * lanes;
-          nlp.row0 = 0;
-          nlp.tcl = tcl;
-          nlp.cgrp = cg * ag_rows;
-          nlp.agrp = ag_rows;
-          nlp.cst_in = ag_rows > 1 ? pd.in_base_a * nl.es : (uint64_t)tcl * pd.in_st * nl.es;
-          nlp.cst_out = (pd.is_last && ag_rows == 1 && !rn_native) ? (uint64_t)tcl * nl.es : nlp.cst_in; // (RN passes are in place: same layout both sides)
-          if (pd.is_last && nl.out_rev && !rn_native) nlp.cst_out = 0; // (the bit-reversed store computes the column's place itself, ntt_fast.hpp)
-          nlp.nrows_launch = row_groups * nlp.lanes * nlp.cgrp;
-        }
+        NttLaunch nlp = fp.nl;
         const unsigned threads = (unsigned)(tw * (L / epb));
         const size_t lds_bytes = rn_mode == 2 ? (size_t)2 * tw * (L + (L >> 4)) * 4 : (size_t)2 * L * (tw + 1) * 4;
         nlp.vec4 = (rn_mode == 2 && nl.es == 1 && nl.bs % 4 == 0 && L >= 16 && (((uintptr_t)src) & 15) == 0) ? 1 : 0;

@@ -180,6 +180,175 @@ namespace icicle_hip {
     return pd;
   }
 
+  // ---- the 31-bit NTT's plan (ntt.hip ntt_run), host-callable so that tests/plan_harness.cpp checks the very same code ----------
+  // Pass lengths: split_logn, then which pass takes the extra bit of a size that is not a multiple of three (`order` =
+  // ICICLE_HIP_NTT_PARTS_ORDER, -1 = default). Measured (profiles/r05_ntt_big_parts.txt, 0 / 1 / 2 = first / last / middle): at 2^25
+  // the MIDDLE pass is the place for the 512-row sub-transform, 8,9,8: 6.48 -> 6.02 ms (x 32 rows); every other size measured
+  // (2^20, 2^22, 2^26, 2^27) is best or within 3 % with the default, so only 2^25 changes.
+  static inline void ntt_split_parts(int logn, int order, int* parts, int* np)
+  {
+    // sub-transforms of 2^8 points (three passes at 2^24). Two passes of 2^12 (1024-thread blocks, 4-column tiles)
+    // and 64-column tiles were built and measured in round 1 and lost: profiles/r01_notes.md.
+    split_logn(logn, 8, parts, np);
+    if (*np == 3 && order == 1) std::swap(parts[0], parts[2]);
+    if (*np == 3 && (order == 2 || (order < 0 && logn == 25))) {
+      std::swap(parts[0], parts[1]);
+      if (parts[0] > parts[2]) std::swap(parts[0], parts[2]);
+    }
+  }
+
+  // Transform-level choices: which kernel family runs the passes and how interleaved transforms are laid out in the work buffer.
+  struct NttPlanFlags {
+    bool rn_native;   // kRN consumed natively (ntt_fast.hpp RN): every pass in place in the output, no work buffer
+    bool prerev;      // bit-reversed input reordered into the work buffer first (kRR, forward cosets on reversed input)
+    bool fast;        // k_ntt_fast passes (else the generic kernel: single-pass transforms with reversed input)
+    bool lane_native; // interleaved transforms (columns_batch, extension field) on lane-native tiles
+    bool pad_w;       // the work buffer pads the lane count to a multiple of 32 words (NttLaunch::es_out)
+    uint32_t ltot;    // interleaved transforms per row group
+    uint32_t row_groups;
+    uint64_t es_w;    // element stride in the work buffer
+  };
+  // es: the caller's element stride; *_on: the A/B switches ICICLE_HIP_NTT_RN_NATIVE / _LANES / _PAD_LANES. (The experimental row
+  // groups of ntt_run, ICICLE_HIP_NTT_GROUP_MB, take row-major base-field batches only: never a padded work buffer.)
+  static inline NttPlanFlags ntt_plan_flags(int P, bool in_rev, bool out_rev, bool coset, bool inverse, bool columns_batch, uint32_t batch, uint32_t lanes,
+                                            uint64_t es, bool rn_on, bool lanes_on, bool pad_on)
+  {
+    NttPlanFlags f{};
+    f.rn_native = rn_on && in_rev && !out_rev && !(coset && !inverse);
+    f.prerev = in_rev && P >= 2 && !f.rn_native;
+    f.fast = !in_rev || f.prerev || f.rn_native;
+    // (A ragged lane count -- 100 columns -- is NOT slow because of its masked last slice: with the 4 surplus lanes split off into a
+    //  row-major side batch the three full slices took as long as the four did, 0.85 vs 0.84 ms at 2^20 x 100. Rows of 100 words are
+    //  400 bytes apart, so every 128-byte access straddles three 64-byte sectors instead of two: 2.9 TB/s per pass against 4.8 for the
+    //  row batch. Built, measured, removed: profiles/r05_notes.md.)
+    f.ltot = columns_batch ? batch * lanes : lanes;
+    f.lane_native = lanes_on && f.fast && f.ltot > 1;
+    f.row_groups = columns_batch ? 1u : batch;
+    // Ragged interleaved layouts (columns_batch with a lane count that is not a multiple of 32 words: the Rust suite's 100
+    // columns): the WORK buffer pads the lane count to the next multiple of 32, so that only the two passes that touch the
+    // caller's buffers see rows that straddle sectors (NttLaunch::es_out).
+    f.pad_w = pad_on && f.lane_native && columns_batch && P >= 2 && !f.prerev && !f.rn_native && f.ltot > 32 && f.ltot % 32 != 0;
+    f.es_w = f.pad_w ? (uint64_t)((f.ltot + 31) / 32) * 32 : es;
+    return f;
+  }
+
+  // One pass of the fast path: what ntt_run launches for pass p.
+  struct FastPassIn {
+    const int* parts;
+    int P, p;
+    uint64_t n;
+    int log_max;
+    NttPlanFlags f;
+    uint32_t lanes;     // u32 words per element: 1, or 4 (quartic extension)
+    bool src_w, dst_w;  // the pass reads / writes the work buffer
+    bool big_on;        // ICICLE_HIP_NTT_BIG
+    uint32_t cg_max;    // ICICLE_HIP_NTT_COLUMN_GROUP (8); 1 = no column / outer-index groups
+  };
+  struct FastPass {
+    PassDesc pd;     // grouped descriptor (pd.T = tcl * cg logical columns, pd.ntiles counts groups of ag outer indices)
+    NttLaunch nl;    // the launch's NttLaunch (strides of both sides, lane-native rows, group strides)
+    uint32_t tmax;   // widest tile the LDS / block budget allows, in word-columns
+    uint32_t lsh;    // lane-native: log2 of the interleaved transforms per launch row (slice)
+    uint32_t tcl;    // logical columns in the LDS tile
+    uint32_t cg, ag; // column groups (pass 0 / last pass), outer-index groups (middle pass)
+    bool big;        // 1024-thread blocks (transforms of 2^27 points and more)
+    int rn_mode;     // 0: not RN, 1: RN column pass, 2: RN run pass (pass 0 of a row-major batch)
+  };
+  static inline FastPass fast_pass_geometry(const NttLaunch& nl, const FastPassIn& in)
+  {
+    FastPass fp{};
+    const NttPlanFlags& f = in.f;
+    const int* parts = in.parts;
+    const int P = in.P, p = in.p;
+    const uint64_t L = (uint64_t)1 << parts[p];
+    // block = T * L/16 threads (<= 512), LDS = 2 buffers of L*(T+1) words (<= 160 KiB)
+    const uint64_t epb = L >= 16 ? 16 : L;
+    const bool cvar = nl.coset && (nl.inverse ? p == P - 1 : p == 0); // coset factors in this pass
+    // column passes of 512 / 1024 rows (transforms of 2^25 points and more): 1024-thread blocks, twice the tile width.
+    // Measured (profiles/r03_notes.md section 9): 2^27 x 4 5.63 -> 5.18 ms, 2^27 x 8 9.74 -> 9.15, but 2^26 x 16 7.25 -> 7.52 and
+    // 2^25 x 32 unchanged (one 16-wave block per CU hides less latency than two 8-wave ones): only from 2^27 up.
+    fp.big = in.big_on && f.fast && !f.rn_native && !f.lane_native && nl.logn >= 27 && p < P - 1 && P >= 2 && (parts[p] == 9 || parts[p] == 10) && !cvar;
+    uint32_t tmax = (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>(32, (fp.big ? 1024 : 512) * epb / L));
+    while (tmax > 1 && 2 * L * (tmax + 1) * 4 > 160 * 1024)
+      tmax >>= 1;
+    fp.rn_mode = !f.rn_native ? 0 : ((p == 0 && !f.lane_native) ? 2 : 1);
+    while (fp.rn_mode == 2 && tmax > 1 && 2 * (L + (L >> 4)) * tmax * 4 > 160 * 1024)
+      tmax >>= 1;
+    fp.tmax = tmax;
+    // lane-native: the tile's tmax word-columns are (tmax >> lsh) logical columns x 2^lsh interleaved transforms. A lane count
+    // that is not a multiple of the widest slice keeps a masked last slice (running the remainder as a second launch on
+    // narrower slices -- 100 columns = 3 x 32 + a launch of 4-lane tiles -- was built and measured SLOWER, 2^20 x 100:
+    // 0.79 -> 0.99 ms: the tail's logical columns are es * 4 bytes apart, 16-byte runs; profiles/r04_notes.md section 1).
+    uint32_t lsh = 0;
+    if (f.lane_native)
+      while ((2u << lsh) <= tmax && (1u << lsh) < f.ltot)
+        lsh++;
+    fp.lsh = lsh;
+    PassDesc pd = f.rn_native ? make_pass_rn(parts, P, p, in.log_max, tmax >> lsh) : make_pass(parts, P, p, in.n, in.log_max, tmax >> lsh);
+    // Few launch rows (16-64 interleaved transforms = one or two slices): adjacent logical columns that share a twiddle set
+    // run as launch rows of one block -- pass 0 (its inter-pass factor depends on column / cprime only) and the last pass
+    // (none at all); not the coset / bit-reversed-output variants, whose per-block constants depend on the column.
+    uint32_t cg = 1, ag = 1;
+    const uint32_t tcl = (uint32_t)pd.T; // logical columns in the LDS tile
+    {
+      // (only with full slices: grouping multiplies the mostly idle rows of a ragged last slice as well -- 2^20 x 100: 0.84 -> 0.89 ms)
+      const bool full = f.lane_native && f.fast && f.ltot % (1u << lsh) == 0;
+      // (RN: every pass can group adjacent logical columns -- the factor behind a pass is rebuilt per row, ntt_fast.hpp rn_rowfac)
+      const bool allowed = full && !cvar && (f.rn_native ? P >= 2 : ((p == 0 && P >= 2) || p == P - 1)); // (round 5: the bit-reversed-output store too)
+      const bool middle = full && !f.rn_native && P == 3 && p == 1; // groups over the outer index instead (NttLaunch::agrp)
+      const uint32_t rows_now = f.row_groups * ((f.ltot + (1u << lsh) - 1) >> lsh);
+      uint32_t want = 1;
+      while ((allowed || middle) && want * 2 <= in.cg_max && rows_now * want * 2 <= 8)
+        want *= 2;
+      if (middle) {
+        while (want > 1 && ((uint64_t)1 << parts[0]) % want != 0)
+          want >>= 1;
+        ag = want;
+        want = 1;
+        pd.ntiles /= ag; // tiles enumerate (a / ag, ct)
+      }
+      while (want > 1) {
+        const PassDesc pg = f.rn_native ? make_pass_rn(parts, P, p, in.log_max, tcl * want) : make_pass(parts, P, p, in.n, in.log_max, tcl * want);
+        if ((uint32_t)pg.T == tcl * want && (f.rn_native || pg.is_last || (uint32_t)pg.T <= pg.cprime)) {
+          pd = pg;
+          cg = want;
+          break;
+        }
+        want >>= 1;
+      }
+    }
+    fp.tcl = tcl, fp.cg = cg, fp.ag = ag;
+    NttLaunch nlp = nl;
+    if (f.pad_w) { // the work buffer's rows are es_w words apart, the caller's ltot
+      nlp.es = in.src_w ? f.es_w : nl.es;
+      nlp.es_out = in.dst_w ? f.es_w : nl.es;
+    }
+    if (f.lane_native) { // launch rows = slices of 2^lsh transforms
+      nlp.lsh = lsh;
+      nlp.ltot = f.ltot;
+      nlp.lanes = (f.ltot + (1u << lsh) - 1) >> lsh;
+      nlp.bs = in.n * in.lanes;
+      nlp.row0 = 0;
+      nlp.tcl = tcl;
+      nlp.cgrp = cg * ag;
+      nlp.agrp = ag;
+      const uint64_t es_in = nlp.es, es_out = nlp.es_out ? nlp.es_out : nlp.es; // (pad_w: each side with its own stride)
+      nlp.cst_in = ag > 1 ? pd.in_base_a * es_in : (uint64_t)tcl * pd.in_st * es_in;
+      if (f.rn_native) // (RN passes are in place: same layout both sides)
+        nlp.cst_out = nlp.cst_in;
+      else if (pd.is_last && nl.out_rev) // (the bit-reversed store computes the column's place itself, ntt_fast.hpp)
+        nlp.cst_out = 0;
+      else if (pd.is_last && ag == 1)
+        nlp.cst_out = (uint64_t)tcl * es_out;
+      else
+        nlp.cst_out = ag > 1 ? pd.in_base_a * es_out : (uint64_t)tcl * pd.in_st * es_out;
+      nlp.nrows_launch = f.row_groups * nlp.lanes * nlp.cgrp;
+    }
+    fp.pd = pd;
+    fp.nl = nlp;
+    return fp;
+  }
+
   // ---- one transform split over P device slots (ntt_split.hpp): N = 2^a * 2^b, both factors at least P wide ----
   struct SplitShape {
     int P, logn, a, b; // N1 = 2^a, N2 = 2^b

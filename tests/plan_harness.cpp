@@ -5,12 +5,16 @@
 #include "../icicle_amd/csrc/msm_plan.h"
 #include <cstdio>
 #include <vector>
+#include <algorithm>
 using namespace icicle_hip;
 
-static int check(int logn, int smax, uint32_t tmax_cap)
+static int check(int logn, int smax, uint32_t tmax_cap, bool ntt31)
 {
   int parts[3], P;
-  split_logn(logn, smax, parts, &P);
+  if (ntt31)
+    ntt_split_parts(logn, -1, parts, &P); // the 31-bit NTT's pass lengths (8,9,8 at 2^25)
+  else
+    split_logn(logn, smax, parts, &P); // ntt_big.hip
   int sum = 0;
   for (int i = 0; i < P; i++)
     sum += parts[i];
@@ -46,12 +50,197 @@ static int check(int logn, int smax, uint32_t tmax_cap)
   return 0;
 }
 
-extern "C" int plan_check(int max_logn)
+// max_logn: the 31-bit fields (up to 2^27, BabyBear's two-adicity: the 512-row passes from 2^25 up); max_logn_big: the 256-bit ones
+extern "C" int plan_check(int max_logn, int max_logn_big)
 {
-  for (int logn = 1; logn <= max_logn; logn++) {
-    if (int rc = check(logn, 8, 32)) return logn * 100 + rc;  // 31-bit fields
-    if (int rc = check(logn, 8, 4)) return logn * 100 + rc;   // 256-bit fields: tiles of at most 4 columns
+  for (int logn = 1; logn <= std::max(max_logn, max_logn_big); logn++) {
+    if (logn <= max_logn)
+      if (int rc = check(logn, 8, 32, true)) return logn * 100 + rc; // 31-bit fields
+    if (logn <= max_logn_big)
+      if (int rc = check(logn, 8, 4, false)) return logn * 100 + rc; // 256-bit fields: tiles of at most 4 columns
   }
+  return 0;
+}
+
+// ---- lane-native launch geometry (ntt_plan.h fast_pass_geometry, the code ntt_run launches with) -----------------------------
+// Grouping (cg adjacent logical columns in pass 0 / the last pass, ag adjacent outer indices in the middle pass) is a launch
+// optimisation only: it must not change which word any logical element is read from or written to. For every pass, launch row
+// (row group, slice, cs), tile, slot and live lane, the word address -- the kernels' formulas, k_ntt_fast LN -- is mapped back to
+// (row group, element j, lane l) of that side's buffer and must be the one the ungrouped pass (cg_max = 1, same function) gives
+// the same logical column / outer index; l < ltot (no padding lane), and the word lies inside the side's buffer.
+namespace lanecheck {
+  struct Side {
+    uint64_t es, cst; // element stride, group stride (words)
+  };
+  static uint64_t brev(uint64_t x, uint32_t bits)
+  {
+    uint64_t r = 0;
+    for (uint32_t i = 0; i < bits; i++)
+      r |= ((x >> i) & 1ull) << (bits - 1 - i);
+    return r;
+  }
+  // word of (launch row r, tile (a, ct) with a the kernel's first outer index, row k of the tile, logical column c of the
+  // LDS tile, lane of the slice) on side `out`
+  static uint64_t word(const FastPass& g, bool out, bool rn, uint32_t r, uint64_t a, uint64_t ct, uint64_t k, uint64_t c, uint32_t lane)
+  {
+    const PassDesc& pd = g.pd;
+    const NttLaunch& nl = g.nl;
+    const uint32_t cs = r % nl.cgrp, rs = r / nl.cgrp;
+    const uint64_t es = out ? (nl.es_out ? nl.es_out : nl.es) : nl.es;
+    const uint64_t roff = (uint64_t)(rs / nl.lanes) * nl.bs + ((uint64_t)(rs % nl.lanes) << nl.lsh) + (uint64_t)cs * (out ? nl.cst_out : nl.cst_in);
+    const uint64_t in_base = a * pd.in_base_a + ct * pd.in_base_ct;
+    uint64_t e;
+    if (!out || !pd.is_last || rn) { // column passes on both sides, the row pass's load (in_sk = 1)
+      e = in_base + k * pd.in_sk + c * pd.in_st;
+    } else {
+      const uint64_t K0 = (pd.pidx <= 1) ? (ct * pd.T + c) : (ct * pd.T + c + (uint64_t)pd.n0 * a);
+      if (nl.out_rev) // bitrev(K0 + cs * tcl + k * out_sk) = bitrev_s(k) + L * bitrev(K0 + cs * tcl): tile row k holds bitrev_s(k)
+        e = brev(K0 + (uint64_t)cs * nl.tcl, nl.logn - pd.s) * (1ull << pd.s) + k;
+      else
+        e = K0 + k * pd.out_sk;
+    }
+    return roff + e * es + lane;
+  }
+
+  struct Shape {
+    uint32_t logn, batch, lanes;
+    bool columns;
+    int ord; // 0 kNN, 1 kNR, 2 kRN, 3 kRR
+    bool coset, inverse;
+  };
+
+  static uint64_t rng_state = 0x9E3779B97F4A7C15ull;
+  static uint64_t rnd()
+  {
+    rng_state ^= rng_state << 13, rng_state ^= rng_state >> 7, rng_state ^= rng_state << 17;
+    return rng_state;
+  }
+
+  // 0 = every word right; else a code: 1 bad ungrouped plan, 2 lane out of range / padding lane, 3 outside the buffer,
+  // 4 grouped word differs from the ungrouped one, 5 a word of the full map touched twice, 6 a live word never touched
+  static int check_shape(const Shape& sh, bool sample)
+  {
+    int parts[3], P;
+    ntt_split_parts((int)sh.logn, -1, parts, &P);
+    const uint64_t n = 1ull << sh.logn;
+    NttLaunch nl{};
+    nl.logn = sh.logn, nl.n = n, nl.nbatch = sh.batch * sh.lanes, nl.lanes = sh.lanes;
+    nl.bs = sh.columns ? sh.lanes : n * sh.lanes;
+    nl.es = sh.columns ? (uint64_t)sh.batch * sh.lanes : sh.lanes;
+    nl.in_rev = sh.ord == 2 || sh.ord == 3, nl.out_rev = sh.ord == 1 || sh.ord == 3;
+    nl.inverse = sh.inverse, nl.coset = sh.coset, nl.log_max = 27;
+    const NttPlanFlags f = ntt_plan_flags(P, nl.in_rev, nl.out_rev, nl.coset, nl.inverse, sh.columns, sh.batch, sh.lanes, nl.es, true, true, true);
+    if (!f.lane_native) return 0;
+    if (f.prerev) nl.in_rev = 0; // (ntt_run: the passes see natural-order rows in the work buffer)
+    const uint32_t ltot = f.ltot;
+    for (int p = 0; p < P; p++) {
+      const bool src_w = !f.rn_native && (p > 0 || f.prerev), dst_w = !f.rn_native && p < P - 1; // (ntt_run's src / dst)
+      const FastPassIn gi{parts, P, p, n, 27, f, sh.lanes, src_w, dst_w, true, 8u};
+      FastPassIn ui = gi;
+      ui.cg_max = 1;
+      const FastPass G = fast_pass_geometry(nl, gi), U = fast_pass_geometry(nl, ui);
+      if (U.cg != 1 || U.ag != 1 || U.tcl != G.tcl || U.lsh != G.lsh || (uint32_t)U.pd.T != U.tcl || U.nl.cgrp != 1) return 1;
+      if (G.nl.cgrp != G.cg * G.ag || (uint32_t)G.pd.T != G.tcl * G.cg || (uint64_t)G.pd.ntiles * G.ag != U.pd.ntiles / G.cg) return 1;
+      const uint64_t L = 1ull << parts[p];
+      const uint32_t TL = 1u << G.lsh, slices = G.nl.lanes;
+      if (slices != (ltot + TL - 1) / TL || G.nl.nrows_launch != f.row_groups * slices * G.nl.cgrp) return 1;
+      for (int out = 0; out < 2; out++) {
+        const uint64_t es = out ? (G.nl.es_out ? G.nl.es_out : G.nl.es) : G.nl.es;
+        const uint64_t ues = out ? (U.nl.es_out ? U.nl.es_out : U.nl.es) : U.nl.es;
+        if (es != ues || es < ltot) return 1;
+        const uint64_t words = (uint64_t)f.row_groups * n * es;
+        // full word map: every live word once. Sampled: the first and last tile of every outer index a (of 16 spread over the range
+        // when there are more), plus 8 seeded tiles; the first and last slice and row group with every cs; in each tile the first
+        // and last logical column, rows 0, L - 1 and a seeded one, the first and last live lane
+        std::vector<uint8_t> seen;
+        if (!sample) seen.assign(words, 0);
+        std::vector<uint32_t> tiles, rows;
+        const uint32_t na = G.pd.ntiles / G.pd.tiles_per_a;
+        if (!sample) {
+          for (uint32_t t = 0; t < G.pd.ntiles; t++)
+            tiles.push_back(t);
+          for (uint32_t r = 0; r < G.nl.nrows_launch; r++)
+            rows.push_back(r);
+        } else {
+          const uint32_t nas = std::min<uint32_t>(na, 16);
+          for (uint32_t i = 0; i < nas; i++) {
+            const uint32_t ai = nas == 1 ? 0 : (uint32_t)((uint64_t)i * (na - 1) / (nas - 1));
+            tiles.push_back(ai * G.pd.tiles_per_a);
+            if (G.pd.tiles_per_a > 1) tiles.push_back(ai * G.pd.tiles_per_a + G.pd.tiles_per_a - 1);
+          }
+          for (int i = 0; i < 8; i++)
+            tiles.push_back((uint32_t)(rnd() % G.pd.ntiles));
+          for (uint32_t grp : {0u, f.row_groups - 1})
+            for (uint32_t sl : {0u, slices - 1})
+              for (uint32_t cs = 0; cs < G.nl.cgrp; cs++) {
+                const uint32_t r = (grp * slices + sl) * G.nl.cgrp + cs;
+                if (std::find(rows.begin(), rows.end(), r) == rows.end()) rows.push_back(r);
+              }
+        }
+        for (uint32_t r : rows) {
+          const uint32_t cs = r % G.nl.cgrp, rs = r / G.nl.cgrp, slice = rs % slices;
+          const uint32_t live = std::min<uint32_t>(TL, ltot - slice * TL);
+          for (uint32_t tile : tiles) {
+            const uint64_t a = (uint64_t)(tile / G.pd.tiles_per_a) * G.ag, ct = tile % G.pd.tiles_per_a;
+            // the same logical element in the ungrouped pass: column ct * T + cs * tcl + c (cg), outer index a + cs (ag)
+            const uint64_t ua = G.ag > 1 ? a + cs : a;
+            for (uint64_t c = 0; c < G.tcl; c += sample ? std::max<uint64_t>(1, G.tcl - 1) : 1) {
+              const uint64_t col = ct * G.pd.T + (G.cg > 1 ? (uint64_t)cs * G.tcl : 0) + c;
+              const uint64_t uct = col / U.tcl, uc = col % U.tcl;
+              if (ua * U.pd.tiles_per_a + uct >= U.pd.ntiles || uct >= U.pd.tiles_per_a) return 1;
+              const uint64_t ks[3] = {0, L - 1, rnd() % L};
+              for (uint64_t ki = 0; ki < (sample ? 3 : L); ki++) {
+                const uint64_t k = sample ? ks[ki] : ki;
+                for (uint32_t lane = 0; lane < live; lane += sample ? std::max<uint32_t>(1, live - 1) : 1) {
+                  const uint64_t w = word(G, out, f.rn_native, r, a, ct, k, c, lane);
+                  if (w >= words) return 3;
+                  const uint64_t grp = w / (n * es), j = (w % (n * es)) / es, l = w % es;
+                  if (l >= ltot || l != (uint64_t)slice * TL + lane || grp != rs / slices) return 2;
+                  const uint64_t wu = word(U, out, f.rn_native, rs, ua, uct, k, uc, lane);
+                  if (wu != w || j >= n) return 4;
+                  if (!sample && seen[w]++) return 5;
+                }
+              }
+            }
+          }
+        }
+        if (!sample) // every live word of the side once (the padding lanes never)
+          for (uint64_t w = 0; w < words; w++)
+            if ((w % es < ltot) != (seen[w] == 1)) return 6;
+      }
+    }
+    return 0;
+  }
+} // namespace lanecheck
+
+// Returns 0, or an encoded failing shape: code + 10 * (ord + 4 * (coset + 2 * inverse)) + 1000 * logn + 100000 * ltot
+// (+ 50000000 for the extension field, + 100000000 for row-major). Sizes up to 2^14 words get the full word map (each live word
+// exactly once), larger ones sampled tiles and rows of the tile.
+extern "C" int lane_plan_check(int min_logn, int max_logn)
+{
+  using namespace lanecheck;
+  std::vector<uint32_t> ltots;
+  for (uint32_t t = 2; t <= 160; t++)
+    ltots.push_back(t);
+  ltots.push_back(192), ltots.push_back(256);
+  for (uint32_t logn = (uint32_t)min_logn; logn <= (uint32_t)max_logn; logn++)
+    for (int mode = 0; mode < 12; mode++) { // (without a coset the direction changes no address: forward only)
+      const int ord = mode % 4;
+      const bool coset = mode >= 4, inverse = mode >= 8;
+      std::vector<Shape> shapes;
+      for (uint32_t t : ltots) {
+        shapes.push_back({logn, t, 1, true, ord, coset, inverse});                   // columns_batch, base field
+        if (t % 4 == 0) shapes.push_back({logn, t / 4, 4, true, ord, coset, inverse}); // columns_batch, extension
+      }
+      for (uint32_t b : {1u, 2u, 3u})
+        shapes.push_back({logn, b, 4, false, ord, coset, inverse}); // row-major extension rows: ltot = 4
+      for (const Shape& sh : shapes) {
+        const bool sample = (uint64_t)(1ull << logn) * sh.batch * sh.lanes > (1ull << 14);
+        if (int rc = check_shape(sh, sample))
+          return rc + 10 * (ord + 4 * ((int)coset + 2 * (int)inverse)) + 1000 * (int)logn + 100000 * (int)(sh.batch * (sh.columns ? sh.lanes : 1)) +
+                 (sh.lanes == 4 ? 50000000 : 0) + (sh.columns ? 0 : 100000000);
+      }
+    }
   return 0;
 }
 
