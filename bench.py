@@ -2,12 +2,18 @@
 """bench.py -- BN254 MSM 2^26 (primary, BASELINE.json configs[1]) + BabyBear NTT 2^24 x 64
 (secondary, configs[2]) on N MI355X, one process per GPU.
 
-  python bench.py --gpus 1 --steps K --warmup W [--dump-outputs DIR]
+  python bench.py --gpus 1 --steps K --warmup W [--dump-outputs DIR] [--full]
   python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
   python bench.py --gpus N ...      (no WORLD_SIZE in the environment: re-launches itself under torch.distributed.run;
                                      on a box with fewer than N GPUs it prints a JSON line with an "error" key, exit 0)
 
-At N > 1 the line carries a second object, "inproc": the same shard cut driven by ONE process through the C ABI
+A plain run does only what the headline figure needs: it sets up the MSM inputs, runs W warm-up and K timed steps, writes
+--dump-outputs if given (the NTT leg then runs as well, since its outputs are part of the dump) and prints the line.
+Everything else the benchmark measures or checks runs with --full only: the objects "ntt", "cpu_baseline",
+"config3_shard" / "config4_shard", the in-run ALU and gather roofs of "roofline", and at N > 1 "strong", "ntt_split",
+"inproc" and the cross-rank result check. The --no-* options below narrow a --full run.
+
+With --full at N > 1 the line carries a second object, "inproc": the same shard cut driven by ONE process through the C ABI
 (MSMConfig.ext / NTTConfig.ext "hip_num_devices" = N, one host thread + stream per GPU inside the call, in-library RCCL
 exchange, bases resident per GPU) -- what a Rust / Go / C++ caller of msm() / ntt() reaches. --no-inproc skips it.
 
@@ -16,14 +22,14 @@ one 2^26-term BN254 MSM per rank (weak scaling: the N shards form one 2^26*N-ter
 results are all-gathered over RCCL and summed on every rank). Timed region: barrier + synchronize on
 both sides, max over ranks. One JSON line on rank 0.
 
---scaling strong cuts ONE 2^26 MSM over the N GPUs instead (2^26/N pairs per rank, same exchange); the default (weak)
-line at N > 1 carries that figure as well, as the object "strong", so one invocation records both.
+--scaling strong cuts ONE 2^26 MSM over the N GPUs instead (2^26/N pairs per rank, same exchange); with --full the default
+(weak) line at N > 1 carries that figure as well, as the object "strong", so one invocation records both.
 
-Extra objects: "roofline" (dominant kernel = MSM bucket accumulation, duration from hipEvents on the
-launch stream, algorithmic bytes per SURVEY.md 8(d); its ALU and gather roofs are measured in the same
-run), "cpu_baseline" (the reference CPU backend from oracle/_ref timed on this box's host cores -- on
-the full workload when the host grants >= 16 cores of CPU time), "ntt" (secondary metric with its own
-roofline/cpu_baseline).  --size-log2 / --ntt-log2 shrink the workload for quick checks; the
+"roofline": dominant kernel = MSM bucket accumulation, duration from hipEvents on the launch stream during the timed steps,
+algorithmic bytes per SURVEY.md 8(d); --full adds its ALU and gather roofs, measured in the same run. --full objects:
+"cpu_baseline" (the reference CPU backend from oracle/_ref timed on this box's host cores -- on the full workload when the
+host grants >= 16 cores of CPU time), "ntt" (secondary metric with its own roofline/cpu_baseline), "config3_shard" /
+"config4_shard".  --size-log2 / --ntt-log2 shrink the workload for quick checks; the
 JSON then names the reduced workload (never reported as the headline config).
 
 --dump-outputs DIR writes, after the timed steps, what the last timed step computed (dump_outputs() below), so that two
@@ -54,6 +60,8 @@ def parse():
     ap.add_argument("--size-log2", type=int, default=26, help="MSM size per GPU (headline: 26)")
     ap.add_argument("--ntt-log2", type=int, default=24, help="NTT size (headline: 24)")
     ap.add_argument("--ntt-batch", type=int, default=64)
+    ap.add_argument("--full", action="store_true",
+                    help="also measure and check everything beyond the headline figure (NTT, roofs, CPU baseline, shard configs, N > 1 extras)")
     ap.add_argument("--no-ntt", action="store_true")
     ap.add_argument("--msm-c", type=int, default=0, help="force the MSM window size (0 = backend default)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
@@ -221,7 +229,7 @@ def _last_json_line(text):
 
 def launch_self(args):
     """`python bench.py --gpus N` with no rendezvous in the environment: run the one-process-per-GPU job under
-    torch.distributed.run ourselves, then (GPUs free again) the single-process hip_num_devices = N leg, and print ONE line."""
+    torch.distributed.run ourselves, then (--full, GPUs free again) the single-process hip_num_devices = N leg, and print ONE line."""
     import subprocess
 
     have = visible_gpus()
@@ -243,7 +251,7 @@ def launch_self(args):
     if out is None:
         out = {"metric": "bn254_msm_2^26_per_sec", "value": None, "unit": "MSM/s", "n_gpus": args.gpus,
                "error": f"one-process-per-GPU leg failed (rc {r.returncode}): " + (r.stderr or r.stdout)[-1500:]}
-    if not args.no_inproc:
+    if args.full and not args.no_inproc:
         try:
             r2 = subprocess.run([sys.executable, os.path.abspath(__file__)] + passthrough + ["--inproc-only"], capture_output=True, text=True,
                                 env=env, timeout=240)
@@ -479,17 +487,18 @@ def main():
     lib.icicle_hip_enable_kernel_timing(False)
     msm_ms = dt / args.steps * 1e3
     dumps = msm_dump_arrays(res) if args.dump_outputs and rank == 0 else None  # the last timed step's result
-    # ---- what the collectives layer saw: recorded in the line, and the gathered result must be the SAME bytes
-    # on every rank (each rank sums the all-gathered partials itself: same inputs, same deterministic kernel)
+    # ---- what the collectives layer saw: recorded in the line, and (--full) the gathered result must be the SAME
+    # bytes on every rank (each rank sums the all-gathered partials itself: same inputs, same deterministic kernel)
     collectives = {"world_size": world, "backend": None, "rccl_version": None}
     try:
         collectives["rccl_version"] = ".".join(str(v) for v in torch.cuda.nccl.version())
     except Exception as e:
         collectives["rccl_version"] = f"unavailable: {e!r}"
     if world > 1:
+        collectives["world_size"] = dist.get_world_size()
+        collectives["backend"] = dist.get_backend()
+    if world > 1 and args.full:
         try:
-            collectives["world_size"] = dist.get_world_size()
-            collectives["backend"] = dist.get_backend()
             mine = {"rank": rank, "local_rank": local_rank, "device": torch.cuda.current_device(), "name": torch.cuda.get_device_name(),
                     "icicle_device": runtime.get_active_device() if hasattr(runtime, "get_active_device") else None}
             seen = [None] * world
@@ -557,32 +566,33 @@ def main():
             roofline["traffic_unit"] = f"GB per launch (FETCH_SIZE x calibration + WRITE_SIZE, profiles/{pmc['_file']}, kernel sources {msm_sha})"
         else:
             roofline["traffic_note"] = f"profiles/{pmc.get('_file')} was taken on other kernel sources ({pmc.get('msm_sources_sha16')} != {msm_sha}): not attached"
-    # secondary: integer-ALU view. mixed adds per MSM = n * windows; 8M + 2S field operations each. The roof is
-    # measured in this run: the same ec.hpp mixed add with every operand in registers (no memory traffic at all).
     pc, pw = ctypes.c_int(), ctypes.c_int()
-    pcfg = MSMConfig.default()
-    pcfg.c = args.msm_c
-    check(lib.icicle_hip_msm_plan(n, 254, ctypes.byref(pcfg), ctypes.byref(pc), ctypes.byref(pw)), "msm_plan")
-    madds = n * pw.value
     rate = ctypes.c_double()
-    check(lib.icicle_hip_ubench_mixed_add(0, ctypes.byref(rate)), "ubench_mixed_add")
-    roofline["alu"] = {"window_bits": pc.value, "windows": pw.value, "mixed_adds": madds,
-                       "mixed_adds_per_s": madds / (acc_ms * 1e-3), "roof": rate.value,
-                       "frac": madds / (acc_ms * 1e-3) / rate.value,
-                       "roof_is": "XYZZ mixed adds/s, operands in registers, measured in this run (icicle_hip_ubench_mixed_add)",
-                       # the hardware's own figure beside the self-referential one: pure v_mad_u64_u32 issue. 1024 SIMDs x f / 6.05
-                       # cycles per wave-instruction x 64 lanes / 1467 mads per mixed add (profiles/r02_alu_ubench.txt); f = 2.4 GHz
-                       # nominal. Under this all-mad load the chip sustains ~0.83 of the clock it holds half-loaded
-                       # (profiles/r03_notes.md section 1), i.e. ~14.7e9/s.
-                       "hw_roof_nominal_clock": 1024 * 2.4e9 / 6.05 * 64 / 1467,
-                       "hw_frac_nominal_clock": madds / (acc_ms * 1e-3) / (1024 * 2.4e9 / 6.05 * 64 / 1467),
-                       "hw_roof_is": "v_mad_u64_u32 issue roof: 1024 SIMDs x 2.4 GHz / 6.05 cycles x 64 lanes / 1467 mads per mixed add"}
-    # every mixed add gathers one 64-byte point at a random address of the bases array: ceiling of that access pattern
-    # over a region of the same size, measured in this run
-    check(lib.icicle_hip_ubench_gather(max(64, n * 64), 1 << 27, ctypes.byref(rate)), "ubench_gather")
-    roofline["gather"] = {"gathers_per_s": madds / (acc_ms * 1e-3), "measured_ceiling": rate.value,
-                          "frac": madds / (acc_ms * 1e-3) / rate.value,
-                          "unit": f"random 64-byte gathers/s over {n * 64 / 2**30:.2f} GiB, measured in this run"}
+    if args.full:  # the roofs take runs of their own
+        # secondary: integer-ALU view. mixed adds per MSM = n * windows; 8M + 2S field operations each. The roof is
+        # measured in this run: the same ec.hpp mixed add with every operand in registers (no memory traffic at all).
+        pcfg = MSMConfig.default()
+        pcfg.c = args.msm_c
+        check(lib.icicle_hip_msm_plan(n, 254, ctypes.byref(pcfg), ctypes.byref(pc), ctypes.byref(pw)), "msm_plan")
+        madds = n * pw.value
+        check(lib.icicle_hip_ubench_mixed_add(0, ctypes.byref(rate)), "ubench_mixed_add")
+        roofline["alu"] = {"window_bits": pc.value, "windows": pw.value, "mixed_adds": madds,
+                           "mixed_adds_per_s": madds / (acc_ms * 1e-3), "roof": rate.value,
+                           "frac": madds / (acc_ms * 1e-3) / rate.value,
+                           "roof_is": "XYZZ mixed adds/s, operands in registers, measured in this run (icicle_hip_ubench_mixed_add)",
+                           # the hardware's own figure beside the self-referential one: pure v_mad_u64_u32 issue. 1024 SIMDs x f / 6.05
+                           # cycles per wave-instruction x 64 lanes / 1467 mads per mixed add (profiles/r02_alu_ubench.txt); f = 2.4 GHz
+                           # nominal. Under this all-mad load the chip sustains ~0.83 of the clock it holds half-loaded
+                           # (profiles/r03_notes.md section 1), i.e. ~14.7e9/s.
+                           "hw_roof_nominal_clock": 1024 * 2.4e9 / 6.05 * 64 / 1467,
+                           "hw_frac_nominal_clock": madds / (acc_ms * 1e-3) / (1024 * 2.4e9 / 6.05 * 64 / 1467),
+                           "hw_roof_is": "v_mad_u64_u32 issue roof: 1024 SIMDs x 2.4 GHz / 6.05 cycles x 64 lanes / 1467 mads per mixed add"}
+        # every mixed add gathers one 64-byte point at a random address of the bases array: ceiling of that access pattern
+        # over a region of the same size, measured in this run
+        check(lib.icicle_hip_ubench_gather(max(64, n * 64), 1 << 27, ctypes.byref(rate)), "ubench_gather")
+        roofline["gather"] = {"gathers_per_s": madds / (acc_ms * 1e-3), "measured_ceiling": rate.value,
+                              "frac": madds / (acc_ms * 1e-3) / rate.value,
+                              "unit": f"random 64-byte gathers/s over {n * 64 / 2**30:.2f} GiB, measured in this run"}
     check(lib.icicle_hip_release_workspace(), "release_workspace")
 
     out = {
@@ -603,8 +613,8 @@ def main():
 
     # ---------------- N > 1, default (weak) line: the STRONG figure in the same invocation ----------------
     # ONE 2^size MSM cut over the N GPUs (2^size / N pairs per rank, a prefix of this rank's resident inputs; same exchange),
-    # so that a single driver run records both scaling modes. Never costs the primary line.
-    if world > 1 and not strong and os.environ.get("ICICLE_BENCH_STRONG", "1") == "1":
+    # so that a single driver run records both scaling modes. --full only; never costs the primary line.
+    if world > 1 and args.full and not strong and os.environ.get("ICICLE_BENCH_STRONG", "1") == "1":
         import threading
 
         strong_done = threading.Event()
@@ -645,8 +655,9 @@ def main():
             strong_done.set()
             strong_watchdog.cancel()
 
-    # ---------------- NTT secondary ----------------
-    if not args.no_ntt:
+    # ---------------- NTT secondary: --full, or for the outputs --dump-outputs writes (the same on every rank) ----------------
+    run_ntt = not args.no_ntt and (args.full or args.dump_outputs is not None)
+    if run_ntt:
         logn, batch = args.ntt_log2, args.ntt_batch
         lo, hi = D.ntt_batch_shard(batch * world, rank, world)  # weak scaling: `batch` rows per GPU
         rows = hi - lo
@@ -700,23 +711,24 @@ def main():
                          "avg_launch_ms": ntt_call_ms, "launches": cnt.value},
         }
         # VALU-issue roof beside the HBM fraction: the butterfly arithmetic of the passes with every operand in
-        # registers, measured in this run. Unit: 16 elements through one 8-stage pass (2 radix-16 register rounds + 16 products with
-        # the factor behind the pass); a direction is rows * N * log2(N) / 128 of them.
-        try:
-            rate = ctypes.c_double()
-            check(lib.icicle_hip_ubench_ntt_pass(0, ctypes.byref(rate)), "ubench_ntt_pass")
-            units = rows * nn * logn / 128.0
-            alu_frac = units / (ntt_call_ms * 1e-3) / rate.value
-            hbm_copy_frac = ntt_bytes * ((logn + 7) // 8) / (ntt_call_ms * 1e-3) / 1e9 / 6290.0
-            out["ntt"]["roofline"]["alu"] = {
-                "pass_units": units, "pass_units_per_s": units / (ntt_call_ms * 1e-3), "roof": rate.value, "frac": alu_frac,
-                "roof_ms_per_direction": units / rate.value * 1e3,
-                "roof_is": "16-element x 8-stage pass units/s, operands in registers, measured in this run (icicle_hip_ubench_ntt_pass: k_ntt_fast's own ntt_stages code)",
-                "hbm_passes": (logn + 7) // 8, "hbm_traffic_frac_of_measured_copy": hbm_copy_frac,
-                "binds": "alu" if alu_frac >= hbm_copy_frac else "hbm",
-                "binds_note": "frac = share of the VALU-issue roof; hbm_traffic_frac_of_measured_copy = (passes x algorithmic bytes) / time / 6.29 TB/s (the guide's measured float4 copy)"}
-        except Exception as e:
-            out["ntt"]["roofline"]["alu"] = {"error": repr(e)}
+        # registers, measured in this run (--full). Unit: 16 elements through one 8-stage pass (2 radix-16 register rounds + 16 products
+        # with the factor behind the pass); a direction is rows * N * log2(N) / 128 of them.
+        if args.full:
+            try:
+                rate = ctypes.c_double()
+                check(lib.icicle_hip_ubench_ntt_pass(0, ctypes.byref(rate)), "ubench_ntt_pass")
+                units = rows * nn * logn / 128.0
+                alu_frac = units / (ntt_call_ms * 1e-3) / rate.value
+                hbm_copy_frac = ntt_bytes * ((logn + 7) // 8) / (ntt_call_ms * 1e-3) / 1e9 / 6290.0
+                out["ntt"]["roofline"]["alu"] = {
+                    "pass_units": units, "pass_units_per_s": units / (ntt_call_ms * 1e-3), "roof": rate.value, "frac": alu_frac,
+                    "roof_ms_per_direction": units / rate.value * 1e3,
+                    "roof_is": "16-element x 8-stage pass units/s, operands in registers, measured in this run (icicle_hip_ubench_ntt_pass: k_ntt_fast's own ntt_stages code)",
+                    "hbm_passes": (logn + 7) // 8, "hbm_traffic_frac_of_measured_copy": hbm_copy_frac,
+                    "binds": "alu" if alu_frac >= hbm_copy_frac else "hbm",
+                    "binds_note": "frac = share of the VALU-issue roof; hbm_traffic_frac_of_measured_copy = (passes x algorithmic bytes) / time / 6.29 TB/s (a measured float4 copy on MI355X)"}
+            except Exception as e:
+                out["ntt"]["roofline"]["alu"] = {"error": repr(e)}
         if logn == 24 and rows == 64 and "ntt_babybear_2^24x64_one_direction" in pmc:
             if pmc.get("ntt_sources_sha16") == ntt_sha and ntt_sha:
                 m = pmc["ntt_babybear_2^24x64_one_direction"]
@@ -728,8 +740,8 @@ def main():
 
     # ---------------- N > 1 only: ONE large NTT split over the ranks (4-step, all-to-all over RCCL/xGMI) -----
     # Guarded twice: an exception only costs this extra object, and a collective that stalls (nothing a single-GPU
-    # box can rehearse) trips a watchdog that prints the primary line without it. ICICLE_BENCH_NTT_SPLIT=0 skips it.
-    if world > 1 and not args.no_ntt and os.environ.get("ICICLE_BENCH_NTT_SPLIT", "1") == "1":
+    # box can rehearse) trips a watchdog that prints the primary line without it. --full only; ICICLE_BENCH_NTT_SPLIT=0 skips it.
+    if world > 1 and args.full and not args.no_ntt and os.environ.get("ICICLE_BENCH_NTT_SPLIT", "1") == "1":
         import threading
 
         split_done = threading.Event()
@@ -773,8 +785,8 @@ def main():
     # ---------------- N = 1: the per-GPU shares of BASELINE configs[3] and [4] ----------------
     # configs[3] = BLS12-381 MSM 2^28 over 8 GPUs -> 2^25 terms per GPU; configs[4] = KoalaBear NTT 2^22 x 1024 over 8 GPUs -> 128 rows
     # per GPU. Same measurement as the headline objects (hipEvents on the launch stream, roofs measured in this run); reproducible
-    # from profiles/r06_config3_shard_* / r06_config4_shard_*. Never costs the primary line.
-    if world == 1 and not args.no_shard_extras and args.size_log2 == 26 and args.ntt_log2 == 24:
+    # from profiles/r06_config3_shard_* / r06_config4_shard_*. --full only; never costs the primary line.
+    if world == 1 and args.full and not args.no_shard_extras and args.size_log2 == 26 and args.ntt_log2 == 24:
         try:
             n3 = 1 << 25
             b3 = torch.empty((n3, 24), dtype=torch.int32, device=dev)
@@ -866,8 +878,8 @@ def main():
     # ---------------- CPU baseline: the reference CPU backend on this box's host cores ----------------
     # On a host that grants >= 16 cores of CPU time (the GPU boxes: 256 visible threads, a cgroup quota of 16 cores) the baseline is timed
     # on the REAL workload: the full 2^26 MSM (about half a minute) and full-size NTT rows; on small hosts a 2^20 sample is timed and the
-    # JSON says so.
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    # JSON says so. --full only.
+    if rank == 0 and world == 1 and args.full and not args.no_cpu_baseline:
         try:
             from oracle import ref
 
@@ -901,7 +913,7 @@ def main():
                 "timed_on_full_workload": full, "parity_with_gpu_on_sample": parity,
             }
             del hb, hs
-            if not args.no_ntt:
+            if run_ntt:
                 rf = ref.RefNttField("babybear")
                 cl = args.cpu_ntt_log2 or (args.ntt_log2 if big_host else min(20, args.ntt_log2))
                 rf.init_domain(rf.get_root_of_unity(1 << cl))
@@ -933,11 +945,11 @@ def main():
 
     # ---------------- N > 1 under an external launcher: the single-process hip_num_devices = N leg ----------------
     # (when bench.py launched the ranks itself, launch_self() runs this leg after they have exited.) Every rank gives
-    # its device memory back first; rank 0 then runs the leg in a child process with the launcher's variables removed.
-    if world > 1 and not args.no_inproc:
+    # its device memory back first; rank 0 then runs the leg in a child process with the launcher's variables removed. --full only.
+    if world > 1 and args.full and not args.no_inproc:
         try:
             del scalars, bases
-            if not args.no_ntt:
+            if run_ntt:
                 del x, y, z
             torch.cuda.empty_cache()
             lib.icicle_hip_release_workspace()

@@ -58,7 +58,7 @@ def test_bench_inprocess_leg_rehearsed_on_virtual_slots():
 
 @pytest.mark.gpu
 def test_bench_one_process_per_gpu_leg_rehearsed_with_two_ranks():
-    """`bench.py --gpus 2` end to end on the ONE GPU of the test box -- the self-launch under
+    """`bench.py --gpus 2 --full` end to end on the ONE GPU of the test box -- the self-launch under
     torch.distributed.run, two ranks (sharing GPU 0, collectives over gloo: ICICLE_BENCH_GLOO_REHEARSAL), the weak line, the
     strong object, the split transform with its all-to-alls, the watchdogs, and the in-process leg (virtual slots) -- so that
     every line of the N > 1 path has executed before the driver's 8-GPU node runs it over RCCL."""
@@ -66,7 +66,7 @@ def test_bench_one_process_per_gpu_leg_rehearsed_with_two_ranks():
     env["ICICLE_BENCH_GLOO_REHEARSAL"] = "1"
     env["ICICLE_BENCH_INPROC_VIRTUAL"] = "1"
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1", "--size-log2", "18",
-                        "--ntt-log2", "16", "--ntt-batch", "8"], capture_output=True, text=True, env=env, timeout=900)
+                        "--ntt-log2", "16", "--ntt-batch", "8", "--full"], capture_output=True, text=True, env=env, timeout=900)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [ln for ln in r.stdout.strip().splitlines() if ln.startswith("{")]
     assert len(lines) == 1, r.stdout[-3000:]
@@ -115,3 +115,36 @@ def test_bench_dump_outputs_are_the_last_steps_results_and_repeat(tmp_path):
     assert a["ntt_forward_sample.npy"].max() < pyref.BABYBEAR.p and a["ntt_inverse_sample.npy"].max() < pyref.BABYBEAR.p
     for n in sorted(a):
         assert np.array_equal(a[n], dumped[1][n]), n
+
+
+@pytest.mark.gpu
+def test_bench_plain_run_is_the_headline_alone_and_full_adds_the_rest():
+    """A plain `bench.py --gpus 1` run prints the headline line and nothing it does not need; `--full` adds the NTT secondary
+    metric, the in-run ALU and gather roofs and the CPU baseline, as every run did before --full existed"""
+    from oracle import ref
+
+    env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT")}
+
+    def run(*extra):
+        r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "2", "--warmup", "1", "--size-log2", "16",
+                            "--ntt-log2", "14", "--ntt-batch", "4", *extra], capture_output=True, text=True, env=env, timeout=600)
+        assert r.returncode == 0, r.stderr[-3000:]
+        lines = [ln for ln in r.stdout.strip().splitlines() if ln.startswith("{")]
+        assert len(lines) == 1, r.stdout[-3000:]
+        out = json.loads(lines[0])
+        assert "error" not in out, out
+        assert out["metric"] == "bn254_msm_2^26_per_sec" and out["unit"] == "MSM/s" and out["higher_is_better"] is True
+        assert out["steps"] == 2 and out["warmup"] == 1 and out["ms_per_step"] > 0 and out["value"] > 0 and out["dtype"]
+        assert out["roofline"]["launches"] > 0 and out["roofline"]["avg_launch_ms"] > 0
+        return out
+
+    plain = run()
+    assert not {"ntt", "cpu_baseline", "config3_shard", "config4_shard", "dump_outputs"} & set(plain), sorted(plain)
+    assert not {"alu", "gather"} & set(plain["roofline"])
+    full = run("--full")
+    assert full["ntt"]["roundtrip_ok"] is True and full["ntt"]["value"] > 0 and full["ntt"]["roofline"]["alu"]["roof"] > 0
+    assert full["roofline"]["alu"]["roof"] > 0 and full["roofline"]["gather"]["measured_ceiling"] > 0
+    assert "cpu_baseline" in full
+    if ref.available("bn254") and ref.available("babybear"):
+        assert full["cpu_baseline"]["parity_with_gpu_on_sample"] is True, full["cpu_baseline"]
+        assert full["ntt"]["cpu_baseline"]["parity_with_gpu_on_sample"] is True, full["ntt"]["cpu_baseline"]

@@ -3,7 +3,7 @@ cd $GRAFT_REPO_ROOT
 O=gpurun_out/r06b; mkdir -p $O
 ( time timeout 2400 python -m pytest tests -q -m gpu -x --durations=15 ) > $O/gpu_pytest.txt 2>&1; echo "pytest rc=$?"
 tail -30 $O/gpu_pytest.txt
-python bench.py 2>$O/bench.err | grep '^{"metric"' > $O/bench.json; echo "bench rc=$?"; tail -3 $O/bench.err
+python bench.py --full 2>$O/bench.err | grep '^{"metric"' > $O/bench.json; echo "bench rc=$?"; tail -3 $O/bench.err
 python tools/bench_brief.py plain < $O/bench.json
 python - <<'PY' $O/bench.json
 import json,sys

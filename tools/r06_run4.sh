@@ -5,7 +5,7 @@ timeout 1500 python -m pytest tests/test_gpu_ntt_refspace.py tests/test_gpu_ecnt
 timeout 900 python -m pytest tests/test_gpu_multi_rehearsal.py tests/test_gpu_msm.py -q -k "peer or combine or refuses or precompute or mixed or table" 2>&1 | tail -15 | cut -c1-2500 | tee $O/pytest_msm_new.txt
 timeout 300 python tools/perf_matrix.py ecntt 2>/dev/null | grep -v amdgpu.ids | tee $O/ecntt_glv.txt
 for v in 1 0; do echo "ICICLE_HIP_NTT_PAD_LANES=$v"; ICICLE_HIP_NTT_PAD_LANES=$v timeout 300 python tools/perf_matrix.py layouts 2>/dev/null | grep -v amdgpu.ids; done | tee $O/layouts_pad_ab.txt
-for v in 1 0 1 0; do echo "ICICLE_HIP_MSM_REDUCE_BALANCE=$v"; ICICLE_HIP_MSM_REDUCE_BALANCE=$v python bench.py --no-cpu-baseline --no-shard-extras --no-ntt 2>/dev/null | grep '^{"metric"' | python -c "import json,sys; d=json.load(sys.stdin); print(round(d['ms_per_step'],2), d['roofline']['phases_ms'], 'roof', round(d['roofline']['alu']['roof']/1e9,2))"; done | tee $O/reduce_balance_ab.txt
+for v in 1 0 1 0; do echo "ICICLE_HIP_MSM_REDUCE_BALANCE=$v"; ICICLE_HIP_MSM_REDUCE_BALANCE=$v python bench.py --full --no-cpu-baseline --no-shard-extras --no-ntt 2>/dev/null | grep '^{"metric"' | python -c "import json,sys; d=json.load(sys.stdin); print(round(d['ms_per_step'],2), d['roofline']['phases_ms'], 'roof', round(d['roofline']['alu']['roof']/1e9,2))"; done | tee $O/reduce_balance_ab.txt
 for w in 2 3 2 3; do echo "bls12_381 2^25 ICICLE_HIP_MSM_ACC_WAVES=$w"; ICICLE_HIP_MSM_ACC_WAVES=$w python - <<'PY'
 import sys, os, time, ctypes
 sys.path.insert(0, os.getcwd())
