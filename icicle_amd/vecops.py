@@ -81,6 +81,16 @@ def scalar_mul_vec(field, scalars, b, cfg=None, out=None, size=None):
     return _vec2("scalar_mul_vec", field, scalars, b, size, cfg, out)
 
 
+def scalar_add_vec(field, scalars, b, cfg=None, out=None, size=None):
+    """scalar[k] + b[i] for every element of batch entry k; scalars: one per batch entry"""
+    return _vec2("scalar_add_vec", field, scalars, b, size, cfg, out)
+
+
+def scalar_sub_vec(field, scalars, b, cfg=None, out=None, size=None):
+    """scalar[k] - b[i] (the scalar is the minuend); scalars: one per batch entry"""
+    return _vec2("scalar_sub_vec", field, scalars, b, size, cfg, out)
+
+
 def bit_reverse(field, inp, cfg=None, out=None, size=None):
     cfg = cfg or VecOpsConfig.default()
     ip, cfg.is_a_on_device = _ptr(inp)

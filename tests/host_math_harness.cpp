@@ -4,49 +4,19 @@
 // Not part of the shipped library; nothing in icicle_amd/ links it.
 #include <cstdint>
 #include <cstring>
-#include "../icicle_amd/csrc/ec.hpp"
-#include "../icicle_amd/csrc/smallfield.hpp"
-#include "../icicle_amd/csrc/goldfield.hpp"
+#include "math_cases.hpp"
 #include "../icicle_amd/csrc/glv.hpp"
 #include "../icicle_amd/csrc/ec_dbl_quad.hpp"
 
 using namespace icicle_hip;
 
 namespace {
+  // the case bodies shared with the device harness live in math_cases.hpp
   template <class PR>
   int field_op(int op, const uint32_t* a, const uint32_t* b, uint32_t* out)
   {
-    using F = FieldOps<PR>;
-    typename F::fe x = F::from_canonical(a), y = F::from_canonical(b), r;
-    switch (op) {
-    case 0: r = F::mul(x, y); break;
-    case 1: r = F::sqr(x); break;
-    case 2: r = F::add(x, y); break;
-    case 3: r = F::template sub<2>(x, y); break;
-    case 4: r = F::template neg<2>(x); break;
-    case 5: { // stress lazy bounds: ((x+y)+(x+y)) * (x - y + 8p) ...
-      auto s = F::add(F::add(x, y), F::add(x, y));
-      auto d = F::template sub<8>(x, F::add(F::add(y, y), F::add(y, y)));
-      r = F::mul(s, d); // 2(x+y)(x-4y)
-      break;
-    }
-    case 6: { // from reference-Montgomery words -> canonical
-      r = F::from_refmont(a);
-      break;
-    }
-    case 7: { // canonical -> reference-Montgomery words
-      F::to_refmont(out, x);
-      return 0;
-    }
-    case 8: { // is_zero(x - y)
-      out[0] = F::is_zero(F::template sub<2>(x, y)) ? 1 : 0;
-      return 0;
-    }
-    case 9: r = F::inv(x); break; // x^(p-2); 0 -> 0 (the reference's inverse(0) = 0, projective.h:55-59)
-    default: return -1;
-    }
-    F::to_canonical(out, r);
-    return 0;
+    if (op < 0 || op > 9) return -1;
+    return math_cases::field_case<FieldOps<PR>>(op, a, b, a, b, out);
   }
 
   // points: affine canonical words (x,y); identity (0,0)
@@ -56,7 +26,6 @@ namespace {
     using E = EC<C>;
     using F = typename E::F;
     constexpr int N32 = E::N32;
-    // Montgomery-form affine point (cold kernels: precompute, generator, complete adds)
     auto load = [&](const uint32_t* w) {
       typename E::Aff a;
       a.x = F::from_canonical(w);
@@ -64,70 +33,13 @@ namespace {
       return a;
     };
     switch (op) {
-    case 0: { // XYZZ accumulate all points (aux[i]&1 = negate), output projective canonical
-      typename E::XYZZ acc;
-      bool empty = true;
-      for (int i = 0; i < n; i++) {
-        const uint32_t* w = pts + (size_t)i * 2 * N32;
-        if (E::words_are_zero(w)) continue;
-        // the hot loop consumes the canonical words exactly as they lie in HBM (ec.hpp scaling convention)
-        auto a = E::cneg(E::load_plain(w), aux && (aux[i] & 1));
-        E::madd(acc, empty, a);
-      }
-      E::store_proj_canonical(out, E::to_proj(acc, empty));
-      return 0;
-    }
-    case 1: { // complete projective sum of all points (identity allowed)
-      auto acc = E::proj_identity();
-      for (int i = 0; i < n; i++) {
-        const uint32_t* w = pts + (size_t)i * 2 * N32;
-        if (E::words_are_zero(w)) {
-          acc = E::add(acc, E::proj_identity());
-          continue;
-        }
-        acc = E::add(acc, E::to_proj(E::cneg(load(w), aux && (aux[i] & 1))));
-      }
-      E::store_proj_canonical(out, acc);
-      return 0;
-    }
-    case 2: { // mul_small: aux[0] * pts[0]
-      auto p = E::words_are_zero(pts) ? E::proj_identity() : E::to_proj(load(pts));
-      E::store_proj_canonical(out, E::mul_small(p, aux[0]));
-      return 0;
-    }
-    case 3: { // generator
-      E::store_proj_canonical(out, E::to_proj(E::generator()));
-      return 0;
-    }
-    case 4: { // repeated doubling: 2^aux[0] * pts[0] via complete dbl
-      auto p = E::to_proj(load(pts));
-      for (uint32_t i = 0; i < aux[0]; i++)
-        p = E::dbl(p);
-      E::store_proj_canonical(out, p);
-      return 0;
-    }
-    case 5: { // the window-combine chain: 2^aux[0] * pts[0] via to_jac / dbl_jac / from_jac
-      auto p = E::words_are_zero(pts) ? E::proj_identity() : E::add(E::to_proj(load(pts)), E::proj_identity()); // a non-trivial Z
-      auto j = E::to_jac(p);
-      for (uint32_t i = 0; i < aux[0]; i++)
-        j = E::dbl_jac(j);
-      E::store_proj_canonical(out, E::from_jac(j));
-      return 0;
-    }
-    case 6: { // msm_precompute_bases' chain: 2^aux[0] * pts[0] via dbl_jac_lazy from Z = 1, reduced at the end (bounds tracked)
-      if (E::words_are_zero(pts)) {
-        E::store_proj_canonical(out, E::proj_identity());
-        return 0;
-      }
-      typename E::Jac j;
-      const auto a = load(pts);
-      j.x = a.x, j.y = a.y, j.z = F::one();
-      for (uint32_t i = 0; i < aux[0]; i++)
-        j = E::dbl_jac_lazy(j);
-      j.x = F::reduce(j.x), j.y = F::reduce(j.y), j.z = F::reduce(j.z);
-      E::store_proj_canonical(out, E::from_jac(j));
-      return 0;
-    }
+    case 0:
+    case 1:
+    case 2:
+    case 3:
+    case 4:
+    case 5:
+    case 6: return math_cases::ec_case<C>(op, pts, n, aux, out);
     case 7: { // the ECNTT butterflies' scalar multiplication (ecntt.hip mul_words_quad, one lane's arithmetic): aux[0..7] * pts[0] by the GLV
               // split, 33 joint four-bit windows, four lazily reduced doublings per window with Y brought back below 4p for the complete addition
       if constexpr (C::EXT_DEGREE == 1) {
@@ -280,23 +192,62 @@ extern "C" int host_ec_op(int curve, int op, const uint32_t* pts, int n, const u
 // 31-bit fields
 extern "C" int host_small_op(int field, int op, uint32_t a, uint32_t b, uint32_t* out)
 {
-  auto run = [&](auto tag) {
-    using S = SmallField<decltype(tag)>;
-    uint32_t x = S::to_mont(a), y = S::to_mont(b), r;
-    switch (op) {
-    case 0: r = S::mul(x, y); break;
-    case 1: r = S::add(x, y); break;
-    case 2: r = S::sub(x, y); break;
-    case 3: r = S::pow(x, b); break; // x^b (b plain integer)
-    case 4: r = S::inv(x); break;
-    default: return -1;
-    }
-    *out = S::from_mont(r);
-    return 0;
-  };
+  if (op < 0 || op > 4) return -1;
   switch (field) {
-  case 0: return run(babybear_params{});
-  case 1: return run(koalabear_params{});
+  case 0: return math_cases::small_case<babybear_params>(op, a, b, out);
+  case 1: return math_cases::small_case<koalabear_params>(op, a, b, out);
   }
   return -1;
+}
+
+// ---- batched twins of the device harness's entry points (tests/device_math_harness.hip): same arguments, same case bodies,
+// one tuple after the other on the host, the bound tracker asserting every precondition ----------------------------------------
+extern "C" int host_field_canon(int field, int op, int n, const uint32_t* a, const uint32_t* b, const uint32_t* c, const uint32_t* d, uint32_t* out)
+{
+  return math_cases::with_field(field, [&](auto tag) {
+    using F = typename decltype(tag)::type;
+    constexpr size_t W = F::N32;
+    for (size_t t = 0; t < (size_t)n; t++)
+      if (int e = math_cases::field_case<F>(op, a + t * W, b + t * W, c + t * W, d + t * W, out + t * W)) return e;
+    return 0;
+  });
+}
+
+extern "C" int host_field_raw(int field, int op, int K, const int* kb, int n, const uint32_t* a, const uint32_t* b, const uint32_t* c, const uint32_t* d,
+                              uint32_t* out)
+{
+  return math_cases::with_raw_field(field, [&](auto tag) {
+    using F = typename decltype(tag)::type;
+    if constexpr (math_cases::is_gold<F>::value || F::N32 > F::N) {
+      return -1;
+    } else {
+      constexpr size_t N = F::N;
+      for (size_t t = 0; t < (size_t)n; t++)
+        if (int e = math_cases::raw_case<F>(op, K, kb, a + t * N, b + t * N, c + t * N, d + t * N, out + t * N)) return e;
+      return 0;
+    }
+  });
+}
+
+extern "C" int host_small_batch(int field, int op, int n, const uint32_t* a, const uint32_t* b, uint32_t* out)
+{
+  for (int t = 0; t < n; t++) {
+    int e = field == 0 ? math_cases::small_case<babybear_params>(op, a[t], b[t], out + t)
+                       : (field == 1 ? math_cases::small_case<koalabear_params>(op, a[t], b[t], out + t) : -1);
+    if (e) return e;
+  }
+  return 0;
+}
+
+// sequence s holds the points offs[s] .. offs[s+1]-1 (and the aux words of the same indices); 3 * E::N32 words out per sequence
+extern "C" int host_ec_batch(int curve, int op, int nseq, const uint32_t* pts, const int* offs, const uint32_t* aux, uint32_t* out)
+{
+  if (op < 0 || op > 6) return -1;
+  return math_cases::with_curve(curve, [&](auto tag) {
+    using C = typename decltype(tag)::type;
+    constexpr size_t N32 = EC<C>::N32;
+    for (int s = 0; s < nseq; s++)
+      if (int e = math_cases::ec_case<C>(op, pts + (size_t)offs[s] * 2 * N32, offs[s + 1] - offs[s], aux + offs[s], out + (size_t)s * 3 * N32)) return e;
+    return 0;
+  });
 }

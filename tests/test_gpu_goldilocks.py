@@ -140,6 +140,10 @@ def test_montgomery_conversion_and_vector_ops(hip):
     n = 5000
     x = rand_elems(rng, n)
     x.view("<u8")[:4] = [0, 1, F.p - 1, (1 << 32) - 1]
+    from tests import directed_operands as D
+
+    dv = D.gold_values()  # the directed list behind the four edge values: mul by 2^32 - 1 / its inverse through every branch of reduce128
+    x.view("<u8")[4:4 + len(dv)] = dv
     sym = "goldilocks_scalar_convert_montgomery"
     to_ref = ref.ref_convert_montgomery(FNAME, sym, x, n, True)
     assert to_ints(to_ref)[:3] == [0, (1 << 64) % F.p, (F.p - 1) * (1 << 64) % F.p]  # x * 2^64 (goldilocks.h:179)

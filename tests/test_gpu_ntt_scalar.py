@@ -105,6 +105,32 @@ def test_edge_values_and_montgomery_linearity(env, hip):
     assert gm == [(v * R) % F.p for v in to_ints(got)]
 
 
+@pytest.mark.parametrize("logn", [8, 17])
+def test_structured_inputs_vs_reference(env, hip, logn):
+    """all p-1, alternating p-1 / 0, a single p-1 at index 1: inputs that push every lazy butterfly toward its documented bound (random
+    inputs stay near the middle), at the largest single-pass size (2^8: split_logn(logn, 8), all eight stages in LDS) and at 2^17 (three passes), both directions and
+    a reordering, against the reference CPU backend"""
+    fname, F, rf, N = env
+    n = 1 << logn
+    top = np.array([((F.p - 1) >> (32 * j)) & 0xFFFFFFFF for j in range(8)], dtype=np.uint32)
+    full = np.tile(top, n)
+    alt = full.reshape(n, 8).copy()
+    alt[1::2] = 0
+    single = np.zeros((n, 8), dtype=np.uint32)
+    single[1] = top
+    for name, x in (("all p-1", full), ("alternating", alt.reshape(-1)), ("single", single.reshape(-1))):
+        x = np.ascontiguousarray(x)
+        for direction, ordering in ((0, 0), (1, 0), (0, 1)):
+            cfg = hip.NTTConfigU256.default()
+            cfg.ordering = ordering
+            got = N.ntt(fname, x, direction, cfg)
+            assert np.array_equal(got, rf.ntt(x, n, direction, ordering=ordering)), (fname, logn, name, direction, ordering)
+    if logn == 8:  # and the Python definition for the one with a closed form: NTT(single p-1 at 1)[k] = -w^k
+        w = pyref.omega(F, logn)
+        got = to_ints(N.ntt(fname, np.ascontiguousarray(single.reshape(-1)), N.FORWARD))
+        assert got == [(-pow(w, k, F.p)) % F.p for k in range(n)]
+
+
 def test_device_inplace_async(env, hip):
     fname, F, rf, N = env
     from icicle_amd.runtime import DeviceVec, Stream

@@ -12,6 +12,24 @@ pytestmark = pytest.mark.gpu
 BIG = ("bn254", "bls12_381", "bls12_377", "grumpkin", "stark252")  # 8-word scalars
 
 
+def directed_scalars(field):
+    """tests/directed_operands.py for a field of the vector ops: (values, pairs) -- the limb-boundary, tie and Montgomery-domain values of
+    the 256-bit fields (0, 1, p-1 among them), goldilocks' branch-by-branch pairs, the 31-bit fields' small list"""
+    from tests import directed_operands as D
+
+    p = scalar_modulus(field)
+    if field in BIG:
+        vals = D.directed_values(p, 9, 8)
+        rel = D.relation_pairs(vals, p)
+    elif field == "goldilocks":
+        vals = D.gold_values()
+        rel = [pr for pr in D.gold_pairs()[0]]
+    else:
+        vals = D.small_values(p)
+        rel = D.relation_pairs(vals, p)
+    return vals, rel
+
+
 def scalar_modulus(field):
     """a curve name stands for its scalar field"""
     return pyref.CURVES[field].r if field in pyref.CURVES else pyref.NTT_FIELDS[field].p
@@ -28,6 +46,8 @@ def test_scalar_convert_montgomery(hip, field):
         p = scalar_modulus(field)
         vals = rand_scalars(rng, n, p)
         vals[:4] = [0, 1, p - 1, p // 2]
+        dv = directed_scalars(field)[0]
+        vals[4:4 + len(dv)] = dv  # the directed list as the prefix
         x = to_words(vals, 8)
     else:
         p = pyref.NTT_FIELDS[field].p
@@ -97,7 +117,7 @@ def _ref_vec2(fname, op, a, b, size, batch=1, columns=False):
     return out
 
 
-@pytest.mark.parametrize("fname", ["babybear", "koalabear", "bn254", "bls12_381", "bls12_377", "grumpkin", "stark252"])
+@pytest.mark.parametrize("fname", ["babybear", "koalabear", "bn254", "bls12_381", "bls12_377", "grumpkin", "stark252", "goldilocks"])
 def test_vector_arithmetic_vs_reference(hip, fname):
     """vector_add / sub / mul, scalar_mul_vec, bit_reverse vs the reference CPU backend (memcmp), with batches in
     both layouts, edge values (0, 1, p-1) and device-resident operands"""
@@ -105,13 +125,27 @@ def test_vector_arithmetic_vs_reference(hip, fname):
     from icicle_amd.runtime import DeviceVec
 
     P = scalar_modulus(fname)
-    W = 8 if fname in BIG else 1
+    W = 8 if fname in BIG else (2 if fname == "goldilocks" else 1)
     rng = np.random.default_rng(71)
+    dvals, dpairs = directed_scalars(fname)  # (0, 1, P - 1 are the first values of every list)
+    assert all(v in dvals for v in (0, 1, P - 1))
+    flip = [False]
 
     def rand(count):
+        """random operands behind a directed prefix: the directed values, reversed on every other call so that the two operands of an op
+        do not always meet index against index"""
         vals = rand_scalars(rng, count, P)
-        vals[:3] = [0, 1, P - 1][: min(3, count)]
+        pre = dvals[::-1] if flip[0] else dvals
+        flip[0] = not flip[0]
+        vals[: min(len(pre), count)] = pre[: min(len(pre), count)]
         return np.ascontiguousarray(to_words(vals, W).reshape(-1))
+
+    # every directed pair by relation, element against element ((a,a), (a,p-a), (a,a+1), (a,a-1); goldilocks: a pair for every branch of
+    # goldfield.hpp's add / sub / reduce128)
+    pa = np.ascontiguousarray(to_words([x for x, _ in dpairs], W).reshape(-1))
+    pb = np.ascontiguousarray(to_words([y for _, y in dpairs], W).reshape(-1))
+    for op, fn in (("vector_add", V.vector_add), ("vector_sub", V.vector_sub), ("vector_mul", V.vector_mul)):
+        assert np.array_equal(fn(fname, pa, pb, hip.VecOpsConfig.default()), _ref_vec2(fname, op, pa, pb, len(dpairs))), (fname, op, "directed pairs")
 
     for size, batch, columns in ((1, 1, False), (1000, 1, False), (256, 3, False), (256, 3, True), (1 << 14, 2, True)):
         a, b = rand(size * batch), rand(size * batch)
@@ -132,6 +166,38 @@ def test_vector_arithmetic_vs_reference(hip, fname):
     assert np.array_equal(db.to_host(), _ref_vec2(fname, "vector_mul", a, b, size))
     V.bit_reverse(fname, da, hip.VecOpsConfig.default(), out=da, size=size)
     assert np.array_equal(da.to_host(), _ref_vec2(fname, "bit_reverse", None, a, size))
+
+
+@pytest.mark.parametrize("fname", ["babybear", "koalabear", "bn254", "bls12_381", "bls12_377", "grumpkin", "stark252", "goldilocks"])
+def test_scalar_add_sub_vec_vs_reference(hip, fname):
+    """scalar_add_vec / scalar_sub_vec (one scalar per batch entry) vs the reference CPU backend (memcmp) in both batch layouts, on the
+    directed values; and against the integers: scalar_sub_vec is scalar - vec[i], not the reverse"""
+    from icicle_amd import vecops as V
+    from tests.util import from_words
+
+    P = scalar_modulus(fname)
+    W = 8 if fname in BIG else (2 if fname == "goldilocks" else 1)
+    rng = np.random.default_rng(171)
+    dvals, _ = directed_scalars(fname)
+    for size, batch, columns in ((1, 1, False), (len(dvals), 1, False), (256, 3, False), (256, 3, True), (1000, 4, True)):
+        vals = rand_scalars(rng, size * batch, P)
+        vals[: min(len(dvals), len(vals))] = dvals[: min(len(dvals), len(vals))]
+        b = np.ascontiguousarray(to_words(vals, W).reshape(-1))
+        svals = [P - 1, 1, 0, dvals[7]][:batch]
+        s = np.ascontiguousarray(to_words(svals, W).reshape(-1))
+        cfg = hip.VecOpsConfig.default()
+        cfg.batch_size, cfg.columns_batch = batch, columns
+        got_add = V.scalar_add_vec(fname, s, b, cfg)
+        got_sub = V.scalar_sub_vec(fname, s, b, cfg)
+        assert np.array_equal(got_add, _ref_vec2(fname, "scalar_add_vec", s, b, size, batch, columns)), (fname, "scalar_add_vec", size, batch, columns)
+        assert np.array_equal(got_sub, _ref_vec2(fname, "scalar_sub_vec", s, b, size, batch, columns)), (fname, "scalar_sub_vec", size, batch, columns)
+        # the definition, on integers: element i of batch entry k lies at k*size + i (rows) or i*batch + k (columns)
+        ga, gs = from_words(got_add.reshape(-1, W)), from_words(got_sub.reshape(-1, W))
+        for k in range(batch):
+            for i in range(0, size, max(1, size // 97)):
+                at = i * batch + k if columns else k * size + i
+                assert ga[at] == (svals[k] + vals[at]) % P, (fname, "scalar_add_vec", size, batch, columns, k, i)
+                assert gs[at] == (svals[k] - vals[at]) % P, (fname, "scalar_sub_vec is scalar - vec", size, batch, columns, k, i)
 
 
 def test_polynomial_product_pipeline_on_device(hip):

@@ -22,7 +22,7 @@ NL = {0: 8, 1: 8, 2: 12, 3: 8, 4: 12, 5: 8, 6: 8, 7: 2}
 @pytest.fixture(scope="module")
 def lib():
     os.makedirs(os.path.dirname(SO), exist_ok=True)
-    deps = [SRC] + [os.path.join(HERE, "..", "icicle_amd", "csrc", f) for f in ("bigfield.hpp", "fq2.hpp", "ec.hpp", "smallfield.hpp", "goldfield.hpp", "field_consts.h", "glv.hpp", "ec_dbl_quad.hpp")]
+    deps = [SRC, os.path.join(HERE, "math_cases.hpp")] + [os.path.join(HERE, "..", "icicle_amd", "csrc", f) for f in ("bigfield.hpp", "fq2.hpp", "ec.hpp", "smallfield.hpp", "goldfield.hpp", "field_consts.h", "glv.hpp", "ec_dbl_quad.hpp")]
     if not os.path.exists(SO) or any(os.path.getmtime(d) > os.path.getmtime(SO) for d in deps):
         subprocess.check_call(["g++", "-std=c++17", "-O1", "-DBIGFIELD_BOUNDS", "-fPIC", "-shared", SRC, "-o", SO])
     return ctypes.CDLL(SO)
@@ -264,3 +264,82 @@ def test_small_field(lib, fi, f):
         if a:
             lib.host_small_op(fi, 4, a, 0, ctypes.byref(out))
             assert out.value == pow(a, -1, f.p)
+
+
+# ---- directed operands (tests/directed_operands.py) through the batched entry points: the CPU leg of tests/test_gpu_device_math.py.
+# Every tuple the GPU tests send passes here first with the bound tracker on, which aborts on a tuple outside a precondition.
+def _host_backend(lib):
+    from tests import math_expect
+
+    return math_expect.Backend(lib, device=False)
+
+
+def test_directed_operand_lists():
+    """the generator holds what it promises: the named values, both domains, the limb-boundary neighbours, and for goldilocks a pair for
+    every branch of add / sub / neg / reduce128 (which the seeded random pairs alone do not reach)"""
+    from tests import directed_operands as D
+
+    for p, nl, nl32 in ((pyref.BN254.q, 9, 8), (pyref.BLS12_381.q, 14, 12), (pyref.STARK252.p, 9, 8)):
+        vals = D.directed_values(p, nl, nl32)
+        assert len(vals) == len(set(vals)) and all(0 <= v < p for v in vals)
+        R = 1 << (29 * nl)
+        named = [0, 1, 2, 3, p - 1, p - 2, p - 3, (p - 1) // 2, (p + 1) // 2, R % p, R * R % p, -R % p, pow(R, -1, p)]
+        named += [(1 << (29 * k)) + d for k in range(1, nl - 1) for d in (-1, 0, 1)] + [p - (1 << (29 * k)) + d for k in range(1, nl - 1) for d in (-1, 0, 1)]
+        named += [(1 << (32 * k)) + d for k in range(1, nl32 - 1) for d in (-1, 0, 1)]
+        named += [(p >> (29 * k)) << (29 * k) for k in range(1, nl)] + [p % (1 << (29 * k)) for k in range(1, nl)]
+        for v in named:
+            assert v in vals, hex(v)
+            assert v * pow(R, -1, p) % p in vals, ("Montgomery domain", hex(v))
+        dp, rp = D.directed_pairs(p, nl, nl32)
+        assert len(dp) >= len(vals) ** 2 and len(rp) == D.RANDOM_PAIRS
+        assert D.directed_pairs(p, nl, nl32) == (dp, rp)  # deterministic
+        for a0 in (0, 1, p - 1):
+            for K in D.LAZY_K:
+                reps = D.lazy_values(a0, K, p, nl)
+                assert reps and all(v < K * p and v < (1 << (29 * nl)) and v % p == a0 for v in reps)
+                assert all(D.from_limbs(D.to_limbs(v, nl)) == v for v in reps)
+    dp, rp = D.gold_pairs()
+    taken = set()
+    for a, b in dp:
+        taken |= D.gold_branches(a, b)
+    assert taken == D.GOLD_ALL_BRANCHES, D.GOLD_ALL_BRANCHES - taken
+    for v in (0, 1, D.GOLD_P - 1, D.GOLD_P - 2, (1 << 32) - 1, 1 << 32, (1 << 32) + 1, 1 << 63, D.GOLD_P - (1 << 32), (D.GOLD_P - 1) // 2):
+        assert v in D.gold_values()
+
+
+@pytest.mark.parametrize("f", list(range(11)))
+def test_directed_canonical(lib, f):
+    """host loops == Python integers on all directed pairs and the random pairs, every op of the device tier (mul_add and the in-place
+    products included), fields 0..6, goldilocks (7), Fq2 over the three G2 base fields (8..10)"""
+    from tests import math_expect
+
+    n = math_expect.check_canon(_host_backend(lib), f)
+    if f == math_expect.GOLD:
+        n += math_expect.check_gold_noncanonical(_host_backend(lib))
+    print(f"{math_expect.FIELD_NAME[f]}: {n} (op, tuple) comparisons on the host")
+    assert n > 0
+
+
+@pytest.mark.parametrize("f", list(range(7)))
+def test_directed_raw(lib, f):
+    """raw lazy representatives through one op each: the header's written contract, with the tracker's bound set from the stated K"""
+    from tests import math_expect
+
+    n, _ = math_expect.check_raw(_host_backend(lib), f)
+    print(f"{math_expect.FIELD_NAME[f]}: {n} raw tuples on the host")
+    assert n > 0
+
+
+@pytest.mark.parametrize("fi", [0, 1])
+def test_directed_small_field(lib, fi):
+    from tests import math_expect
+
+    assert math_expect.check_small(_host_backend(lib), fi) > 0
+
+
+@pytest.mark.parametrize("ci", [0, 1, 2, 3, 4, 5, 6])
+def test_ec_sequences_batched(lib, ci):
+    """the EC sequences exactly as the device tier runs them (one per thread there, one after the other here)"""
+    from tests import math_expect
+
+    assert math_expect.check_ec(_host_backend(lib), ci) > 0
