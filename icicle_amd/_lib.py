@@ -155,7 +155,41 @@ class NTTInitDomainConfig(ctypes.Structure):
         return cls(None, False, None)
 
 
+class HashConfig(ctypes.Structure):
+    """icicle::HashConfig (include/icicle/hash/hash_config.h:15-24), 32 bytes."""
+    _fields_ = [
+        ("stream", ctypes.c_void_p),
+        ("batch", ctypes.c_uint64),
+        ("are_inputs_on_device", ctypes.c_bool),
+        ("are_outputs_on_device", ctypes.c_bool),
+        ("is_async", ctypes.c_bool),
+        ("ext", ctypes.c_void_p),
+    ]
+
+    @classmethod
+    def default(cls):
+        return cls(None, 1, False, False, False, None)
+
+
+class MerkleTreeConfig(ctypes.Structure):
+    """icicle::MerkleTreeConfig (include/icicle/merkle/merkle_tree_config.h:26-37), 24 bytes."""
+    _fields_ = [
+        ("stream", ctypes.c_void_p),
+        ("is_leaves_on_device", ctypes.c_bool),
+        ("is_tree_on_device", ctypes.c_bool),
+        ("is_async", ctypes.c_bool),
+        ("padding_policy", ctypes.c_int),
+        ("ext", ctypes.c_void_p),
+    ]
+
+    @classmethod
+    def default(cls):
+        return cls(None, False, False, False, 0, None)
+
+
 assert ctypes.sizeof(Device) == 68 and Device.id.offset == 64
+assert ctypes.sizeof(HashConfig) == 32 and HashConfig.are_inputs_on_device.offset == 16 and HashConfig.ext.offset == 24
+assert ctypes.sizeof(MerkleTreeConfig) == 24 and MerkleTreeConfig.padding_policy.offset == 12 and MerkleTreeConfig.ext.offset == 16
 assert ctypes.sizeof(MSMConfig) == 40 and MSMConfig.ext.offset == 32
 assert ctypes.sizeof(NTTConfigU32) == 40 and NTTConfigU32.ordering.offset == 20
 assert ctypes.sizeof(NTTInitDomainConfig) == 24
@@ -215,7 +249,21 @@ API_SYMBOLS = (
     + [f"{pre}{f}_extension_scalar_convert_montgomery" for pre in ("", "icicle_hip_") for f in NTT_FIELDS + [GOLD]]
     + [f"{pre}{c}_{k}_convert_montgomery" for pre in ("", "icicle_hip_") for c in CURVES for k in ("affine", "projective")]
     + [f"{pre}{c}_g2_{k}_convert_montgomery" for pre in ("", "icicle_hip_") for c in G2_CURVES for k in ("affine", "projective")]
+    + ["icicle_hasher_hash", "icicle_hasher_delete", "icicle_merkle_tree_delete", "icicle_merkle_tree_build", "icicle_merkle_tree_get_proof",
+       "icicle_merkle_tree_verify", "icicle_merkle_proof_delete", "icicle_merkle_proof_is_pruned"]
 )
+# hash / Merkle functions that return a handle, a size or a byte pointer (tests/test_abi.py's header scan sees only the return types
+# of the lists above; tests/test_hash_cpu.py checks these against the header with a scan of its own): name -> restype
+_HASH_RESTYPES = {
+    "icicle_create_keccak_256": ctypes.c_void_p, "icicle_create_keccak_512": ctypes.c_void_p,
+    "icicle_create_sha3_256": ctypes.c_void_p, "icicle_create_sha3_512": ctypes.c_void_p,
+    "icicle_hasher_output_size": ctypes.c_uint64,
+    "icicle_merkle_tree_create": ctypes.c_void_p, "icicle_merkle_tree_get_root": ctypes.c_void_p,
+    "icicle_merkle_proof_create": ctypes.c_void_p, "icicle_merkle_proof_create_with_data": ctypes.c_void_p,
+    "icicle_merkle_proof_get_path": ctypes.c_void_p, "icicle_merkle_proof_get_leaf": ctypes.c_void_p,
+    "icicle_merkle_proof_get_root": ctypes.c_void_p,
+}
+HASH_HANDLE_SYMBOLS = list(_HASH_RESTYPES)
 
 if not os.path.exists(LIB_PATH):
     raise ImportError(
@@ -225,6 +273,8 @@ if not os.path.exists(LIB_PATH):
 lib = ctypes.CDLL(LIB_PATH)
 for _s in RUNTIME_SYMBOLS + API_SYMBOLS:
     getattr(lib, _s)  # AttributeError if the library does not export a declared symbol
+for _s in HASH_HANDLE_SYMBOLS:
+    getattr(lib, _s).restype = _HASH_RESTYPES[_s]  # AttributeError if the symbol is missing, as above
 lib.icicle_hip_version.restype = ctypes.c_char_p
 lib.create_config_extension.restype = ctypes.c_void_p
 lib.clone_config_extension.restype = ctypes.c_void_p
@@ -307,6 +357,28 @@ lib.icicle_hip_multi_stats2.argtypes = [ctypes.POINTER(ctypes.c_uint64), ctypes.
 lib.icicle_hip_test_set_virtual_devices.argtypes = [ctypes.c_int]
 lib.icicle_hip_set_collectives_library.argtypes = [ctypes.c_char_p]
 lib.icicle_hip_test_inject_failure.argtypes = [ctypes.c_int, ctypes.c_int]
+_size_p = ctypes.POINTER(ctypes.c_size_t)
+for _n in ("icicle_create_keccak_256", "icicle_create_keccak_512", "icicle_create_sha3_256", "icicle_create_sha3_512"):
+    getattr(lib, _n).argtypes = [ctypes.c_uint64]
+lib.icicle_hasher_hash.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64, ctypes.POINTER(HashConfig), ctypes.c_void_p]
+lib.icicle_hasher_output_size.argtypes = [ctypes.c_void_p]
+lib.icicle_hasher_delete.argtypes = [ctypes.c_void_p]
+lib.icicle_merkle_tree_create.argtypes = [ctypes.POINTER(ctypes.c_void_p), ctypes.c_size_t, ctypes.c_uint64, ctypes.c_uint64]
+lib.icicle_merkle_tree_delete.argtypes = [ctypes.c_void_p]
+lib.icicle_merkle_tree_build.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64, ctypes.POINTER(MerkleTreeConfig)]
+lib.icicle_merkle_tree_get_root.argtypes = [ctypes.c_void_p, _size_p]
+lib.icicle_merkle_tree_get_proof.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_uint64, ctypes.c_bool,
+                                             ctypes.POINTER(MerkleTreeConfig), ctypes.c_void_p]
+lib.icicle_merkle_tree_verify.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.POINTER(ctypes.c_bool)]
+lib.icicle_merkle_proof_create.argtypes = []
+lib.icicle_merkle_proof_create_with_data.argtypes = [ctypes.c_bool, ctypes.c_int64, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p, ctypes.c_size_t,
+                                                     ctypes.c_void_p, ctypes.c_size_t]
+lib.icicle_merkle_proof_delete.argtypes = [ctypes.c_void_p]
+lib.icicle_merkle_proof_is_pruned.argtypes = [ctypes.c_void_p]
+lib.icicle_merkle_proof_is_pruned.restype = ctypes.c_bool
+lib.icicle_merkle_proof_get_path.argtypes = [ctypes.c_void_p, _size_p]
+lib.icicle_merkle_proof_get_leaf.argtypes = [ctypes.c_void_p, _size_p, ctypes.POINTER(ctypes.c_uint64)]
+lib.icicle_merkle_proof_get_root.argtypes = [ctypes.c_void_p, _size_p]
 
 
 def multi_stats(reset=False):

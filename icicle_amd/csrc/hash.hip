@@ -1,0 +1,802 @@
+// Keccak / SHA3 batch hashing and Merkle trees on the device.
+//
+// C ABI of the reference: icicle/src/hash/hash_c_api.cpp (icicle_create_keccak_256 .., icicle_hasher_hash), src/hash/merkle_c_api.cpp
+// (icicle_merkle_tree_*, icicle_merkle_proof_*); configs include/icicle/hash/hash_config.h, include/icicle/merkle/merkle_tree_config.h;
+// tree / proof semantics backend/cpu/src/hash/cpu_merkle_tree.cpp:143-211,546-573 and include/icicle/merkle/merkle_tree.h:148-203.
+//
+// The permutation is written from FIPS 202:
+//   * rotation offsets: (t + 1)(t + 2) / 2 mod 64 for t = 0 .. 23 along the walk (x, y) -> (y, 2x + 3y) from (1, 0); lane (0, 0) stays.
+//       rot, (x, y) = [0] * 25, (1, 0)
+//       for t in range(24): rot[x + 5 * y] = (t + 1) * (t + 2) // 2 % 64; x, y = y, (2 * x + 3 * y) % 5
+//   * rho + pi: B[y][2x + 3y] = rotl(A[x][y], rot[x][y]), lane index x + 5 y (the 25 lines of KECCAK_RHO_PI are this, printed by
+//       for x in range(5): for y in range(5): print(f"b[{y + 5 * ((2 * x + 3 * y) % 5)}] = rotl64<{rot[x + 5 * y]}>(a[{x + 5 * y}]);"))
+//   * round constants: bit 2^j - 1 of RC[i] is rc(j + 7 i), rc(t) = bit 0 of x^t mod x^8 + x^6 + x^5 + x^4 + 1 over GF(2):
+//       r = 1
+//       for i in range(24):
+//           c = 0
+//           for j in range(7):
+//               if r & 1: c |= 1 << ((1 << j) - 1)
+//               r = ((r << 1) ^ (0x71 if r & 0x80 else 0)) & 0xFF
+//           RC.append(c)
+// (tests/merkle_model.py holds the same three derivations and is checked against hashlib's SHA3.)
+//
+// One lane hashes one message: the 25-lane state is 50 VGPRs, every index a compile-time constant, the 24 rounds a rolled loop.
+// Keccak is 64-bit integer ALU work, far from the memory roof, so the lanes' strided loads do not matter.
+#include "common.h"
+#include "merkle_plan.h"
+#include <algorithm>
+#include <cstring>
+#include <new>
+
+namespace icicle_hip {
+
+  __constant__ uint64_t KECCAK_RC[24] = {
+    0x0000000000000001ull, 0x0000000000008082ull, 0x800000000000808aull, 0x8000000080008000ull, 0x000000000000808bull, 0x0000000080000001ull,
+    0x8000000080008081ull, 0x8000000000008009ull, 0x000000000000008aull, 0x0000000000000088ull, 0x0000000080008009ull, 0x000000008000000aull,
+    0x000000008000808bull, 0x800000000000008bull, 0x8000000000008089ull, 0x8000000000008003ull, 0x8000000000008002ull, 0x8000000000000080ull,
+    0x000000000000800aull, 0x800000008000000aull, 0x8000000080008081ull, 0x8000000000008080ull, 0x0000000080000001ull, 0x8000000080008008ull};
+
+  // rotate left by a constant. Default: the compiler's 64-bit shift pair; -DICICLE_HIP_KECCAK_ALIGNBIT: two v_alignbit_b32 on the halves
+  // (profiles/hash_merkle_notes.md has the instruction counts of both).
+  template <int N>
+  __device__ __forceinline__ uint64_t rotl64(uint64_t v)
+  {
+    if constexpr (N == 0) {
+      return v;
+    } else {
+#ifdef ICICLE_HIP_KECCAK_ALIGNBIT
+      const uint32_t lo = (uint32_t)v, hi = (uint32_t)(v >> 32);
+      if constexpr (N == 32) {
+        return ((uint64_t)lo << 32) | hi;
+      } else if constexpr (N < 32) {
+        const uint32_t nh = __builtin_amdgcn_alignbit(hi, lo, 32 - N), nl = __builtin_amdgcn_alignbit(lo, hi, 32 - N);
+        return ((uint64_t)nh << 32) | nl;
+      } else {
+        const uint32_t nh = __builtin_amdgcn_alignbit(lo, hi, 64 - N), nl = __builtin_amdgcn_alignbit(hi, lo, 64 - N);
+        return ((uint64_t)nh << 32) | nl;
+      }
+#else
+      return (v << N) | (v >> (64 - N));
+#endif
+    }
+  }
+
+#define KECCAK_RHO_PI                                                                                                  \
+  b[0] = rotl64<0>(a[0]), b[16] = rotl64<36>(a[5]), b[7] = rotl64<3>(a[10]), b[23] = rotl64<41>(a[15]), b[14] = rotl64<18>(a[20]);    \
+  b[10] = rotl64<1>(a[1]), b[1] = rotl64<44>(a[6]), b[17] = rotl64<10>(a[11]), b[8] = rotl64<45>(a[16]), b[24] = rotl64<2>(a[21]);    \
+  b[20] = rotl64<62>(a[2]), b[11] = rotl64<6>(a[7]), b[2] = rotl64<43>(a[12]), b[18] = rotl64<15>(a[17]), b[9] = rotl64<61>(a[22]);   \
+  b[5] = rotl64<28>(a[3]), b[21] = rotl64<55>(a[8]), b[12] = rotl64<25>(a[13]), b[3] = rotl64<21>(a[18]), b[19] = rotl64<56>(a[23]);  \
+  b[15] = rotl64<27>(a[4]), b[6] = rotl64<20>(a[9]), b[22] = rotl64<39>(a[14]), b[13] = rotl64<8>(a[19]), b[4] = rotl64<14>(a[24]);
+#define KECCAK_CHI_ROW(r)                                                                                              \
+  a[r + 0] = b[r + 0] ^ (~b[r + 1] & b[r + 2]), a[r + 1] = b[r + 1] ^ (~b[r + 2] & b[r + 3]), a[r + 2] = b[r + 2] ^ (~b[r + 3] & b[r + 4]), \
+        a[r + 3] = b[r + 3] ^ (~b[r + 4] & b[r + 0]), a[r + 4] = b[r + 4] ^ (~b[r + 0] & b[r + 1]);
+
+  __device__ __forceinline__ void keccak_f1600(uint64_t (&a)[25])
+  {
+#pragma unroll 1
+    for (int rnd = 0; rnd < 24; rnd++) {
+      const uint64_t c0 = a[0] ^ a[5] ^ a[10] ^ a[15] ^ a[20], c1 = a[1] ^ a[6] ^ a[11] ^ a[16] ^ a[21], c2 = a[2] ^ a[7] ^ a[12] ^ a[17] ^ a[22],
+                     c3 = a[3] ^ a[8] ^ a[13] ^ a[18] ^ a[23], c4 = a[4] ^ a[9] ^ a[14] ^ a[19] ^ a[24];
+      const uint64_t d0 = c4 ^ rotl64<1>(c1), d1 = c0 ^ rotl64<1>(c2), d2 = c1 ^ rotl64<1>(c3), d3 = c2 ^ rotl64<1>(c4), d4 = c3 ^ rotl64<1>(c0);
+#pragma unroll
+      for (int y = 0; y < 25; y += 5)
+        a[y] ^= d0, a[y + 1] ^= d1, a[y + 2] ^= d2, a[y + 3] ^= d3, a[y + 4] ^= d4;
+      uint64_t b[25];
+      KECCAK_RHO_PI
+      KECCAK_CHI_ROW(0) KECCAK_CHI_ROW(5) KECCAK_CHI_ROW(10) KECCAK_CHI_ROW(15) KECCAK_CHI_ROW(20)
+      a[0] ^= KECCAK_RC[rnd];
+    }
+  }
+
+  // ---- where a lane's message bytes come from ----------------------------------------------------------------------------------
+  // 8-aligned message: 64-bit loads, 128-bit ones where message and offset are 16-aligned
+  struct ReadAligned {
+    const uint8_t* p;
+    bool a16;
+    __device__ __forceinline__ uint64_t word(uint64_t off) const { return *reinterpret_cast<const uint64_t*>(p + off); }
+    __device__ __forceinline__ uint32_t byte(uint64_t off) const { return p[off]; }
+    __device__ __forceinline__ void pair(uint64_t off, uint64_t& lo, uint64_t& hi) const
+    {
+      if (a16 && (off & 15) == 0) {
+        const ulonglong2 v = *reinterpret_cast<const ulonglong2*>(p + off);
+        lo = v.x, hi = v.y;
+      } else {
+        lo = word(off), hi = word(off + 8);
+      }
+    }
+  };
+  // any alignment
+  struct ReadBytes {
+    const uint8_t* p;
+    __device__ __forceinline__ uint32_t byte(uint64_t off) const { return p[off]; }
+    __device__ __forceinline__ uint64_t word(uint64_t off) const
+    {
+      uint64_t w = 0;
+#pragma unroll
+      for (int k = 0; k < 8; k++)
+        w |= (uint64_t)p[off + k] << (8 * k);
+      return w;
+    }
+    __device__ __forceinline__ void pair(uint64_t off, uint64_t& lo, uint64_t& hi) const { lo = word(off), hi = word(off + 8); }
+  };
+  // a layer-0 chunk of a tree that reaches into the padding: byte q of the padded leaves is leaves[q] below `valid`, beyond it
+  // 0 (ZeroPadding: last == nullptr) or byte q % es of the last element (LastValue; valid and the chunk size are multiples of es)
+  struct ReadPadded {
+    const uint8_t* base; // leaves, addressed by the byte offset in the whole tree's leaves
+    uint64_t pos;        // offset of this chunk
+    uint64_t valid;
+    const uint8_t* last;
+    uint64_t es;
+    __device__ __forceinline__ uint32_t byte(uint64_t off) const
+    {
+      const uint64_t q = pos + off;
+      if (q < valid) return base[q];
+      return last ? last[q % es] : 0;
+    }
+    __device__ __forceinline__ uint64_t word(uint64_t off) const
+    {
+      uint64_t w = 0;
+      for (int k = 0; k < 8; k++)
+        w |= (uint64_t)byte(off + k) << (8 * k);
+      return w;
+    }
+    __device__ __forceinline__ void pair(uint64_t off, uint64_t& lo, uint64_t& hi) const { lo = word(off), hi = word(off + 8); }
+  };
+
+  // sponge over one message of `len` bytes: absorb whole blocks, then the last block with the domain suffix at byte len % rate and
+  // 0x80 at the block's last byte (pad10*1). The digest is a[0 .. OUT_WORDS).
+  template <int RATE_WORDS, class RD>
+  __device__ __forceinline__ void keccak_msg(const RD& rd, uint64_t len, uint32_t suffix, uint64_t (&a)[25])
+  {
+    constexpr uint64_t RATE = 8ull * RATE_WORDS;
+#pragma unroll
+    for (int i = 0; i < 25; i++)
+      a[i] = 0;
+    uint64_t off = 0;
+    for (;;) { // one call site of the permutation: whole blocks, then the padded last one
+      const bool last_block = len - off < RATE;
+      if (!last_block) {
+#pragma unroll
+        for (int i = 0; i + 1 < RATE_WORDS; i += 2) {
+          uint64_t lo, hi;
+          rd.pair(off + 8 * i, lo, hi);
+          a[i] ^= lo, a[i + 1] ^= hi;
+        }
+        if constexpr (RATE_WORDS & 1) a[RATE_WORDS - 1] ^= rd.word(off + 8 * (RATE_WORDS - 1));
+      } else {
+        // words [0, wi) are whole, word wi holds the last rem % 8 message bytes and the suffix, the block's last byte takes 0x80
+        const uint32_t rem = (uint32_t)(len - off), wi = rem >> 3, nb = rem & 7;
+        uint64_t part = (uint64_t)suffix << (8 * nb);
+        for (uint32_t k = 0; k < nb; k++)
+          part |= (uint64_t)rd.byte(off + 8 * wi + k) << (8 * k);
+#pragma unroll
+        for (int i = 0; i < RATE_WORDS; i++) {
+          uint64_t w = 0;
+          if ((uint32_t)i < wi) w = rd.word(off + 8 * i);
+          if ((uint32_t)i == wi) w = part;
+          if (i == RATE_WORDS - 1) w ^= 0x80ull << 56;
+          a[i] ^= w;
+        }
+      }
+      keccak_f1600(a);
+      if (last_block) break;
+      off += RATE;
+    }
+  }
+
+  template <int OUT_WORDS>
+  __device__ __forceinline__ void store_digest(uint8_t* out, bool aligned, const uint64_t (&a)[25])
+  {
+    if (aligned) {
+#pragma unroll
+      for (int i = 0; i < OUT_WORDS; i++)
+        reinterpret_cast<uint64_t*>(out)[i] = a[i];
+    } else {
+#pragma unroll
+      for (int i = 0; i < OUT_WORDS; i++)
+#pragma unroll
+        for (int k = 0; k < 8; k++)
+          out[8 * i + k] = (uint8_t)(a[i] >> (8 * k));
+    }
+  }
+
+  enum : uint32_t { HASH_IN_ALIGNED16 = 2, HASH_OUT_ALIGNED8 = 4 };
+
+  // n messages of `len` bytes at in + t * stride -> digests of 8 * OUT_WORDS bytes at out + t * 8 * OUT_WORDS. One lane per message.
+  // ALIGNED: `in` and `stride` are multiples of 8 (64-bit loads, 128-bit ones with HASH_IN_ALIGNED16); otherwise byte loads. Two
+  // kernels rather than a branch, so that the byte path's loads in flight do not set the aligned path's register count.
+  template <int RATE_WORDS, int OUT_WORDS, bool ALIGNED>
+  __global__ __launch_bounds__(256) void k_keccak_batch(const uint8_t* __restrict__ in, uint64_t len, uint64_t stride, uint64_t n, uint32_t suffix, uint32_t flags,
+                                                         uint8_t* __restrict__ out)
+  {
+    static_assert(2 * OUT_WORDS + RATE_WORDS == 25, "capacity = twice the digest");
+    const uint64_t step = (uint64_t)gridDim.x * blockDim.x;
+    for (uint64_t t = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; t < n; t += step) {
+      uint64_t a[25];
+      const uint8_t* p = in + t * stride;
+      if constexpr (ALIGNED)
+        keccak_msg<RATE_WORDS>(ReadAligned{p, (flags & HASH_IN_ALIGNED16) != 0}, len, suffix, a);
+      else
+        keccak_msg<RATE_WORDS>(ReadBytes{p}, len, suffix, a);
+      store_digest<OUT_WORDS>(out + t * (8 * OUT_WORDS), (flags & HASH_OUT_ALIGNED8) != 0, a);
+    }
+  }
+
+  // layer-0 chunks [first, first + n) of a tree whose leaves end inside or in front of them (ReadPadded); digest t goes to
+  // out + t * 8 * OUT_WORDS, 8-aligned
+  template <int RATE_WORDS, int OUT_WORDS>
+  __global__ __launch_bounds__(256) void k_keccak_leaves(const uint8_t* __restrict__ leaves, uint64_t chunk, uint64_t first, uint64_t n, uint64_t valid,
+                                                          const uint8_t* __restrict__ last, uint64_t es, uint32_t suffix, uint8_t* __restrict__ out)
+  {
+    const uint64_t step = (uint64_t)gridDim.x * blockDim.x;
+    for (uint64_t t = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; t < n; t += step) {
+      uint64_t a[25];
+      keccak_msg<RATE_WORDS>(ReadPadded{leaves, (first + t) * chunk, valid, last, es}, chunk, suffix, a);
+      store_digest<OUT_WORDS>(out + t * (8 * OUT_WORDS), true, a);
+    }
+  }
+
+  // ---- the top of a tree in one launch ------------------------------------------------------------------------------------------
+  // Once a layer has at most MERKLE_TOP_MAX_HASHES hashes every further layer is smaller still: one launch per layer would be a
+  // chain of launches that cannot fill one CU. One block walks them all, a barrier between layers; each layer reads the digests
+  // the layer below wrote to global memory (the stored layer buffers, all 8-aligned). The layers may use different hashers.
+  struct MerkleTopLayer {
+    const uint8_t* in; // count chunks of `chunk` bytes
+    uint8_t* out;
+    uint32_t chunk, count, rate_words, suffix;
+  };
+  struct MerkleTopArgs {
+    MerkleTopLayer l[MERKLE_MAX_LAYERS];
+    int n;
+  };
+  constexpr int MERKLE_TOP_THREADS = 1024;
+  // default switch point (MerkleTreeConfig.ext "hip_merkle_top_max_hashes" overrides it, 0 = never fuse): the largest layer the one
+  // block hashes in a single pass, one message per thread (profiles/hash_merkle_notes.md)
+  constexpr int MERKLE_TOP_MAX_HASHES = 1024;
+
+  __global__ __launch_bounds__(MERKLE_TOP_THREADS) void k_merkle_top(const MerkleTopArgs args)
+  {
+    for (int d = 0; d < args.n; d++) {
+      const MerkleTopLayer& l = args.l[d];
+      for (uint32_t j = threadIdx.x; j < l.count; j += MERKLE_TOP_THREADS) {
+        uint64_t a[25];
+        const ReadAligned rd{l.in + (uint64_t)j * l.chunk, false};
+        if (l.rate_words == 17) {
+          keccak_msg<17>(rd, l.chunk, l.suffix, a);
+          store_digest<4>(l.out + (uint64_t)j * 32, true, a);
+        } else {
+          keccak_msg<9>(rd, l.chunk, l.suffix, a);
+          store_digest<8>(l.out + (uint64_t)j * 64, true, a);
+        }
+      }
+      __syncthreads(); // the next layer reads what other waves of this block just wrote
+    }
+  }
+
+  // ---- host side ----------------------------------------------------------------------------------------------------------------
+  struct Hasher {
+    int rate_words; // 17: 256-bit digest, 9: 512-bit digest
+    int out_words;
+    uint32_t suffix; // 0x01 Keccak, 0x06 SHA3
+    uint64_t chunk;  // default input size, 0 = none
+  };
+
+  static unsigned grid_for(uint64_t n) { return (unsigned)std::min<uint64_t>((n + 255) / 256, 1u << 22); }
+
+  static icicle_error_t launch_batch(const Hasher& h, const uint8_t* in, uint64_t len, uint64_t stride, uint64_t n, uint8_t* out, hipStream_t st)
+  {
+    if (n == 0) return ICICLE_SUCCESS;
+    uint32_t flags = 0;
+    const bool a8 = ((uintptr_t)in & 7) == 0 && (stride & 7) == 0;
+    if (((uintptr_t)in & 15) == 0 && (stride & 15) == 0) flags |= HASH_IN_ALIGNED16;
+    if (((uintptr_t)out & 7) == 0) flags |= HASH_OUT_ALIGNED8;
+    if (h.rate_words == 17 && a8)
+      k_keccak_batch<17, 4, true><<<grid_for(n), 256, 0, st>>>(in, len, stride, n, h.suffix, flags, out);
+    else if (h.rate_words == 17)
+      k_keccak_batch<17, 4, false><<<grid_for(n), 256, 0, st>>>(in, len, stride, n, h.suffix, flags, out);
+    else if (a8)
+      k_keccak_batch<9, 8, true><<<grid_for(n), 256, 0, st>>>(in, len, stride, n, h.suffix, flags, out);
+    else
+      k_keccak_batch<9, 8, false><<<grid_for(n), 256, 0, st>>>(in, len, stride, n, h.suffix, flags, out);
+    LAUNCH_CHECK("k_keccak_batch", st);
+    return ICICLE_SUCCESS;
+  }
+
+  static icicle_error_t launch_leaves(const Hasher& h, const uint8_t* leaves, uint64_t chunk, uint64_t first, uint64_t n, uint64_t valid, const uint8_t* last,
+                                      uint64_t es, uint8_t* out, hipStream_t st)
+  {
+    if (n == 0) return ICICLE_SUCCESS;
+    if (h.rate_words == 17)
+      k_keccak_leaves<17, 4><<<grid_for(n), 256, 0, st>>>(leaves, chunk, first, n, valid, last, es, h.suffix, out);
+    else
+      k_keccak_leaves<9, 8><<<grid_for(n), 256, 0, st>>>(leaves, chunk, first, n, valid, last, es, h.suffix, out);
+    LAUNCH_CHECK("k_keccak_leaves", st);
+    return ICICLE_SUCCESS;
+  }
+
+  static Hasher* make_hasher(int rate_words, uint32_t suffix, uint64_t chunk)
+  {
+    return new (std::nothrow) Hasher{rate_words, (25 - rate_words) / 2, suffix, chunk};
+  }
+
+  static icicle_error_t hasher_hash(const Hasher* h, const uint8_t* input, uint64_t input_len, const icicle_hash_config_t* cfg, uint8_t* output)
+  {
+    if (!h || !cfg) return ICICLE_INVALID_POINTER;
+    const uint64_t len = input_len ? input_len : h->chunk;
+    if (len == 0) return ICICLE_INVALID_ARGUMENT;
+    const uint64_t batch = cfg->batch;
+    if (batch == 0) return ICICLE_SUCCESS;
+    if (!input || !output) return ICICLE_INVALID_POINTER;
+    if (len >= (1ull << 56) / batch) return ICICLE_INVALID_ARGUMENT;
+    ICICLE_TRY(bind_current_device());
+    hipStream_t st = (hipStream_t)cfg->stream;
+    const size_t in_bytes = (size_t)(len * batch), out_bytes = (size_t)(8ull * h->out_words * batch);
+    TempBuf d_in_tmp, d_out_tmp;
+    const uint8_t* d_in = input;
+    uint8_t* d_out = output;
+    if (!cfg->are_inputs_on_device) {
+      HIP_TRY(d_in_tmp.alloc(in_bytes, st), ICICLE_ALLOCATION_FAILED);
+      HIP_TRY(hipMemcpyAsync(d_in_tmp.ptr(), input, in_bytes, hipMemcpyHostToDevice, st), ICICLE_COPY_FAILED);
+      d_in = d_in_tmp.as<uint8_t>();
+    }
+    if (!cfg->are_outputs_on_device) {
+      HIP_TRY(d_out_tmp.alloc(out_bytes, st), ICICLE_ALLOCATION_FAILED);
+      d_out = d_out_tmp.as<uint8_t>();
+    }
+    ICICLE_TRY(launch_batch(*h, d_in, len, len, batch, d_out, st));
+    if (!cfg->are_outputs_on_device) {
+      HIP_TRY(hipMemcpyAsync(output, d_out, out_bytes, hipMemcpyDeviceToHost, st), ICICLE_COPY_FAILED);
+      HIP_TRY(hipStreamSynchronize(st), ICICLE_SYNCHRONIZATION_FAILED);
+    } else if (!cfg->is_async) {
+      HIP_TRY(hipStreamSynchronize(st), ICICLE_SYNCHRONIZATION_FAILED);
+    }
+    return ICICLE_SUCCESS;
+  }
+
+  // ---- Merkle tree --------------------------------------------------------------------------------------------------------------
+  struct Proof {
+    bool pruned = false;
+    uint64_t leaf_idx = 0;
+    std::vector<uint8_t> leaf, root, path;
+  };
+
+  struct Tree {
+    MerklePlan plan;
+    std::vector<Hasher> hashers;
+    int store_min = 0;
+    bool built = false;
+    bool on_device = false;
+    uint8_t* d_store = nullptr; // layers store_min .. L-1 (hipMalloc), when the tree stays on the device
+    uint8_t* h_store = nullptr; // the same layers in pinned host memory otherwise
+    uint8_t* h_root = nullptr;  // pinned, so that an asynchronous build can fill it in stream order
+    uint64_t store_off(int i) const { return plan.layers[i].offset - plan.layers[store_min].offset; }
+    uint64_t store_bytes() const { return plan.total_bytes - plan.layers[store_min].offset; }
+    void release()
+    {
+      if (d_store) (void)hipFree(d_store);
+      if (h_store) (void)hipHostFree(h_store);
+      if (h_root) (void)hipHostFree(h_root);
+      d_store = h_store = h_root = nullptr;
+      built = false;
+    }
+  };
+
+  static int top_max_of(const icicle_merkle_tree_config_t* cfg)
+  {
+    int v = MERKLE_TOP_MAX_HASHES;
+    if (cfg->ext) v = reinterpret_cast<const ConfigExt*>(cfg->ext)->get_int("hip_merkle_top_max_hashes", v);
+    return std::max(0, v);
+  }
+
+  // What layer 0 reads: `base` is addressed by byte offsets of the whole tree's leaves (only [.., valid) is ever read), `last`
+  // the LastValue element or nullptr.
+  struct LeafSource {
+    const uint8_t* base;
+    uint64_t valid;
+    const uint8_t* last;
+  };
+
+  // Hashes layers [0, upto) of the (sub-)tree over layer-0 chunks [first, first + count): out[i] takes the digests of layer i in
+  // order. Layer 0 goes through the batch kernel where the chunks lie inside the leaves and through k_keccak_leaves where they
+  // reach into the padding; from the first layer above it with at most top_max hashes one k_merkle_top launch does the rest.
+  static icicle_error_t hash_layers(const Tree& t, const LeafSource& src, uint64_t first, uint64_t count, int upto, uint8_t* const* out, int top_max,
+                                    hipStream_t st)
+  {
+    const MerklePlan& p = t.plan;
+    const uint64_t c0 = p.layers[0].chunk, full_chunks = src.valid / c0;
+    const uint64_t n_full = first >= full_chunks ? 0 : std::min(count, full_chunks - first);
+    ICICLE_TRY(launch_batch(t.hashers[0], src.base + first * c0, c0, c0, n_full, out[0], st));
+    ICICLE_TRY(launch_leaves(t.hashers[0], src.base, c0, first + n_full, count - n_full, src.valid, src.last, p.leaf_element_size,
+                             out[0] + n_full * p.layers[0].out, st));
+    uint64_t n = count;
+    for (int i = 1; i < upto; i++) {
+      n /= p.arity(i);
+      if (top_max > 0 && n <= (uint64_t)top_max) {
+        MerkleTopArgs args;
+        args.n = 0;
+        uint64_t m = n;
+        for (int j = i; j < upto; j++) {
+          if (j > i) m /= p.arity(j);
+          args.l[args.n++] = MerkleTopLayer{out[j - 1], out[j], (uint32_t)p.layers[j].chunk, (uint32_t)m, (uint32_t)t.hashers[j].rate_words, t.hashers[j].suffix};
+        }
+        k_merkle_top<<<1, MERKLE_TOP_THREADS, 0, st>>>(args);
+        LAUNCH_CHECK("k_merkle_top", st);
+        return ICICLE_SUCCESS;
+      }
+      ICICLE_TRY(launch_batch(t.hashers[i], out[i - 1], p.layers[i].chunk, p.layers[i].chunk, n, out[i], st));
+    }
+    return ICICLE_SUCCESS;
+  }
+
+  static icicle_error_t tree_build(Tree* t, const uint8_t* leaves, uint64_t leaves_size, const icicle_merkle_tree_config_t* cfg)
+  {
+    if (t->built) return ICICLE_INVALID_ARGUMENT;
+    MerklePadding pad;
+    if (merkle_padding(t->plan, leaves_size, cfg->padding_policy, &pad)) return ICICLE_INVALID_ARGUMENT;
+    ICICLE_TRY(bind_current_device());
+    t->release();
+    hipStream_t st = (hipStream_t)cfg->stream;
+    const MerklePlan& p = t->plan;
+    const int L = p.L(), m = t->store_min;
+    TempBuf d_leaves_tmp, d_low, d_top;
+    const uint8_t* d_leaves = leaves;
+    if (!cfg->is_leaves_on_device) {
+      HIP_TRY(d_leaves_tmp.alloc(leaves_size, st), ICICLE_ALLOCATION_FAILED);
+      HIP_TRY(hipMemcpyAsync(d_leaves_tmp.ptr(), leaves, leaves_size, hipMemcpyHostToDevice, st), ICICLE_COPY_FAILED);
+      d_leaves = d_leaves_tmp.as<uint8_t>();
+    }
+    t->on_device = cfg->is_tree_on_device;
+    HIP_TRY(hipHostMalloc((void**)&t->h_root, 64, hipHostMallocDefault), ICICLE_ALLOCATION_FAILED);
+    uint8_t* store = nullptr; // device memory the stored layers are computed in
+    if (t->on_device) {
+      HIP_TRY(hipMalloc((void**)&t->d_store, t->store_bytes()), ICICLE_ALLOCATION_FAILED);
+      store = t->d_store;
+    } else {
+      HIP_TRY(hipHostMalloc((void**)&t->h_store, t->store_bytes(), hipHostMallocDefault), ICICLE_ALLOCATION_FAILED);
+      HIP_TRY(d_top.alloc(t->store_bytes(), st), ICICLE_ALLOCATION_FAILED);
+      store = d_top.as<uint8_t>();
+    }
+    if (m > 0) HIP_TRY(d_low.alloc(p.layers[m].offset, st), ICICLE_ALLOCATION_FAILED);
+    uint8_t* out[MERKLE_MAX_LAYERS];
+    for (int i = 0; i < L; i++)
+      out[i] = i < m ? d_low.as<uint8_t>() + p.layers[i].offset : store + t->store_off(i);
+    const LeafSource src{d_leaves, leaves_size, cfg->padding_policy == MERKLE_PAD_LAST && pad.pad_bytes ? d_leaves + pad.last_off : nullptr};
+    ICICLE_TRY(hash_layers(*t, src, 0, p.layers[0].count, L, out, top_max_of(cfg), st));
+    HIP_TRY(hipMemcpyAsync(t->h_root, out[L - 1], p.layers[L - 1].out, hipMemcpyDeviceToHost, st), ICICLE_COPY_FAILED);
+    if (!t->on_device) HIP_TRY(hipMemcpyAsync(t->h_store, store, t->store_bytes(), hipMemcpyDeviceToHost, st), ICICLE_COPY_FAILED);
+    if (!cfg->is_async) HIP_TRY(hipStreamSynchronize(st), ICICLE_SYNCHRONIZATION_FAILED);
+    t->built = true;
+    return ICICLE_SUCCESS;
+  }
+
+  static icicle_error_t tree_proof(const Tree* t, const uint8_t* leaves, uint64_t leaves_size, uint64_t leaf_idx, bool pruned,
+                                   const icicle_merkle_tree_config_t* cfg, Proof* proof)
+  {
+    if (!t->built) return ICICLE_INVALID_ARGUMENT;
+    const MerklePlan& p = t->plan;
+    MerklePadding pad;
+    if (merkle_padding(p, leaves_size, cfg->padding_policy, &pad)) return ICICLE_INVALID_ARGUMENT;
+    const int L = p.L(), m = t->store_min;
+    MerkleProofPlan pp;
+    if (merkle_proof_plan(p, leaf_idx, pruned, m, &pp)) return ICICLE_INVALID_ARGUMENT;
+    ICICLE_TRY(bind_current_device());
+    hipStream_t st = (hipStream_t)cfg->stream;
+    const uint64_t c0 = p.layers[0].chunk, es = p.leaf_element_size;
+    const bool dev_leaves = cfg->is_leaves_on_device, last_value = cfg->padding_policy == MERKLE_PAD_LAST && pad.pad_bytes > 0;
+
+    // everything that lives on the device is gathered into one staging buffer -- [leaf chunk | last element | path] -- and
+    // comes back in one copy behind one synchronisation; host-resident pieces are copied on the host
+    const uint64_t path_at = (c0 + es + 15) & ~15ull, stage_bytes = path_at + pp.path_size;
+    TempBuf d_stage, d_sub, d_low;
+    HIP_TRY(d_stage.alloc(stage_bytes, st), ICICLE_ALLOCATION_FAILED);
+    uint8_t* stage = d_stage.as<uint8_t>();
+    bool device_pieces = false;
+
+    // the leaf: the part of chunk0 that lies inside the leaves
+    const uint64_t leaf_lo = pp.chunk0 * c0, leaf_real = leaf_lo >= leaves_size ? 0 : std::min(c0, leaves_size - leaf_lo);
+    if (dev_leaves) {
+      if (leaf_real) HIP_TRY(hipMemcpyAsync(stage, leaves + leaf_lo, leaf_real, hipMemcpyDeviceToDevice, st), ICICLE_COPY_FAILED);
+      if (last_value) HIP_TRY(hipMemcpyAsync(stage + c0, leaves + pad.last_off, es, hipMemcpyDeviceToDevice, st), ICICLE_COPY_FAILED);
+      device_pieces = leaf_real || last_value;
+    }
+
+    // layers below store_min: re-hash the sub-tree under the on-path node of layer store_min
+    uint8_t* sub_out[MERKLE_MAX_LAYERS];
+    uint64_t sub_node0[MERKLE_MAX_LAYERS];
+    if (m > 0) {
+      LeafSource src{leaves, leaves_size, last_value ? leaves + pad.last_off : nullptr};
+      if (!dev_leaves) {
+        const uint64_t lo = pp.sub_first * c0, real = lo >= leaves_size ? 0 : std::min(pp.sub_count * c0, leaves_size - lo);
+        const uint64_t last_at = (real + 15) & ~15ull;
+        HIP_TRY(d_sub.alloc(last_at + es, st), ICICLE_ALLOCATION_FAILED);
+        if (real) HIP_TRY(hipMemcpyAsync(d_sub.ptr(), leaves + lo, real, hipMemcpyHostToDevice, st), ICICLE_COPY_FAILED);
+        if (last_value) HIP_TRY(hipMemcpyAsync(d_sub.as<uint8_t>() + last_at, leaves + pad.last_off, es, hipMemcpyHostToDevice, st), ICICLE_COPY_FAILED);
+        // only offsets in [lo, lo + real) are read through this pointer
+        src.base = reinterpret_cast<const uint8_t*>((uintptr_t)d_sub.ptr() - lo);
+        src.last = last_value ? d_sub.as<uint8_t>() + last_at : nullptr;
+      }
+      uint64_t bytes = 0;
+      for (int i = 0; i < m; i++) {
+        const uint64_t ratio = p.layers[0].count / p.layers[i].count; // layer-0 chunks per node of layer i
+        sub_node0[i] = pp.sub_first / ratio;
+        bytes += (pp.sub_count / ratio * p.layers[i].out + 15) & ~15ull;
+      }
+      HIP_TRY(d_low.alloc(bytes, st), ICICLE_ALLOCATION_FAILED);
+      bytes = 0;
+      for (int i = 0; i < m; i++) {
+        sub_out[i] = d_low.as<uint8_t>() + bytes;
+        bytes += (pp.sub_count / (p.layers[0].count / p.layers[i].count) * p.layers[i].out + 15) & ~15ull;
+      }
+      ICICLE_TRY(hash_layers(*t, src, pp.sub_first, pp.sub_count, m, sub_out, top_max_of(cfg), st));
+    }
+
+    proof->pruned = pruned;
+    proof->leaf_idx = leaf_idx;
+    proof->path.assign(pp.path_size, 0);
+    // the path, group by group; pruned: the two runs around the on-path digest
+    for (int i = 0; i + 1 < L; i++) {
+      const MerkleProofStep& s = pp.steps[i];
+      const uint64_t o = p.layers[i].out;
+      const uint64_t run_src[2] = {s.src_off, pruned ? s.src_off + s.skip_off + o : 0};
+      const uint64_t run_len[2] = {pruned ? s.skip_off : s.len, pruned ? s.len - s.skip_off - o : 0};
+      uint64_t dst = s.dst_off;
+      for (int r = 0; r < 2; r++) {
+        if (run_len[r] == 0) continue;
+        if (i < m) {
+          HIP_TRY(hipMemcpyAsync(stage + path_at + dst, sub_out[i] + (run_src[r] - sub_node0[i] * o), run_len[r], hipMemcpyDeviceToDevice, st), ICICLE_COPY_FAILED);
+          device_pieces = true;
+        } else if (t->on_device) {
+          HIP_TRY(hipMemcpyAsync(stage + path_at + dst, t->d_store + t->store_off(i) + run_src[r], run_len[r], hipMemcpyDeviceToDevice, st), ICICLE_COPY_FAILED);
+          device_pieces = true;
+        }
+        dst += run_len[r];
+      }
+    }
+    std::vector<uint8_t> host_stage;
+    if (device_pieces) {
+      host_stage.resize(stage_bytes);
+      HIP_TRY(hipMemcpyAsync(host_stage.data(), stage, stage_bytes, hipMemcpyDeviceToHost, st), ICICLE_COPY_FAILED);
+    }
+    // the one synchronisation: also orders this call behind an asynchronous build on the same stream (h_store, h_root)
+    HIP_TRY(hipStreamSynchronize(st), ICICLE_SYNCHRONIZATION_FAILED);
+    if (device_pieces) std::memcpy(proof->path.data(), host_stage.data() + path_at, pp.path_size);
+    if (!t->on_device)
+      for (int i = m; i + 1 < L; i++) {
+        const MerkleProofStep& s = pp.steps[i];
+        const uint64_t o = p.layers[i].out;
+        const uint8_t* g = t->h_store + t->store_off(i) + s.src_off;
+        if (pruned) {
+          std::memcpy(proof->path.data() + s.dst_off, g, s.skip_off);
+          std::memcpy(proof->path.data() + s.dst_off + s.skip_off, g + s.skip_off + o, s.len - s.skip_off - o);
+        } else {
+          std::memcpy(proof->path.data() + s.dst_off, g, s.len);
+        }
+      }
+    // the leaf chunk, padded per policy
+    proof->leaf.assign(c0, 0);
+    const uint8_t* real_src = dev_leaves ? host_stage.data() : leaves + leaf_lo;
+    if (leaf_real) std::memcpy(proof->leaf.data(), real_src, leaf_real);
+    if (last_value) {
+      const uint8_t* last = dev_leaves ? host_stage.data() + c0 : leaves + pad.last_off;
+      for (uint64_t q = leaf_real; q < c0; q++)
+        proof->leaf[q] = last[(leaf_lo + q) % es];
+    }
+    proof->root.assign(t->h_root, t->h_root + p.layers[L - 1].out);
+    return ICICLE_SUCCESS;
+  }
+
+  // the reference's walk (merkle_tree.h:148-203): hash the leaf, then one hash per layer over the path's group with the previous
+  // digest in its place. All hashes run on the device in one stream-ordered chain. Pruned: every digest is written straight
+  // into its hole in the next layer's input. Full path: the digests come back and are compared with the path on the host.
+  static icicle_error_t tree_verify(const Tree* t, const Proof* pr, bool* valid)
+  {
+    const MerklePlan& p = t->plan;
+    const int L = p.L();
+    *valid = false;
+    if (pr->leaf.empty()) return ICICLE_INVALID_ARGUMENT;
+    if (pr->path.size() != (pr->pruned ? p.pruned_path : p.full_path)) return ICICLE_INVALID_ARGUMENT;
+    if (pr->root.size() != p.layers[L - 1].out) return ICICLE_SUCCESS; // cannot be this tree's root
+    if (pr->leaf_idx > (~0ull) / p.leaf_element_size) return ICICLE_INVALID_ARGUMENT;
+    ICICLE_TRY(bind_current_device());
+    hipStream_t st = nullptr;
+    std::vector<uint64_t> offs;
+    merkle_verify_offsets(p, pr->leaf_idx, pr->leaf.size(), &offs);
+    // host image of the device buffer: [leaf | input of layer 1 | .. | input of layer L-1 | L digests of 64 bytes], all 16-aligned
+    std::vector<uint64_t> in_at(L, 0);
+    uint64_t at = (pr->leaf.size() + 15) & ~15ull;
+    for (int i = 1; i < L; i++) {
+      in_at[i] = at;
+      at += (p.layers[i].chunk + 15) & ~15ull;
+    }
+    const uint64_t dig_at = at, total = dig_at + 64ull * L;
+    std::vector<uint8_t> img(total, 0);
+    std::memcpy(img.data(), pr->leaf.data(), pr->leaf.size());
+    const uint8_t* path = pr->path.data();
+    for (int i = 1; i < L; i++) {
+      const uint64_t c = p.layers[i].chunk, o = p.layers[i - 1].out, off = offs[i - 1];
+      if (pr->pruned) {
+        std::memcpy(img.data() + in_at[i], path, off);
+        std::memcpy(img.data() + in_at[i] + off + o, path + off, c - o - off);
+        path += c - o;
+      } else {
+        std::memcpy(img.data() + in_at[i], path, c);
+        path += c;
+      }
+    }
+    TempBuf d_buf;
+    HIP_TRY(d_buf.alloc(total, st), ICICLE_ALLOCATION_FAILED);
+    uint8_t* d = d_buf.as<uint8_t>();
+    HIP_TRY(hipMemcpyAsync(d, img.data(), dig_at, hipMemcpyHostToDevice, st), ICICLE_COPY_FAILED);
+    for (int i = 0; i < L; i++) {
+      const uint64_t len = i == 0 ? pr->leaf.size() : p.layers[i].chunk;
+      uint8_t* out = d + dig_at + 64ull * i;
+      if (pr->pruned && i + 1 < L) out = d + in_at[i + 1] + offs[i];
+      ICICLE_TRY(launch_batch(t->hashers[i], d + in_at[i], len, len, 1, out, st));
+    }
+    HIP_TRY(hipMemcpyAsync(img.data() + dig_at, d + dig_at, 64ull * L, hipMemcpyDeviceToHost, st), ICICLE_COPY_FAILED);
+    HIP_TRY(hipStreamSynchronize(st), ICICLE_SYNCHRONIZATION_FAILED);
+    bool ok = true;
+    if (!pr->pruned)
+      for (int i = 1; i < L && ok; i++)
+        ok = std::memcmp(img.data() + dig_at + 64ull * (i - 1), img.data() + in_at[i] + offs[i - 1], p.layers[i - 1].out) == 0;
+    *valid = ok && std::memcmp(img.data() + dig_at + 64ull * (L - 1), pr->root.data(), pr->root.size()) == 0;
+    return ICICLE_SUCCESS;
+  }
+
+} // namespace icicle_hip
+
+using namespace icicle_hip;
+
+static_assert(sizeof(icicle_hash_config_t) == 32 && offsetof(icicle_hash_config_t, batch) == 8 && offsetof(icicle_hash_config_t, are_inputs_on_device) == 16 &&
+                offsetof(icicle_hash_config_t, are_outputs_on_device) == 17 && offsetof(icicle_hash_config_t, is_async) == 18 && offsetof(icicle_hash_config_t, ext) == 24,
+              "HashConfig layout (include/icicle/hash/hash_config.h)");
+static_assert(sizeof(icicle_merkle_tree_config_t) == 24 && offsetof(icicle_merkle_tree_config_t, is_leaves_on_device) == 8 &&
+                offsetof(icicle_merkle_tree_config_t, is_tree_on_device) == 9 && offsetof(icicle_merkle_tree_config_t, is_async) == 10 &&
+                offsetof(icicle_merkle_tree_config_t, padding_policy) == 12 && offsetof(icicle_merkle_tree_config_t, ext) == 16,
+              "MerkleTreeConfig layout (include/icicle/merkle/merkle_tree_config.h)");
+
+#define HASH_GUARDED(expr, on_throw)                                                                                   \
+  try {                                                                                                                \
+    return (expr);                                                                                                     \
+  } catch (...) {                                                                                                      \
+    return on_throw;                                                                                                   \
+  }
+
+extern "C" {
+
+icicle_hasher_handle_t icicle_create_keccak_256(uint64_t input_chunk_size) { return (icicle_hasher_handle_t)make_hasher(17, 0x01, input_chunk_size); }
+icicle_hasher_handle_t icicle_create_keccak_512(uint64_t input_chunk_size) { return (icicle_hasher_handle_t)make_hasher(9, 0x01, input_chunk_size); }
+icicle_hasher_handle_t icicle_create_sha3_256(uint64_t input_chunk_size) { return (icicle_hasher_handle_t)make_hasher(17, 0x06, input_chunk_size); }
+icicle_hasher_handle_t icicle_create_sha3_512(uint64_t input_chunk_size) { return (icicle_hasher_handle_t)make_hasher(9, 0x06, input_chunk_size); }
+
+icicle_error_t icicle_hasher_hash(icicle_hasher_handle_t h, const uint8_t* input, uint64_t input_len, const icicle_hash_config_t* config, uint8_t* output)
+{
+  HASH_GUARDED(hasher_hash((const Hasher*)h, input, input_len, config, output), ICICLE_ALLOCATION_FAILED)
+}
+
+uint64_t icicle_hasher_output_size(icicle_hasher_handle_t h) { return h ? 8ull * ((const Hasher*)h)->out_words : 0; }
+
+icicle_error_t icicle_hasher_delete(icicle_hasher_handle_t h)
+{
+  if (!h) return ICICLE_INVALID_POINTER;
+  delete (Hasher*)h;
+  return ICICLE_SUCCESS;
+}
+
+icicle_merkle_tree_handle_t icicle_merkle_tree_create(const icicle_hasher_handle_t* layer_hashes, size_t layer_hashes_len, uint64_t leaf_element_size,
+                                                      uint64_t output_store_min_layer)
+{
+  try {
+    if (!layer_hashes || layer_hashes_len == 0 || layer_hashes_len > (size_t)MERKLE_MAX_LAYERS) return nullptr;
+    std::vector<uint64_t> chunk(layer_hashes_len), out(layer_hashes_len);
+    Tree* t = new Tree;
+    for (size_t i = 0; i < layer_hashes_len; i++) {
+      const Hasher* h = (const Hasher*)layer_hashes[i];
+      if (!h) {
+        delete t;
+        return nullptr;
+      }
+      t->hashers.push_back(*h); // the tree keeps its own copy: the caller may delete the handles
+      chunk[i] = h->chunk, out[i] = 8ull * h->out_words;
+    }
+    if (!merkle_make_plan(chunk.data(), out.data(), (int)layer_hashes_len, leaf_element_size, &t->plan)) {
+      delete t;
+      return nullptr;
+    }
+    t->store_min = (int)std::min<uint64_t>(output_store_min_layer, layer_hashes_len - 1);
+    return (icicle_merkle_tree_handle_t)t;
+  } catch (...) {
+    return nullptr;
+  }
+}
+
+icicle_error_t icicle_merkle_tree_delete(icicle_merkle_tree_handle_t tree)
+{
+  if (!tree) return ICICLE_INVALID_POINTER;
+  Tree* t = (Tree*)tree;
+  t->release();
+  delete t;
+  return ICICLE_SUCCESS;
+}
+
+icicle_error_t icicle_merkle_tree_build(icicle_merkle_tree_handle_t tree, const uint8_t* leaves, uint64_t size, const icicle_merkle_tree_config_t* config)
+{
+  if (!tree || !leaves || !config) return ICICLE_INVALID_POINTER;
+  HASH_GUARDED(tree_build((Tree*)tree, leaves, size, config), ICICLE_ALLOCATION_FAILED)
+}
+
+const uint8_t* icicle_merkle_tree_get_root(icicle_merkle_tree_handle_t tree, size_t* out_size)
+{
+  const Tree* t = (const Tree*)tree;
+  if (!t || !out_size || !t->built) return nullptr;
+  *out_size = (size_t)t->plan.layers.back().out;
+  return t->h_root;
+}
+
+icicle_error_t icicle_merkle_tree_get_proof(icicle_merkle_tree_handle_t tree, const uint8_t* leaves, uint64_t leaves_size, uint64_t leaf_idx, bool is_pruned,
+                                            const icicle_merkle_tree_config_t* config, icicle_merkle_proof_handle_t merkle_proof)
+{
+  if (!tree || !leaves || !config || !merkle_proof) return ICICLE_INVALID_POINTER;
+  HASH_GUARDED(tree_proof((const Tree*)tree, leaves, leaves_size, leaf_idx, is_pruned, config, (Proof*)merkle_proof), ICICLE_ALLOCATION_FAILED)
+}
+
+icicle_error_t icicle_merkle_tree_verify(icicle_merkle_tree_handle_t tree, icicle_merkle_proof_handle_t merkle_proof, bool* valid)
+{
+  if (!tree || !merkle_proof || !valid) return ICICLE_INVALID_POINTER;
+  HASH_GUARDED(tree_verify((const Tree*)tree, (const Proof*)merkle_proof, valid), ICICLE_ALLOCATION_FAILED)
+}
+
+icicle_merkle_proof_handle_t icicle_merkle_proof_create(void) { return (icicle_merkle_proof_handle_t) new (std::nothrow) Proof; }
+
+icicle_merkle_proof_handle_t icicle_merkle_proof_create_with_data(bool pruned_path, int64_t leaf_idx, const uint8_t* leaf, size_t leaf_size, const uint8_t* root,
+                                                                  size_t root_size, const uint8_t* path, size_t path_size)
+{
+  try {
+    if ((!leaf && leaf_size) || (!root && root_size) || (!path && path_size)) return nullptr;
+    Proof* p = new Proof;
+    p->pruned = pruned_path;
+    p->leaf_idx = (uint64_t)leaf_idx;
+    p->leaf.assign(leaf, leaf + leaf_size);
+    p->root.assign(root, root + root_size);
+    p->path.assign(path, path + path_size);
+    return (icicle_merkle_proof_handle_t)p;
+  } catch (...) {
+    return nullptr;
+  }
+}
+
+icicle_error_t icicle_merkle_proof_delete(icicle_merkle_proof_handle_t proof)
+{
+  if (!proof) return ICICLE_INVALID_POINTER;
+  delete (Proof*)proof;
+  return ICICLE_SUCCESS;
+}
+
+bool icicle_merkle_proof_is_pruned(icicle_merkle_proof_handle_t proof) { return proof ? ((const Proof*)proof)->pruned : false; }
+
+const uint8_t* icicle_merkle_proof_get_path(icicle_merkle_proof_handle_t proof, size_t* out_size)
+{
+  if (!proof || !out_size) return nullptr;
+  const Proof* p = (const Proof*)proof;
+  *out_size = p->path.size();
+  return p->path.data();
+}
+
+const uint8_t* icicle_merkle_proof_get_leaf(icicle_merkle_proof_handle_t proof, size_t* out_size, uint64_t* out_leaf_idx)
+{
+  if (!proof || !out_size || !out_leaf_idx) return nullptr;
+  const Proof* p = (const Proof*)proof;
+  *out_size = p->leaf.size();
+  *out_leaf_idx = p->leaf_idx;
+  return p->leaf.data();
+}
+
+const uint8_t* icicle_merkle_proof_get_root(icicle_merkle_proof_handle_t proof, size_t* out_size)
+{
+  if (!proof || !out_size) return nullptr;
+  const Proof* p = (const Proof*)proof;
+  *out_size = p->root.size();
+  return p->root.data();
+}
+
+} // extern "C"

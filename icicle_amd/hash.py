@@ -1,0 +1,73 @@
+"""Keccak / SHA3 batch hashing on the device: mirror of wrappers/rust/icicle-core/src/hash (Hasher, HashConfig) over
+icicle_create_keccak_256 .. / icicle_hasher_hash (include/icicle_hip.h)."""
+import ctypes
+
+import numpy as np
+
+from ._lib import lib, check, HashConfig
+from .runtime import DeviceVec
+
+
+def _ptr(x):
+    """(address, on device): NumPy uint8 / uint32 arrays are host memory, DeviceVec and raw addresses device memory"""
+    if isinstance(x, DeviceVec):
+        return x.ptr, True
+    if isinstance(x, int):
+        return x, True
+    assert isinstance(x, np.ndarray) and x.dtype in (np.uint8, np.uint32) and x.flags["C_CONTIGUOUS"]
+    return x.ctypes.data, False
+
+
+class Hasher:
+    """One of the four Keccak-f[1600] sponges; `chunk` is the default message size in bytes (a Merkle layer's input size)."""
+
+    def __init__(self, handle, chunk):
+        if not handle:
+            raise MemoryError("hasher creation failed")
+        self.handle = handle
+        self.chunk = chunk
+
+    @classmethod
+    def keccak256(cls, chunk=0):
+        return cls(lib.icicle_create_keccak_256(chunk), chunk)
+
+    @classmethod
+    def keccak512(cls, chunk=0):
+        return cls(lib.icicle_create_keccak_512(chunk), chunk)
+
+    @classmethod
+    def sha3_256(cls, chunk=0):
+        return cls(lib.icicle_create_sha3_256(chunk), chunk)
+
+    @classmethod
+    def sha3_512(cls, chunk=0):
+        return cls(lib.icicle_create_sha3_512(chunk), chunk)
+
+    @property
+    def output_size(self) -> int:
+        return int(lib.icicle_hasher_output_size(self.handle))
+
+    def hash(self, inp, size=None, batch=1, out=None, cfg=None):
+        """`batch` messages of `size` bytes back to back in `inp` -> digests back to back. size=None: the whole host array is
+        `batch` equal messages; a device operand needs `size` (or the hasher's default chunk, size=0)."""
+        cfg = cfg or HashConfig.default()
+        ip, cfg.are_inputs_on_device = _ptr(inp)
+        if size is None:
+            size = inp.nbytes // batch if isinstance(inp, np.ndarray) else 0
+        cfg.batch = batch
+        if out is None:
+            out = np.zeros(batch * self.output_size, dtype=np.uint8)
+        op, cfg.are_outputs_on_device = _ptr(out)
+        check(lib.icicle_hasher_hash(self.handle, ip, size, ctypes.byref(cfg), op), "icicle_hasher_hash")
+        return out
+
+    def close(self):
+        if self.handle is not None:
+            check(lib.icicle_hasher_delete(self.handle), "icicle_hasher_delete")
+            self.handle = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass

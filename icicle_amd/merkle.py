@@ -1,0 +1,122 @@
+"""Merkle trees on the device: mirror of wrappers/rust/icicle-core/src/merkle (MerkleTree, MerkleProof, MerkleTreeConfig,
+PaddingPolicy) over icicle_merkle_tree_* / icicle_merkle_proof_* (include/icicle_hip.h)."""
+import ctypes
+
+import numpy as np
+
+from ._lib import lib, check, IcicleError, MerkleTreeConfig
+from .hash import _ptr
+from .runtime import DeviceVec
+
+
+class PaddingPolicy:
+    NONE = 0
+    ZERO_PADDING = 1
+    LAST_VALUE = 2
+
+
+def _bytes_at(ptr, size):
+    return ctypes.string_at(ptr, size) if ptr and size else b""
+
+
+class MerkleProof:
+    def __init__(self, handle=None):
+        self.handle = handle or lib.icicle_merkle_proof_create()
+        if not self.handle:
+            raise MemoryError("proof creation failed")
+
+    @classmethod
+    def with_data(cls, pruned, leaf_idx, leaf: bytes, root: bytes, path: bytes):
+        return cls(lib.icicle_merkle_proof_create_with_data(pruned, leaf_idx, leaf, len(leaf), root, len(root), path, len(path)))
+
+    @property
+    def pruned(self) -> bool:
+        return bool(lib.icicle_merkle_proof_is_pruned(self.handle))
+
+    def _leaf(self):
+        n, idx = ctypes.c_size_t(), ctypes.c_uint64()
+        p = lib.icicle_merkle_proof_get_leaf(self.handle, ctypes.byref(n), ctypes.byref(idx))
+        return _bytes_at(p, n.value), idx.value
+
+    @property
+    def leaf(self) -> bytes:
+        return self._leaf()[0]
+
+    @property
+    def leaf_idx(self) -> int:
+        return self._leaf()[1]
+
+    @property
+    def root(self) -> bytes:
+        n = ctypes.c_size_t()
+        return _bytes_at(lib.icicle_merkle_proof_get_root(self.handle, ctypes.byref(n)), n.value)
+
+    @property
+    def path(self) -> bytes:
+        n = ctypes.c_size_t()
+        return _bytes_at(lib.icicle_merkle_proof_get_path(self.handle, ctypes.byref(n)), n.value)
+
+    def close(self):
+        if self.handle is not None:
+            check(lib.icicle_merkle_proof_delete(self.handle), "icicle_merkle_proof_delete")
+            self.handle = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def _leaves(leaves, size):
+    ptr, on_device = _ptr(leaves)
+    if size is None:
+        size = leaves.nbytes if isinstance(leaves, (np.ndarray, DeviceVec)) else None
+    if size is None:
+        raise ValueError("a raw device address needs size=")
+    return ptr, on_device, size
+
+
+class MerkleTree:
+    """layer_hashers: one Hasher per layer, leaf layer first, each created with its layer's input chunk size"""
+
+    def __init__(self, layer_hashers, leaf_element_size, output_store_min_layer=0):
+        arr = (ctypes.c_void_p * len(layer_hashers))(*[h.handle for h in layer_hashers])
+        self.handle = lib.icicle_merkle_tree_create(arr, len(layer_hashers), leaf_element_size, output_store_min_layer)
+        if not self.handle:
+            raise IcicleError(11, "icicle_merkle_tree_create: the layers do not form a tree")
+
+    def build(self, leaves, size=None, cfg=None):
+        cfg = cfg or MerkleTreeConfig.default()
+        ptr, cfg.is_leaves_on_device, size = _leaves(leaves, size)
+        check(lib.icicle_merkle_tree_build(self.handle, ptr, size, ctypes.byref(cfg)), "icicle_merkle_tree_build")
+        return self
+
+    def root(self):
+        """the root's bytes, None before build; after an asynchronous build synchronise the stream first"""
+        n = ctypes.c_size_t()
+        p = lib.icicle_merkle_tree_get_root(self.handle, ctypes.byref(n))
+        return _bytes_at(p, n.value) if p else None
+
+    def proof(self, leaves, leaf_idx, pruned=False, cfg=None, size=None) -> MerkleProof:
+        cfg = cfg or MerkleTreeConfig.default()
+        ptr, cfg.is_leaves_on_device, size = _leaves(leaves, size)
+        pr = MerkleProof()
+        check(lib.icicle_merkle_tree_get_proof(self.handle, ptr, size, leaf_idx, pruned, ctypes.byref(cfg), pr.handle), "icicle_merkle_tree_get_proof")
+        return pr
+
+    def verify(self, proof: MerkleProof) -> bool:
+        ok = ctypes.c_bool(False)
+        check(lib.icicle_merkle_tree_verify(self.handle, proof.handle, ctypes.byref(ok)), "icicle_merkle_tree_verify")
+        return bool(ok.value)
+
+    def close(self):
+        if self.handle is not None:
+            check(lib.icicle_merkle_tree_delete(self.handle), "icicle_merkle_tree_delete")
+            self.handle = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass

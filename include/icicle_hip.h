@@ -293,6 +293,80 @@ ICICLE_HIP_DECLARE_TRANSPOSE(bls12_377, matrix_transpose)
 ICICLE_HIP_DECLARE_TRANSPOSE(grumpkin, matrix_transpose)
 ICICLE_HIP_DECLARE_TRANSPOSE(stark252, matrix_transpose)
 
+/* ======================================================================================
+ * Hash + Merkle tree: src/hash/hash_c_api.cpp:22-113 (icicle_hasher_*, icicle_create_keccak_256 / _512, icicle_create_sha3_256 / _512),
+ * src/hash/merkle_c_api.cpp:12-166 (icicle_merkle_proof_*, icicle_merkle_tree_*), include/icicle/hash/hash_config.h:15-24
+ * (HashConfig, 32 bytes), include/icicle/merkle/merkle_tree_config.h:11-37 (PaddingPolicy, MerkleTreeConfig, 24 bytes).
+ * Keccak-f[1600] sponges: rate 136 bytes for the 256-bit digests, 72 bytes for the 512-bit ones; Keccak pads 0x01 .. 0x80,
+ * SHA3 0x06 .. 0x80. Creating and deleting handles needs no GPU; hashing, build, get_proof and verify run on the device and
+ * fail without one. Blake2s, Blake3, Poseidon, Poseidon2 and proof serialisation are not built.
+ * ====================================================================================== */
+typedef struct {
+  icicleStreamHandle stream;      /* 0  */
+  uint64_t batch;                 /* 8   messages per call */
+  bool are_inputs_on_device;      /* 16 */
+  bool are_outputs_on_device;     /* 17 */
+  bool is_async;                  /* 18 */
+  icicle_config_extension_t* ext; /* 24  foreign keys ("n_threads" of the CPU backend) are ignored */
+} icicle_hash_config_t;
+
+enum { ICICLE_PADDING_NONE = 0, ICICLE_PADDING_ZERO = 1, ICICLE_PADDING_LAST_VALUE = 2 }; /* merkle_tree_config.h:11-15 */
+typedef struct {
+  icicleStreamHandle stream;      /* 0  */
+  bool is_leaves_on_device;       /* 8  */
+  bool is_tree_on_device;         /* 9   stored layers stay in device memory (otherwise pinned host memory) */
+  bool is_async;                  /* 10 */
+  int padding_policy;             /* 12  ICICLE_PADDING_* */
+  icicle_config_extension_t* ext; /* 16  "hip_merkle_top_max_hashes" (int): layers with at most this many hashes, and all above them,
+                                         run in ONE launch (default 1024; 0 = one launch per layer) */
+} icicle_merkle_tree_config_t;
+
+typedef struct icicle_hasher* icicle_hasher_handle_t;
+typedef struct icicle_merkle_tree* icicle_merkle_tree_handle_t;
+typedef struct icicle_merkle_proof* icicle_merkle_proof_handle_t;
+
+/* input_chunk_size: the default message size of the hasher (0 = none) -- the size of one input of a Merkle tree layer */
+icicle_hasher_handle_t icicle_create_keccak_256(uint64_t input_chunk_size); /* hash_c_api.cpp:71 */
+icicle_hasher_handle_t icicle_create_keccak_512(uint64_t input_chunk_size); /* :84 */
+icicle_hasher_handle_t icicle_create_sha3_256(uint64_t input_chunk_size);   /* :97 */
+icicle_hasher_handle_t icicle_create_sha3_512(uint64_t input_chunk_size);   /* :110 */
+/* config->batch messages of input_len bytes each, back to back (input_len = 0: the hasher's default chunk size; both 0:
+ * INVALID_ARGUMENT); digests of 32 / 64 bytes back to back. Any length, any pointer alignment. */
+icicle_error_t icicle_hasher_hash(icicle_hasher_handle_t h, const uint8_t* input, uint64_t input_len, const icicle_hash_config_t* config, uint8_t* output); /* :22 */
+uint64_t icicle_hasher_output_size(icicle_hasher_handle_t h); /* :40 */
+icicle_error_t icicle_hasher_delete(icicle_hasher_handle_t h); /* :52 */
+
+/* Layer i hashes n_i inputs of c_i bytes (its hasher's chunk size) into digests of o_i bytes: c_{i+1} % o_i == 0 is required
+ * (NULL otherwise), n_{L-1} = 1, n_{i-1} = n_i * c_i / o_{i-1}, the tree takes n_0 * c_0 bytes of leaves. The tree copies the
+ * hashers. Layers >= output_store_min_layer are kept (device or pinned host memory per is_tree_on_device), lower ones are
+ * freed after the build and re-hashed, one sub-tree, by get_proof from the caller's leaves. */
+icicle_merkle_tree_handle_t icicle_merkle_tree_create(const icicle_hasher_handle_t* layer_hashes, size_t layer_hashes_len, uint64_t leaf_element_size,
+                                                      uint64_t output_store_min_layer); /* merkle_c_api.cpp:75 */
+icicle_error_t icicle_merkle_tree_delete(icicle_merkle_tree_handle_t tree);             /* :103 */
+/* The tree over the leaves padded to n_0 * c_0 bytes: ZeroPadding appends zeros, LastValue repeats the last leaf_element_size
+ * bytes (size and c_0 must be multiples of leaf_element_size). INVALID_ARGUMENT: size 0, size beyond the capacity, short leaves
+ * with policy None, a second build. */
+icicle_error_t icicle_merkle_tree_build(icicle_merkle_tree_handle_t tree, const uint8_t* leaves, uint64_t size, const icicle_merkle_tree_config_t* config); /* :111 */
+/* Host pointer owned by the tree (NULL before build). After a build with is_async the bytes are valid once the caller has
+ * synchronised the build's stream. */
+const uint8_t* icicle_merkle_tree_get_root(icicle_merkle_tree_handle_t tree, size_t* out_size); /* :124 */
+/* Proof for element leaf_idx (cpu_merkle_tree.cpp:143-211,546-573): leaf = the whole layer-0 chunk around the element, padded per
+ * policy; path = for layers 0 .. L-2 the c_{i+1} bytes of layer-i digests that form the on-path input of layer i+1 (pruned: without
+ * the on-path digest itself). leaf_idx * leaf_element_size beyond the capacity, or a tree not built: INVALID_ARGUMENT. Synchronises
+ * config->stream once. */
+icicle_error_t icicle_merkle_tree_get_proof(icicle_merkle_tree_handle_t tree, const uint8_t* leaves, uint64_t leaves_size, uint64_t leaf_idx, bool is_pruned,
+                                            const icicle_merkle_tree_config_t* config, icicle_merkle_proof_handle_t merkle_proof); /* :138 */
+/* include/icicle/merkle/merkle_tree.h:148-203, one hash per layer on the device */
+icicle_error_t icicle_merkle_tree_verify(icicle_merkle_tree_handle_t tree, icicle_merkle_proof_handle_t merkle_proof, bool* valid); /* :157 */
+icicle_merkle_proof_handle_t icicle_merkle_proof_create(void); /* :12 */
+icicle_merkle_proof_handle_t icicle_merkle_proof_create_with_data(bool pruned_path, int64_t leaf_idx, const uint8_t* leaf, size_t leaf_size, const uint8_t* root,
+                                                                  size_t root_size, const uint8_t* path, size_t path_size); /* :15 */
+icicle_error_t icicle_merkle_proof_delete(icicle_merkle_proof_handle_t proof);  /* :32 */
+bool icicle_merkle_proof_is_pruned(icicle_merkle_proof_handle_t proof);         /* :40 */
+const uint8_t* icicle_merkle_proof_get_path(icicle_merkle_proof_handle_t proof, size_t* out_size); /* :47 */
+const uint8_t* icicle_merkle_proof_get_leaf(icicle_merkle_proof_handle_t proof, size_t* out_size, uint64_t* out_leaf_idx); /* :56 */
+const uint8_t* icicle_merkle_proof_get_root(icicle_merkle_proof_handle_t proof, size_t* out_size); /* :66 */
+
 /* ---- backend-specific helpers (not part of the reference ABI) ---- */
 const char* icicle_hip_version(void);
 /* The window plan msm() would use for this size / config: c = window bits, nwin = number of c-bit windows of a
