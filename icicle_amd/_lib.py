@@ -264,6 +264,8 @@ _HASH_RESTYPES = {
     "icicle_merkle_proof_get_root": ctypes.c_void_p,
 }
 HASH_HANDLE_SYMBOLS = list(_HASH_RESTYPES)
+# the Blake factories (hash_c_api.cpp:123, :136), a table of their own: name -> restype
+BLAKE_HANDLE_SYMBOLS = {"icicle_create_blake2s": ctypes.c_void_p, "icicle_create_blake3": ctypes.c_void_p}
 
 if not os.path.exists(LIB_PATH):
     raise ImportError(
@@ -275,6 +277,9 @@ for _s in RUNTIME_SYMBOLS + API_SYMBOLS:
     getattr(lib, _s)  # AttributeError if the library does not export a declared symbol
 for _s in HASH_HANDLE_SYMBOLS:
     getattr(lib, _s).restype = _HASH_RESTYPES[_s]  # AttributeError if the symbol is missing, as above
+for _s, _r in BLAKE_HANDLE_SYMBOLS.items():
+    getattr(lib, _s).restype = _r
+    getattr(lib, _s).argtypes = [ctypes.c_uint64]
 lib.icicle_hip_version.restype = ctypes.c_char_p
 lib.create_config_extension.restype = ctypes.c_void_p
 lib.clone_config_extension.restype = ctypes.c_void_p

@@ -1,6 +1,7 @@
-// Keccak / SHA3 batch hashing and Merkle trees on the device.
+// Keccak / SHA3 / Blake2s / Blake3 batch hashing and Merkle trees on the device. The Blake compression and absorb code is blake.hpp,
+// the three message readers hash_readers.hpp (both also compile for the host); the kernels over them are below.
 //
-// C ABI of the reference: icicle/src/hash/hash_c_api.cpp (icicle_create_keccak_256 .., icicle_hasher_hash), src/hash/merkle_c_api.cpp
+// C ABI of the reference: icicle/src/hash/hash_c_api.cpp (icicle_create_keccak_256 .. icicle_create_blake3, icicle_hasher_hash), src/hash/merkle_c_api.cpp
 // (icicle_merkle_tree_*, icicle_merkle_proof_*); configs include/icicle/hash/hash_config.h, include/icicle/merkle/merkle_tree_config.h;
 // tree / proof semantics backend/cpu/src/hash/cpu_merkle_tree.cpp:143-211,546-573 and include/icicle/merkle/merkle_tree.h:148-203.
 //
@@ -24,6 +25,8 @@
 // Keccak is 64-bit integer ALU work, far from the memory roof, so the lanes' strided loads do not matter.
 #include "common.h"
 #include "merkle_plan.h"
+#include "hash_readers.hpp"
+#include "blake.hpp"
 #include <algorithm>
 #include <cstring>
 #include <new>
@@ -88,60 +91,7 @@ namespace icicle_hip {
     }
   }
 
-  // ---- where a lane's message bytes come from ----------------------------------------------------------------------------------
-  // 8-aligned message: 64-bit loads, 128-bit ones where message and offset are 16-aligned
-  struct ReadAligned {
-    const uint8_t* p;
-    bool a16;
-    __device__ __forceinline__ uint64_t word(uint64_t off) const { return *reinterpret_cast<const uint64_t*>(p + off); }
-    __device__ __forceinline__ uint32_t byte(uint64_t off) const { return p[off]; }
-    __device__ __forceinline__ void pair(uint64_t off, uint64_t& lo, uint64_t& hi) const
-    {
-      if (a16 && (off & 15) == 0) {
-        const ulonglong2 v = *reinterpret_cast<const ulonglong2*>(p + off);
-        lo = v.x, hi = v.y;
-      } else {
-        lo = word(off), hi = word(off + 8);
-      }
-    }
-  };
-  // any alignment
-  struct ReadBytes {
-    const uint8_t* p;
-    __device__ __forceinline__ uint32_t byte(uint64_t off) const { return p[off]; }
-    __device__ __forceinline__ uint64_t word(uint64_t off) const
-    {
-      uint64_t w = 0;
-#pragma unroll
-      for (int k = 0; k < 8; k++)
-        w |= (uint64_t)p[off + k] << (8 * k);
-      return w;
-    }
-    __device__ __forceinline__ void pair(uint64_t off, uint64_t& lo, uint64_t& hi) const { lo = word(off), hi = word(off + 8); }
-  };
-  // a layer-0 chunk of a tree that reaches into the padding: byte q of the padded leaves is leaves[q] below `valid`, beyond it
-  // 0 (ZeroPadding: last == nullptr) or byte q % es of the last element (LastValue; valid and the chunk size are multiples of es)
-  struct ReadPadded {
-    const uint8_t* base; // leaves, addressed by the byte offset in the whole tree's leaves
-    uint64_t pos;        // offset of this chunk
-    uint64_t valid;
-    const uint8_t* last;
-    uint64_t es;
-    __device__ __forceinline__ uint32_t byte(uint64_t off) const
-    {
-      const uint64_t q = pos + off;
-      if (q < valid) return base[q];
-      return last ? last[q % es] : 0;
-    }
-    __device__ __forceinline__ uint64_t word(uint64_t off) const
-    {
-      uint64_t w = 0;
-      for (int k = 0; k < 8; k++)
-        w |= (uint64_t)byte(off + k) << (8 * k);
-      return w;
-    }
-    __device__ __forceinline__ void pair(uint64_t off, uint64_t& lo, uint64_t& hi) const { lo = word(off), hi = word(off + 8); }
-  };
+  // where a lane's message bytes come from: ReadAligned, ReadBytes, ReadPadded (hash_readers.hpp)
 
   // sponge over one message of `len` bytes: absorb whole blocks, then the last block with the domain suffix at byte len % rate and
   // 0x80 at the block's last byte (pad10*1). The digest is a[0 .. OUT_WORDS).
@@ -236,6 +186,123 @@ namespace icicle_hip {
     }
   }
 
+  // ---- Blake2s / Blake3 ---------------------------------------------------------------------------------------------------------
+  enum : int { HASH_KECCAK = 0, HASH_BLAKE2S = 1, HASH_BLAKE3 = 2 };
+
+  __device__ __forceinline__ void store_digest32(uint8_t* out, bool aligned, const uint32_t (&h)[8])
+  {
+    if (aligned) {
+#pragma unroll
+      for (int i = 0; i < 4; i++)
+        reinterpret_cast<uint64_t*>(out)[i] = h[2 * i] | (uint64_t)h[2 * i + 1] << 32;
+    } else {
+#pragma unroll
+      for (int i = 0; i < 8; i++)
+#pragma unroll
+        for (int k = 0; k < 4; k++)
+          out[4 * i + k] = (uint8_t)(h[i] >> (8 * k));
+    }
+  }
+
+  // Blake2s of any length, Blake3 of at most one chunk (1024 bytes)
+  template <int KIND, class RD>
+  __device__ __forceinline__ void blake_msg(const RD& rd, uint64_t len, uint32_t (&h)[8])
+  {
+    if constexpr (KIND == HASH_BLAKE2S)
+      blake2s_msg(rd, len, h);
+    else
+      blake3_chunk(rd, len, 0, true, h);
+  }
+
+  // the Blake twin of k_keccak_batch: n messages of `len` bytes at in + t * stride -> 32-byte digests at out + 32 t
+  template <int KIND, bool ALIGNED>
+  __global__ __launch_bounds__(256) void k_blake_batch(const uint8_t* __restrict__ in, uint64_t len, uint64_t stride, uint64_t n, uint32_t flags, uint8_t* __restrict__ out)
+  {
+    const uint64_t step = (uint64_t)gridDim.x * blockDim.x;
+    for (uint64_t t = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; t < n; t += step) {
+      uint32_t h[8];
+      const uint8_t* p = in + t * stride;
+      if constexpr (ALIGNED)
+        blake_msg<KIND>(ReadAligned{p, (flags & HASH_IN_ALIGNED16) != 0}, len, h);
+      else
+        blake_msg<KIND>(ReadBytes{p}, len, h);
+      store_digest32(out + t * 32, (flags & HASH_OUT_ALIGNED8) != 0, h);
+    }
+  }
+
+  // the Blake twin of k_keccak_leaves
+  template <int KIND>
+  __global__ __launch_bounds__(256) void k_blake_leaves(const uint8_t* __restrict__ leaves, uint64_t chunk, uint64_t first, uint64_t n, uint64_t valid,
+                                                         const uint8_t* __restrict__ last, uint64_t es, uint8_t* __restrict__ out)
+  {
+    const uint64_t step = (uint64_t)gridDim.x * blockDim.x;
+    for (uint64_t t = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; t < n; t += step) {
+      uint32_t h[8];
+      blake_msg<KIND>(ReadPadded{leaves, (first + t) * chunk, valid, last, es}, chunk, h);
+      store_digest32(out + t * 32, true, h);
+    }
+  }
+
+  // Blake3 messages of more than one chunk. A per-lane stack of chaining values would be indexed at run time and live in scratch,
+  // so the tree is walked level by level instead: one lane per chunk over all messages writes chaining values, then one launch
+  // per level with one lane per parent (blake.hpp: pairing adjacent nodes, an odd last node carried up, is Blake3's tree).
+  // Chaining value c of message t goes to cv + 32 (t * k + c); k = chunks per message.
+  template <bool ALIGNED>
+  __global__ __launch_bounds__(256) void k_blake3_chunks(const uint8_t* __restrict__ in, uint64_t len, uint64_t stride, uint64_t n, uint64_t k, uint32_t flags,
+                                                          uint8_t* __restrict__ cv)
+  {
+    const uint64_t step = (uint64_t)gridDim.x * blockDim.x, total = n * k;
+    for (uint64_t t = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; t < total; t += step) {
+      const uint64_t msg = t / k, c = t % k, at = c * BLAKE3_CHUNK, clen = len - at < BLAKE3_CHUNK ? len - at : BLAKE3_CHUNK;
+      const uint8_t* p = in + msg * stride + at; // stride % 8 == 0 and at % 1024 == 0 keep the alignment of `in`
+      uint32_t h[8];
+      if constexpr (ALIGNED)
+        blake3_chunk(ReadAligned{p, (flags & HASH_IN_ALIGNED16) != 0}, clen, c, false, h);
+      else
+        blake3_chunk(ReadBytes{p}, clen, c, false, h);
+      store_digest32(cv + t * 32, true, h);
+    }
+  }
+
+  // the same over layer-0 chunks [first, first + n) of a tree that reach into the padding
+  __global__ __launch_bounds__(256) void k_blake3_leaf_chunks(const uint8_t* __restrict__ leaves, uint64_t chunk, uint64_t first, uint64_t n, uint64_t k, uint64_t valid,
+                                                               const uint8_t* __restrict__ last, uint64_t es, uint8_t* __restrict__ cv)
+  {
+    const uint64_t step = (uint64_t)gridDim.x * blockDim.x, total = n * k;
+    for (uint64_t t = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; t < total; t += step) {
+      const uint64_t msg = t / k, c = t % k, at = c * BLAKE3_CHUNK, clen = chunk - at < BLAKE3_CHUNK ? chunk - at : BLAKE3_CHUNK;
+      uint32_t h[8];
+      blake3_chunk(ReadPadded{leaves, (first + msg) * chunk + at, valid, last, es}, clen, c, false, h);
+      store_digest32(cv + t * 32, true, h);
+    }
+  }
+
+  // one level: the k_in nodes of each of n messages (in + 32 (t * k_in + j)) become (k_in + 1) / 2 nodes at out + t * out_stride
+  // + 32 j. k_in == 2 is the root level: ROOT is set and `out` is the digests (out_stride 32, any alignment per flags).
+  __global__ __launch_bounds__(256) void k_blake3_parents(const uint8_t* __restrict__ in, uint64_t k_in, uint64_t n, uint64_t out_stride, uint32_t flags,
+                                                           uint8_t* __restrict__ out)
+  {
+    const uint64_t k_out = (k_in + 1) / 2, total = n * k_out, step = (uint64_t)gridDim.x * blockDim.x;
+    const bool root = k_in == 2, out8 = !root || (flags & HASH_OUT_ALIGNED8) != 0;
+    for (uint64_t t = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; t < total; t += step) {
+      const uint64_t msg = t / k_out, j = t % k_out;
+      const uint4* l = reinterpret_cast<const uint4*>(in + 32 * (msg * k_in + 2 * j)); // the node buffers are 16-aligned
+      uint32_t h[8];
+      const uint4 a0 = l[0], a1 = l[1];
+      const uint32_t left[8] = {a0.x, a0.y, a0.z, a0.w, a1.x, a1.y, a1.z, a1.w};
+      if (2 * j + 1 < k_in) {
+        const uint4 b0 = l[2], b1 = l[3];
+        const uint32_t right[8] = {b0.x, b0.y, b0.z, b0.w, b1.x, b1.y, b1.z, b1.w};
+        blake3_parent(left, right, root, h);
+      } else {
+#pragma unroll
+        for (int i = 0; i < 8; i++)
+          h[i] = left[i];
+      }
+      store_digest32(out + msg * out_stride + 32 * j, out8, h);
+    }
+  }
+
   // ---- the top of a tree in one launch ------------------------------------------------------------------------------------------
   // Once a layer has at most MERKLE_TOP_MAX_HASHES hashes every further layer is smaller still: one launch per layer would be a
   // chain of launches that cannot fill one CU. One block walks them all, a barrier between layers; each layer reads the digests
@@ -244,6 +311,7 @@ namespace icicle_hip {
     const uint8_t* in; // count chunks of `chunk` bytes
     uint8_t* out;
     uint32_t chunk, count, rate_words, suffix;
+    int kind; // HASH_KECCAK (rate_words, suffix), HASH_BLAKE2S, HASH_BLAKE3 (chunk <= 1024: one Blake3 chunk)
   };
   struct MerkleTopArgs {
     MerkleTopLayer l[MERKLE_MAX_LAYERS];
@@ -259,8 +327,17 @@ namespace icicle_hip {
     for (int d = 0; d < args.n; d++) {
       const MerkleTopLayer& l = args.l[d];
       for (uint32_t j = threadIdx.x; j < l.count; j += MERKLE_TOP_THREADS) {
-        uint64_t a[25];
         const ReadAligned rd{l.in + (uint64_t)j * l.chunk, false};
+        if (l.kind != HASH_KECCAK) {
+          uint32_t h[8];
+          if (l.kind == HASH_BLAKE2S)
+            blake2s_msg(rd, l.chunk, h);
+          else
+            blake3_chunk(rd, l.chunk, 0, true, h);
+          store_digest32(l.out + (uint64_t)j * 32, true, h);
+          continue;
+        }
+        uint64_t a[25];
         if (l.rate_words == 17) {
           keccak_msg<17>(rd, l.chunk, l.suffix, a);
           store_digest<4>(l.out + (uint64_t)j * 32, true, a);
@@ -275,13 +352,77 @@ namespace icicle_hip {
 
   // ---- host side ----------------------------------------------------------------------------------------------------------------
   struct Hasher {
-    int rate_words; // 17: 256-bit digest, 9: 512-bit digest
+    int kind;       // HASH_KECCAK, HASH_BLAKE2S, HASH_BLAKE3
+    int rate_words; // Keccak only -- 17: 256-bit digest, 9: 512-bit digest
     int out_words;
-    uint32_t suffix; // 0x01 Keccak, 0x06 SHA3
+    uint32_t suffix; // Keccak only -- 0x01 Keccak, 0x06 SHA3
     uint64_t chunk;  // default input size, 0 = none
+    uint64_t out_bytes() const { return kind == HASH_KECCAK ? 8ull * out_words : 32; }
+    // Blake3 over more than one chunk: several launches and a buffer of chaining values; not for the fused top kernel
+    bool multi_chunk(uint64_t len) const { return kind == HASH_BLAKE3 && len > BLAKE3_CHUNK; }
   };
 
   static unsigned grid_for(uint64_t n) { return (unsigned)std::min<uint64_t>((n + 255) / 256, 1u << 22); }
+
+  // Levels above the chaining values of n Blake3 messages of k chunks each (cv, 32 n k bytes): ping-pong between cv and a second
+  // buffer of half the size, the root level writes the digests to `out`. Both buffers are released in stream order.
+  static icicle_error_t launch_blake3_levels(TempBuf& cv, uint64_t n, uint64_t k, uint32_t flags, uint8_t* out, hipStream_t st)
+  {
+    TempBuf half;
+    if (k > 2) HIP_TRY(half.alloc(32 * n * ((k + 1) / 2), st), ICICLE_ALLOCATION_FAILED);
+    uint8_t* buf[2] = {cv.as<uint8_t>(), half.as<uint8_t>()};
+    for (int cur = 0; k > 1; k = (k + 1) / 2, cur ^= 1) {
+      const uint64_t k_out = (k + 1) / 2;
+      k_blake3_parents<<<grid_for(n * k_out), 256, 0, st>>>(buf[cur], k, n, k == 2 ? 32 : 32 * k_out, flags, k == 2 ? out : buf[cur ^ 1]);
+      LAUNCH_CHECK("k_blake3_parents", st);
+    }
+    return ICICLE_SUCCESS;
+  }
+
+  static icicle_error_t launch_blake_batch(const Hasher& h, const uint8_t* in, uint64_t len, uint64_t stride, uint64_t n, bool a8, uint32_t flags, uint8_t* out,
+                                           hipStream_t st)
+  {
+    if (h.multi_chunk(len)) {
+      const uint64_t k = blake3_chunks_of(len);
+      TempBuf cv;
+      HIP_TRY(cv.alloc(32 * n * k, st), ICICLE_ALLOCATION_FAILED);
+      if (a8)
+        k_blake3_chunks<true><<<grid_for(n * k), 256, 0, st>>>(in, len, stride, n, k, flags, cv.as<uint8_t>());
+      else
+        k_blake3_chunks<false><<<grid_for(n * k), 256, 0, st>>>(in, len, stride, n, k, flags, cv.as<uint8_t>());
+      LAUNCH_CHECK("k_blake3_chunks", st);
+      return launch_blake3_levels(cv, n, k, flags, out, st);
+    }
+    if (h.kind == HASH_BLAKE2S && a8)
+      k_blake_batch<HASH_BLAKE2S, true><<<grid_for(n), 256, 0, st>>>(in, len, stride, n, flags, out);
+    else if (h.kind == HASH_BLAKE2S)
+      k_blake_batch<HASH_BLAKE2S, false><<<grid_for(n), 256, 0, st>>>(in, len, stride, n, flags, out);
+    else if (a8)
+      k_blake_batch<HASH_BLAKE3, true><<<grid_for(n), 256, 0, st>>>(in, len, stride, n, flags, out);
+    else
+      k_blake_batch<HASH_BLAKE3, false><<<grid_for(n), 256, 0, st>>>(in, len, stride, n, flags, out);
+    LAUNCH_CHECK("k_blake_batch", st);
+    return ICICLE_SUCCESS;
+  }
+
+  static icicle_error_t launch_blake_leaves(const Hasher& h, const uint8_t* leaves, uint64_t chunk, uint64_t first, uint64_t n, uint64_t valid, const uint8_t* last,
+                                            uint64_t es, uint8_t* out, hipStream_t st)
+  {
+    if (h.multi_chunk(chunk)) {
+      const uint64_t k = blake3_chunks_of(chunk);
+      TempBuf cv;
+      HIP_TRY(cv.alloc(32 * n * k, st), ICICLE_ALLOCATION_FAILED);
+      k_blake3_leaf_chunks<<<grid_for(n * k), 256, 0, st>>>(leaves, chunk, first, n, k, valid, last, es, cv.as<uint8_t>());
+      LAUNCH_CHECK("k_blake3_leaf_chunks", st);
+      return launch_blake3_levels(cv, n, k, HASH_OUT_ALIGNED8, out, st);
+    }
+    if (h.kind == HASH_BLAKE2S)
+      k_blake_leaves<HASH_BLAKE2S><<<grid_for(n), 256, 0, st>>>(leaves, chunk, first, n, valid, last, es, out);
+    else
+      k_blake_leaves<HASH_BLAKE3><<<grid_for(n), 256, 0, st>>>(leaves, chunk, first, n, valid, last, es, out);
+    LAUNCH_CHECK("k_blake_leaves", st);
+    return ICICLE_SUCCESS;
+  }
 
   static icicle_error_t launch_batch(const Hasher& h, const uint8_t* in, uint64_t len, uint64_t stride, uint64_t n, uint8_t* out, hipStream_t st)
   {
@@ -290,6 +431,7 @@ namespace icicle_hip {
     const bool a8 = ((uintptr_t)in & 7) == 0 && (stride & 7) == 0;
     if (((uintptr_t)in & 15) == 0 && (stride & 15) == 0) flags |= HASH_IN_ALIGNED16;
     if (((uintptr_t)out & 7) == 0) flags |= HASH_OUT_ALIGNED8;
+    if (h.kind != HASH_KECCAK) return launch_blake_batch(h, in, len, stride, n, a8, flags, out, st);
     if (h.rate_words == 17 && a8)
       k_keccak_batch<17, 4, true><<<grid_for(n), 256, 0, st>>>(in, len, stride, n, h.suffix, flags, out);
     else if (h.rate_words == 17)
@@ -306,6 +448,7 @@ namespace icicle_hip {
                                       uint64_t es, uint8_t* out, hipStream_t st)
   {
     if (n == 0) return ICICLE_SUCCESS;
+    if (h.kind != HASH_KECCAK) return launch_blake_leaves(h, leaves, chunk, first, n, valid, last, es, out, st);
     if (h.rate_words == 17)
       k_keccak_leaves<17, 4><<<grid_for(n), 256, 0, st>>>(leaves, chunk, first, n, valid, last, es, h.suffix, out);
     else
@@ -316,8 +459,9 @@ namespace icicle_hip {
 
   static Hasher* make_hasher(int rate_words, uint32_t suffix, uint64_t chunk)
   {
-    return new (std::nothrow) Hasher{rate_words, (25 - rate_words) / 2, suffix, chunk};
+    return new (std::nothrow) Hasher{HASH_KECCAK, rate_words, (25 - rate_words) / 2, suffix, chunk};
   }
+  static Hasher* make_blake(int kind, uint64_t chunk) { return new (std::nothrow) Hasher{kind, 0, 4, 0, chunk}; }
 
   static icicle_error_t hasher_hash(const Hasher* h, const uint8_t* input, uint64_t input_len, const icicle_hash_config_t* cfg, uint8_t* output)
   {
@@ -330,7 +474,7 @@ namespace icicle_hip {
     if (len >= (1ull << 56) / batch) return ICICLE_INVALID_ARGUMENT;
     ICICLE_TRY(bind_current_device());
     hipStream_t st = (hipStream_t)cfg->stream;
-    const size_t in_bytes = (size_t)(len * batch), out_bytes = (size_t)(8ull * h->out_words * batch);
+    const size_t in_bytes = (size_t)(len * batch), out_bytes = (size_t)(h->out_bytes() * batch);
     TempBuf d_in_tmp, d_out_tmp;
     const uint8_t* d_in = input;
     uint8_t* d_out = output;
@@ -397,8 +541,11 @@ namespace icicle_hip {
   };
 
   // Hashes layers [0, upto) of the (sub-)tree over layer-0 chunks [first, first + count): out[i] takes the digests of layer i in
-  // order. Layer 0 goes through the batch kernel where the chunks lie inside the leaves and through k_keccak_leaves where they
-  // reach into the padding; from the first layer above it with at most top_max hashes one k_merkle_top launch does the rest.
+  // order. Layer 0 goes through the hasher's batch kernel where the chunks lie inside the leaves and through its padded-leaf kernel
+  // (k_keccak_leaves, k_blake_leaves, k_blake3_leaf_chunks) where they reach into the padding. From the first layer above it that
+  // has at most top_max hashes one k_merkle_top launch does the rest, except that k_merkle_top hashes a Blake3 input as one chunk:
+  // a Blake3 layer whose inputs exceed 1024 bytes takes its own launches (chunks, then one per tree level), and the fusion starts
+  // above the highest such layer, or not at all.
   static icicle_error_t hash_layers(const Tree& t, const LeafSource& src, uint64_t first, uint64_t count, int upto, uint8_t* const* out, int top_max,
                                     hipStream_t st)
   {
@@ -408,16 +555,20 @@ namespace icicle_hip {
     ICICLE_TRY(launch_batch(t.hashers[0], src.base + first * c0, c0, c0, n_full, out[0], st));
     ICICLE_TRY(launch_leaves(t.hashers[0], src.base, c0, first + n_full, count - n_full, src.valid, src.last, p.leaf_element_size,
                              out[0] + n_full * p.layers[0].out, st));
+    int fuse_from = 1; // first layer with no multi-chunk Blake3 layer at or above it
+    for (int j = 1; j < upto; j++)
+      if (t.hashers[j].multi_chunk(p.layers[j].chunk)) fuse_from = j + 1;
     uint64_t n = count;
     for (int i = 1; i < upto; i++) {
       n /= p.arity(i);
-      if (top_max > 0 && n <= (uint64_t)top_max) {
+      if (i >= fuse_from && top_max > 0 && n <= (uint64_t)top_max) {
         MerkleTopArgs args;
         args.n = 0;
         uint64_t m = n;
         for (int j = i; j < upto; j++) {
           if (j > i) m /= p.arity(j);
-          args.l[args.n++] = MerkleTopLayer{out[j - 1], out[j], (uint32_t)p.layers[j].chunk, (uint32_t)m, (uint32_t)t.hashers[j].rate_words, t.hashers[j].suffix};
+          args.l[args.n++] = MerkleTopLayer{out[j - 1], out[j], (uint32_t)p.layers[j].chunk, (uint32_t)m, (uint32_t)t.hashers[j].rate_words, t.hashers[j].suffix,
+                                            t.hashers[j].kind};
         }
         k_merkle_top<<<1, MERKLE_TOP_THREADS, 0, st>>>(args);
         LAUNCH_CHECK("k_merkle_top", st);
@@ -668,13 +819,15 @@ icicle_hasher_handle_t icicle_create_keccak_256(uint64_t input_chunk_size) { ret
 icicle_hasher_handle_t icicle_create_keccak_512(uint64_t input_chunk_size) { return (icicle_hasher_handle_t)make_hasher(9, 0x01, input_chunk_size); }
 icicle_hasher_handle_t icicle_create_sha3_256(uint64_t input_chunk_size) { return (icicle_hasher_handle_t)make_hasher(17, 0x06, input_chunk_size); }
 icicle_hasher_handle_t icicle_create_sha3_512(uint64_t input_chunk_size) { return (icicle_hasher_handle_t)make_hasher(9, 0x06, input_chunk_size); }
+icicle_hasher_handle_t icicle_create_blake2s(uint64_t input_chunk_size) { return (icicle_hasher_handle_t)make_blake(HASH_BLAKE2S, input_chunk_size); }
+icicle_hasher_handle_t icicle_create_blake3(uint64_t input_chunk_size) { return (icicle_hasher_handle_t)make_blake(HASH_BLAKE3, input_chunk_size); }
 
 icicle_error_t icicle_hasher_hash(icicle_hasher_handle_t h, const uint8_t* input, uint64_t input_len, const icicle_hash_config_t* config, uint8_t* output)
 {
   HASH_GUARDED(hasher_hash((const Hasher*)h, input, input_len, config, output), ICICLE_ALLOCATION_FAILED)
 }
 
-uint64_t icicle_hasher_output_size(icicle_hasher_handle_t h) { return h ? 8ull * ((const Hasher*)h)->out_words : 0; }
+uint64_t icicle_hasher_output_size(icicle_hasher_handle_t h) { return h ? ((const Hasher*)h)->out_bytes() : 0; }
 
 icicle_error_t icicle_hasher_delete(icicle_hasher_handle_t h)
 {
@@ -697,7 +850,7 @@ icicle_merkle_tree_handle_t icicle_merkle_tree_create(const icicle_hasher_handle
         return nullptr;
       }
       t->hashers.push_back(*h); // the tree keeps its own copy: the caller may delete the handles
-      chunk[i] = h->chunk, out[i] = 8ull * h->out_words;
+      chunk[i] = h->chunk, out[i] = h->out_bytes();
     }
     if (!merkle_make_plan(chunk.data(), out.data(), (int)layer_hashes_len, leaf_element_size, &t->plan)) {
       delete t;

@@ -1,5 +1,5 @@
-"""Keccak / SHA3 batch hashing on the device: mirror of wrappers/rust/icicle-core/src/hash (Hasher, HashConfig) over
-icicle_create_keccak_256 .. / icicle_hasher_hash (include/icicle_hip.h)."""
+"""Keccak / SHA3 / Blake2s / Blake3 batch hashing on the device: mirror of wrappers/rust/icicle-core/src/hash (Hasher, HashConfig)
+over icicle_create_keccak_256 .. icicle_create_blake3 / icicle_hasher_hash (include/icicle_hip.h)."""
 import ctypes
 
 import numpy as np
@@ -19,7 +19,8 @@ def _ptr(x):
 
 
 class Hasher:
-    """One of the four Keccak-f[1600] sponges; `chunk` is the default message size in bytes (a Merkle layer's input size)."""
+    """One of the four Keccak-f[1600] sponges, Blake2s-256 or Blake3; `chunk` is the default message size in bytes (a Merkle layer's
+    input size)."""
 
     def __init__(self, handle, chunk):
         if not handle:
@@ -42,6 +43,14 @@ class Hasher:
     @classmethod
     def sha3_512(cls, chunk=0):
         return cls(lib.icicle_create_sha3_512(chunk), chunk)
+
+    @classmethod
+    def blake2s(cls, chunk=0):
+        return cls(lib.icicle_create_blake2s(chunk), chunk)
+
+    @classmethod
+    def blake3(cls, chunk=0):
+        return cls(lib.icicle_create_blake3(chunk), chunk)
 
     @property
     def output_size(self) -> int:

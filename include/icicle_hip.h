@@ -294,7 +294,8 @@ ICICLE_HIP_DECLARE_TRANSPOSE(grumpkin, matrix_transpose)
 ICICLE_HIP_DECLARE_TRANSPOSE(stark252, matrix_transpose)
 
 /* ======================================================================================
- * Hash + Merkle tree: src/hash/hash_c_api.cpp:22-113 (icicle_hasher_*, icicle_create_keccak_256 / _512, icicle_create_sha3_256 / _512),
+ * Hash + Merkle tree: src/hash/hash_c_api.cpp:22-139 (icicle_hasher_*, icicle_create_keccak_256 / _512, icicle_create_sha3_256 / _512,
+ * icicle_create_blake2s, icicle_create_blake3),
  * src/hash/merkle_c_api.cpp:12-166 (icicle_merkle_proof_*, icicle_merkle_tree_*), include/icicle/hash/hash_config.h:15-24
  * (HashConfig, 32 bytes), include/icicle/merkle/merkle_tree_config.h:11-37 (PaddingPolicy, MerkleTreeConfig, 24 bytes).
  * Keccak-f[1600] sponges: rate 136 bytes for the 256-bit digests, 72 bytes for the 512-bit ones; Keccak pads 0x01 .. 0x80,
@@ -330,6 +331,9 @@ icicle_hasher_handle_t icicle_create_keccak_256(uint64_t input_chunk_size); /* h
 icicle_hasher_handle_t icicle_create_keccak_512(uint64_t input_chunk_size); /* :84 */
 icicle_hasher_handle_t icicle_create_sha3_256(uint64_t input_chunk_size);   /* :97 */
 icicle_hasher_handle_t icicle_create_sha3_512(uint64_t input_chunk_size);   /* :110 */
+/* Blake2s-256 (RFC 7693, no key) and Blake3 (default hash mode, 32-byte output; any message length) */
+icicle_hasher_handle_t icicle_create_blake2s(uint64_t input_chunk_size);    /* :123 */
+icicle_hasher_handle_t icicle_create_blake3(uint64_t input_chunk_size);     /* :136 */
 /* config->batch messages of input_len bytes each, back to back (input_len = 0: the hasher's default chunk size; both 0:
  * INVALID_ARGUMENT); digests of 32 / 64 bytes back to back. Any length, any pointer alignment. */
 icicle_error_t icicle_hasher_hash(icicle_hasher_handle_t h, const uint8_t* input, uint64_t input_len, const icicle_hash_config_t* config, uint8_t* output); /* :22 */

@@ -1,7 +1,10 @@
 #!/usr/bin/env python3
-"""Times the device hashers and the Merkle build (profiles/hash_merkle_notes.md): Keccak-256 over 2^k messages of 64 bytes, device to
-device, and a binary Keccak-256 tree over 32-byte leaves with the fused top and with one launch per layer.
-usage: tools/hash_merkle_bench.py [--log-batch 22] [--log-leaves 22 10] [--top-max 0 256 1024] [--reps 5]"""
+"""Times the device hashers and the Merkle build (profiles/hash_merkle_notes.md): one hasher (Keccak-256, Blake2s or Blake3) over 2^k
+messages of 64 bytes, device to device, and a binary tree of that hasher over 32-byte leaves with the fused top and with one launch
+per layer. Several hashers (--hash keccak256 blake3) are timed in interleaved rounds of one process, so their ratio is a property of
+the kernels and not of two runs. Every output line begins with its hasher's name; a run without --hash times Keccak-256 alone, as
+the tool did before it knew other hashers.
+usage: tools/hash_merkle_bench.py [--hash keccak256 [blake2s blake3]] [--log-batch 22] [--log-leaves 22 10] [--top-max 0 256 1024] [--reps 5]"""
 import argparse
 import ctypes
 import os
@@ -13,18 +16,22 @@ import numpy as np
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 
 
-def best(fn, reps):
-    fn()
-    ts = []
-    for _ in range(reps):
-        t = time.perf_counter()
+def best_interleaved(fns, reps):
+    """(best ms, median ms) of each callable after a warm-up call, one call of each per round"""
+    for fn in fns:
         fn()
-        ts.append(time.perf_counter() - t)
-    return min(ts) * 1e3, sorted(ts)[len(ts) // 2] * 1e3
+    ts = [[] for _ in fns]
+    for _ in range(reps):
+        for i, fn in enumerate(fns):
+            t = time.perf_counter()
+            fn()
+            ts[i].append(time.perf_counter() - t)
+    return [(min(t) * 1e3, sorted(t)[len(t) // 2] * 1e3) for t in ts]
 
 
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--hash", choices=["keccak256", "blake2s", "blake3"], nargs="+", default=["keccak256"])
     ap.add_argument("--log-batch", type=int, default=22)
     ap.add_argument("--log-leaves", type=int, nargs="*", default=[22, 10])
     ap.add_argument("--top-max", type=int, nargs="*", default=[0, 1024])
@@ -42,9 +49,11 @@ def main():
     n = 1 << a.log_batch
     d_in = DeviceVec.from_host(rng.integers(0, 256, 64 * n, dtype=np.uint8))
     d_out = DeviceVec(32 * n)
-    h = Hasher.keccak256(64)
-    lo, med = best(lambda: h.hash(d_in, size=64, batch=n, out=d_out), a.reps)
-    print(f"keccak256 batch 2^{a.log_batch} x 64 B device->device: best {lo:.3f} ms, median {med:.3f} ms, {n / lo * 1e3:.3e} hashes/s")
+    hashers = [getattr(Hasher, name)(64) for name in a.hash]
+    timed = best_interleaved([lambda h=h: h.hash(d_in, size=64, batch=n, out=d_out) for h in hashers], a.reps)
+    for name, (lo, med) in zip(a.hash, timed):
+        print(f"{name} batch 2^{a.log_batch} x 64 B device->device: best {lo:.3f} ms, median {med:.3f} ms, {n / lo * 1e3:.3e} hashes/s"
+              + (f", {timed[0][1] / med:.2f}x {a.hash[0]} (medians)" if name != a.hash[0] else ""))
     for logl in a.log_leaves:
         leaves = 1 << logl
         L = logl  # 32-byte leaves, two per 64-byte layer-0 input: 2^(logl-1) hashes at the bottom, logl layers
@@ -56,13 +65,14 @@ def main():
             cfg.is_tree_on_device = True
             cfg.ext = ext
 
-            def build():
+            def build(h):
                 t = MerkleTree([h] * L, 32)
                 t.build(d_leaves, size=32 * leaves, cfg=cfg)
                 t.close()
 
-            lo, med = best(build, a.reps)
-            print(f"merkle build 2^{logl} x 32 B leaves, {L} layers, hip_merkle_top_max_hashes={top}: best {lo:.3f} ms, median {med:.3f} ms")
+            timed = best_interleaved([lambda h=h: build(h) for h in hashers], a.reps)
+            for name, (lo, med) in zip(a.hash, timed):
+                print(f"{name} merkle build 2^{logl} x 32 B leaves, {L} layers, hip_merkle_top_max_hashes={top}: best {lo:.3f} ms, median {med:.3f} ms")
             lib.destroy_config_extension(ext)
 
 
