@@ -154,19 +154,11 @@ namespace icicle_hip {
       fe d = F::template sub<(F::TIGHT ? 4 : 8)>(Q, X3);         // <= 9.2
       // Y3 = R*d - Y1*PPP = R*d + (4p - Y1)*PPP with one shared reduction (lazy, mul_add), produced in Y's own
       // registers; ZZ, ZZZ likewise (no copies of the accumulator at the loop's back edge)
-#ifndef EC_NO_INPLACE
       acc.y = F::template neg<4>(acc.y);
       F::mul_add_inplace_c(acc.y, R, d, PPP); // <= 1.5
       F::mul_inplace(acc.zz, PP);
       F::mul_inplace(acc.zzz, PPP);
       acc.x = X3;
-#else // A/B switch for tools/ab_lib.sh
-      fe Y3 = F::mul_add(R, d, F::template neg<4>(acc.y), PPP);
-      acc.zz = F::mul(acc.zz, PP);
-      acc.zzz = F::mul(acc.zzz, PPP);
-      acc.x = X3;
-      acc.y = Y3;
-#endif
     }
 
     // ---- complete projective arithmetic (identity = (0:1:0)) -----------------------------------

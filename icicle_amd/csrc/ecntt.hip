@@ -6,29 +6,23 @@
 // feature applies: orderings, coset generator, batch / columns_batch, 1/N on the inverse. It uses the
 // twiddle domain of the scalar-field NTT (<curve>_ntt_init_domain).
 //
-// A butterfly here is one 254-bit scalar multiplication (rounds 3-5: 4-bit windows, 252 Jacobian doublings + <= 77 complete
-// additions, ~0.8 M instructions; round 6: GLV split, 27 signed 5-bit joint windows, 130 complete projective doublings + <= 69
-// additions -- mul_words_quad below) plus two point additions; memory traffic is irrelevant by five orders of
-// magnitude, and a stage of an ECNTT of practical size has far fewer butterflies than the chip has lanes: the
-// time of a stage is the LATENCY of one scalar multiplication. So the structure is radix-2 DIT with one launch per
-// stage, points in HBM in the kernels' internal form (Montgomery limbs, 3 x 9 or 3 x 14 words), and FOUR lanes (a DPP
-// quad) per butterfly sharing the doubling chain (two dependent products per doubling, ec_dbl_quad.hpp); the
-// reorderings / coset / 1/N factors are folded into the load and store kernels. The projective representative of a result differs from
-// the reference's (it depends on the order of additions); the group element is the same -- tests
-// compare to_affine() limbs, as for the MSM.
+// A butterfly here is one 254-bit scalar multiplication (mul_words_quad below: GLV split, 27 signed 5-bit joint windows,
+// 130 complete projective doublings + at most 54 + 15 complete additions) plus two point additions; memory traffic is
+// irrelevant by five orders of magnitude, and a stage of an ECNTT of practical size has far fewer butterflies than the
+// chip has lanes: the time of a stage is the LATENCY of one scalar multiplication. So the structure is radix-2 DIT with
+// one launch per stage, points in HBM in the kernels' internal form (Montgomery limbs, 3 x 9 or 3 x 14 words), and FOUR
+// lanes (a DPP quad) per butterfly sharing the doubling chain (two dependent products per doubling, ec_dbl_quad.hpp) and
+// the additions (four product rounds, EcQuadAdd); the reorderings / coset / 1/N factors are folded into the load and
+// store kernels. The projective representative of a result differs from the reference's (it depends on the order of
+// additions); the group element is the same -- tests compare to_affine() limbs, as for the MSM.
+// The chains this one replaced (four-bit windows, Jacobian doublings, no GLV) and their measurements:
+// profiles/retired_variants.md.
 #include "ntt_big_common.hpp"
 #include "ec.hpp"
 #include "glv.hpp"
 #include "ec_dbl_quad.hpp"
 #include "ntt_plan.h"
 #include <algorithm>
-
-// the quad addition of every kernel here: four product rounds (ec_dbl_quad.hpp EcQuadAdd); -DECNTT_ADD5 = ec.hpp add_quad's five, for A/B builds
-#ifdef ECNTT_ADD5
-  #define QADD(a, b, role) E::add_quad(a, b, role)
-#else
-  #define QADD(a, b, role) EcQuadAdd<C>::add(a, b, role)
-#endif
 
 namespace icicle_hip {
 
@@ -39,207 +33,61 @@ namespace icicle_hip {
     using FR = FieldOps<typename C::fr>;
     using Proj = typename E::Proj;
 
-    // k * p, k = 8 canonical words, MSB-first double-and-add over the complete formulas: the cold uses (coset factors on
-    // the way in, 1/N and coset factors on the way out: n scalar multiplications per transform against n/2 log n in the
-    // butterflies)
-    static __device__ Proj mul_words_serial(const Proj& p, const uint32_t* k)
-    {
-      Proj r = E::proj_identity();
-      bool started = false;
-      for (int bit = 255; bit >= 0; bit--) {
-        if (started) r = E::dbl(r);
-        if ((k[bit >> 5] >> (bit & 31)) & 1) {
-          r = started ? E::add(r, p) : p;
-          started = true;
-        }
-      }
-      return r;
-    }
-    // The butterflies' k * p: fixed windows, most significant first (the reference's own scalar multiplication is windowed
-    // too, include/icicle/curves/projective.h:192-224), a run of doublings and COMPLETE additions of table entries per window, so
-    // no input is exceptional. Three generations live here, the older ones behind A/B macros (tools/ab_lib.sh):
-    //   rounds 3-5 (-DECNTT_NO_GLV): 63 four-bit windows, 252 Jacobian doublings (2M + 5S, three product levels per quad) + <= 77 additions;
-    //   round 6a (-DECNTT_JAC_DBL / -DECNTT_WIN4): the GLV split, 33 joint four-bit windows, 132 doublings + <= 80 additions;
-    //   round 6b (default, curves with small 3 b): GLV, 27 joint signed five-bit windows, 130 complete projective doublings in two
-    //   product levels each (ec_dbl_quad.hpp) + <= 69 additions.
-    // The four lanes of a DPP quad hold the same operands and share every doubling and addition -- a butterfly is a latency chain
-    // and an ECNTT stage of practical size has fewer butterflies than
-    // the chip has lanes, so spending four lanes on one chain is free. `tab` = 16 entries of LDS owned by the quad (a
+    // k * p, k = 8 canonical words: every scalar multiplication of a transform (the butterflies, the coset factors and
+    // 1/N). Fixed windows, most significant first (the reference's own scalar multiplication is windowed too,
+    // include/icicle/curves/projective.h:192-224), a run of doublings and COMPLETE additions of table entries per
+    // window, so no input is exceptional:
+    //   k P = k1 P + k2 phi(P), phi(x, y) = (beta x, y), |k1|, |k2| < 2^129 (glv.hpp glv_decompose) -- ONE joint chain
+    //   over both halves; each half is recoded into 27 signed five-bit digits (glv.hpp glv_recode5; the top one is 0 or 1
+    //   and costs nothing while the chain has not started). The multiples of phi(P) are the same table entries with X
+    //   scaled by beta; a negative half or a negative digit negates the entry's Y.
+    // Counts: 130 doublings (26 x 5, EcDblSmallB::dbl_quad, two product levels each) and at most 54 + 15 additions
+    // (2 x 27 in the windows, EcQuadAdd::add, four product rounds each; 15 steps to build the table, the first of them
+    // a doubling). History and measurements of the earlier chains: profiles/retired_variants.md.
+    // The four lanes of a DPP quad hold the same operands and share every doubling and addition -- a butterfly is a
+    // latency chain and an ECNTT stage of practical size has fewer butterflies than the chip has lanes, so spending four
+    // lanes on one chain is free. `tab` = 16 entries of LDS (or global memory) owned by the quad, the multiples 1..16 (a
     // private array indexed by the digit would live in scratch memory). Every lane of the WAVE must call this together
-    // (the table is published with a barrier); lanes with go == false compute on the identity and the result is unused.
-    // (round 6a) dbl_jac_quad (ec.hpp) with the range management of dbl_jac_lazy: inside a run of doublings only D is brought back below 4 p
-    // (X < 9.2 p, Y < 17.8 p, Z < 2.8 p is a fixed point of the step), two conditional subtractions per step instead of eight. In quad
-    // form every lane executes the linear steps redundantly, so they were ~45 % of a doubling's instructions. The caller reduces Y once
-    // per window. The same operand flow, one lane's arithmetic, runs under the host bound tracker: tests/host_math_harness.cpp op 7.
-    static __device__ __forceinline__ typename E::Jac dbl_jac_quad_lazy(const typename E::Jac& p, uint32_t role)
-    {
-      using fe = typename F::fe;
-      const fe l1 = F::mul(E::lane_select(role == 0, p.x, p.y), E::lane_select(role == 0, p.x, E::lane_select(role == 1, p.y, p.z)));
-      const fe A = E::template quad_bcast<0>(l1), B = E::template quad_bcast<1>(l1), YZ = E::template quad_bcast<2>(l1);
-      const fe Ev = F::add(F::dbl(A), A);
-      const fe l2 = F::sqr(E::lane_select(role == 0, Ev, E::lane_select(role == 1, B, F::add(p.x, B))));
-      const fe Fv = E::template quad_bcast<0>(l2), CC = E::template quad_bcast<1>(l2), t = E::template quad_bcast<2>(l2);
-      const fe D = F::below4(F::dbl(F::template sub<4>(t, F::add(A, CC))));
-      typename E::Jac r;
-      r.x = F::template sub<8>(Fv, F::dbl(D));
-      const fe m = F::mul(Ev, F::template sub<16>(D, r.x));
-      r.y = F::template sub<16>(m, F::dbl(F::dbl(F::dbl(CC))));
-      r.z = F::dbl(YZ);
-      return r;
-    }
-    // The two coordinate changes around a window's doublings, (X : Y : Z) -> (X Z, Y Z^2, Z) and back (X Z : Y : Z^3), are three products
-    // each; spread over the quad they are two dependent products per lane instead of three (ec.hpp to_jac / from_jac, same values).
-    static __device__ __forceinline__ typename E::Jac to_jac_quad(const Proj& p, uint32_t role)
-    {
-      using fe = typename F::fe;
-      const fe l1 = F::mul(E::lane_select(role == 0, p.x, p.z), p.z); // role 0: X Z ; others: Z^2
-      typename E::Jac r;
-      r.x = E::template quad_bcast<0>(l1);
-      r.y = F::mul(p.y, E::template quad_bcast<1>(l1));
-      r.z = p.z;
-      return r;
-    }
-    static __device__ __forceinline__ Proj from_jac_quad(const typename E::Jac& j, uint32_t role)
-    {
-      using fe = typename F::fe;
-      if (F::is_zero(j.z)) return E::proj_identity(); // (uniform over the quad: every lane holds the same point)
-      const fe l1 = F::mul(E::lane_select(role == 0, j.x, j.z), j.z); // role 0: X Z ; others: Z^2
-      Proj r;
-      r.x = E::template quad_bcast<0>(l1);
-      r.y = j.y;
-      r.z = F::mul(E::template quad_bcast<1>(l1), j.z);
-      return r;
-    }
+    // (the table is published with a barrier); a quad past the end of the work computes on the identity and its result is unused.
+    // One lane's arithmetic of the same operand flow runs under the host bound tracker: tests/host_math_harness.cpp op 7.
     static __device__ Proj mul_words_quad(const Proj& p, const uint32_t* k, uint32_t role, Proj* tab)
     {
-      // the additions are quad-cooperative as well (five product latencies instead of fourteen): -DECNTT_NOQUADADD = A/B
-#ifdef ECNTT_NOQUADADD
-      auto ADD = [&](const Proj& a, const Proj& b) { return E::add(a, b); };
-#else
-      auto ADD = [&](const Proj& a, const Proj& b) { return QADD(a, b, role); };
-#endif
-#if !defined(ECNTT_NO_GLV) && !defined(ECNTT_JAC_DBL) && !defined(ECNTT_NOQUAD) && !defined(ECNTT_NO_LAZY_DBL) && !defined(ECNTT_WIN4)
-      constexpr bool WIN5 = C::B3_SMALL != 0; // signed five-bit windows over the multiples 1..16 (below); -DECNTT_WIN4 = A/B
-#else
-      constexpr bool WIN5 = false;
-#endif
-      if constexpr (WIN5) {
-        Proj e = p;
-        for (int i = 0; i < 16; i++) { // tab[i] = (i + 1) p
-          if (role == 0) tab[i] = e;
-          if (i < 15) e = (i == 0) ? EcDblSmallB<C>::dbl_quad(p, role) : ADD(e, p);
-        }
-      } else {
-        Proj e = E::proj_identity();
-        for (int i = 0; i < 16; i++) {
-          if (role == 0) tab[i] = e;
-          e = (i == 0) ? p : ((i == 1) ? E::dbl(p) : ADD(e, p)); // 0, p, 2p, 3p, ...
-        }
+      static_assert(has_small_b3<C>::value, "mul_words_quad: G1 curves with 3 b = 3, 9 or 12 only (EcDblSmallB)");
+      Proj e = p;
+      for (int i = 0; i < 16; i++) { // tab[i] = (i + 1) p
+        if (role == 0) tab[i] = e;
+        if (i < 15) e = (i == 0) ? EcDblSmallB<C>::dbl_quad(p, role) : EcQuadAdd<C>::add(e, p, role);
       }
       __syncthreads();
-      auto quad_dbl4 = [&](Proj& r) {
-#if !defined(ECNTT_JAC_DBL) && !defined(ECNTT_NOQUAD) && !defined(ECNTT_NO_LAZY_DBL) // (-DECNTT_JAC_DBL: the Jacobian chain below, for A/B builds)
-        if constexpr (C::B3_SMALL != 0) {
-          // complete projective doublings in two product levels each, no coordinate change around the window (ec_dbl_quad.hpp)
-          for (int q = 0; q < 4; q++)
-            r = EcDblSmallB<C>::dbl_quad(r, role);
-          return;
-        }
-#endif
-#if defined(ECNTT_NOQUAD) || defined(ECNTT_NO_LAZY_DBL)
-        typename E::Jac j = E::to_jac(r);
-#else
-        typename E::Jac j = to_jac_quad(r, role);
-#endif
-#ifdef ECNTT_NOQUAD
-        for (int q = 0; q < 4; q++)
-          j = E::dbl_jac(j);
-#elif defined(ECNTT_NO_LAZY_DBL) // (A/B: the fully reduced quad doubling of rounds 3-5)
-        for (int q = 0; q < 4; q++)
-          j = E::dbl_jac_quad(j, role);
-#else
-        for (int q = 0; q < 4; q++)
-          j = dbl_jac_quad_lazy(j, role);
-        F::template cond_sub<16>(j.y); // back to Y < 4 p, the bound the complete addition (and the butterfly's negation) is laid out for
-        j.y = F::below4(j.y);
-        r = from_jac_quad(j, role);
-        return;
-#endif
-        r = E::from_jac(j);
-      };
       Proj r = E::proj_identity();
       bool started = false;
-#ifndef ECNTT_NO_GLV // (-DECNTT_NO_GLV: the plain 63-window chain of rounds 3-5, for A/B builds with tools/ab_lib.sh)
-      {
-        // Round 6: k P = k1 P + k2 phi(P), phi(x, y) = (beta x, y), |k1|, |k2| < 2^129 (glv.hpp) -- ONE joint chain of 33 windows
-        // (128 + 4 doublings) with up to two additions each instead of 63 windows (252 doublings) with one: the multiples of
-        // phi(P) are the same table entries with X scaled by beta, a negative half negates the entry's Y. The chain is the latency
-        // of a stage and, from 2^16 points up, its throughput: 252 x 3 + 78 x 5 dependent product latencies become 132 x 3 + 81 x 5.
-        uint32_t k1[5], k2[5];
-        bool n1, n2;
-        glv_decompose<C>(k, k1, n1, k2, n2);
-        const typename F::fe beta = F::from_const(C::GLV_BETA);
-        if constexpr (WIN5) {
-          // 27 signed five-bit windows (glv.hpp glv_recode5; the top one is 0 or 1 and costs nothing while the chain has not started):
-          // 130 doublings and <= 54 additions where four-bit windows take 132 and <= 66 -- the table is the same 16 entries, now the
-          // multiples 1..16, and a negative digit negates the entry's Y like a negative half does.
-          if constexpr (C::B3_SMALL != 0) {
-            uint32_t pk1[7], pk2[7];
-            glv_recode5(k1, pk1);
-            glv_recode5(k2, pk2);
-            for (int d = 26; d >= 0; d--) {
-              const uint32_t b1 = (pk1[d >> 2] >> ((d & 3) * 8)) & 0xFFu, b2 = (pk2[d >> 2] >> ((d & 3) * 8)) & 0xFFu;
-              if (started) {
-                for (int q = 0; q < 5; q++)
-                  r = EcDblSmallB<C>::dbl_quad(r, role);
-              }
-              if (b1 & 31u) {
-                Proj t = tab[(b1 & 31u) - 1];
-                if (n1 != ((b1 & 0x80u) != 0)) t.y = F::template neg<4>(F::below4(t.y));
-                r = started ? ADD(r, t) : t;
-                started = true;
-              }
-              if (b2 & 31u) {
-                Proj t = tab[(b2 & 31u) - 1];
-                t.x = F::mul(t.x, beta);
-                if (n2 != ((b2 & 0x80u) != 0)) t.y = F::template neg<4>(F::below4(t.y));
-                r = started ? ADD(r, t) : t;
-                started = true;
-              }
-            }
-          }
-          return r;
-        }
-        for (int d = 32; d >= 0; d--) {
-          const uint32_t d1 = (k1[d >> 3] >> ((d & 7) * 4)) & 15u, d2 = (k2[d >> 3] >> ((d & 7) * 4)) & 15u;
-          if (started) quad_dbl4(r);
-          if (d1) {
-            Proj t = tab[d1];
-            if (n1) t.y = F::template neg<4>(F::below4(t.y));
-            r = started ? ADD(r, t) : t;
-            started = true;
-          }
-          if (d2) {
-            Proj t = tab[d2];
-            t.x = F::mul(t.x, beta);
-            if (n2) t.y = F::template neg<4>(F::below4(t.y));
-            r = started ? ADD(r, t) : t;
-            started = true;
-          }
-        }
-      }
-#else
-      for (int d = 63; d >= 0; d--) {
-        const uint32_t dig = (k[d >> 3] >> ((d & 7) * 4)) & 15u;
+      uint32_t k1[5], k2[5];
+      bool n1, n2;
+      glv_decompose<C>(k, k1, n1, k2, n2);
+      const typename F::fe beta = F::from_const(C::GLV_BETA);
+      uint32_t pk1[7], pk2[7];
+      glv_recode5(k1, pk1);
+      glv_recode5(k2, pk2);
+      for (int d = 26; d >= 0; d--) {
+        const uint32_t b1 = (pk1[d >> 2] >> ((d & 3) * 8)) & 0xFFu, b2 = (pk2[d >> 2] >> ((d & 3) * 8)) & 0xFFu;
         if (started) {
-          quad_dbl4(r);
-          if (dig) r = ADD(r, tab[dig]);
-        } else if (dig) {
-          r = tab[dig];
+          for (int q = 0; q < 5; q++)
+            r = EcDblSmallB<C>::dbl_quad(r, role);
+        }
+        if (b1 & 31u) {
+          Proj t = tab[(b1 & 31u) - 1];
+          if (n1 != ((b1 & 0x80u) != 0)) t.y = F::template neg<4>(F::below4(t.y));
+          r = started ? EcQuadAdd<C>::add(r, t, role) : t;
+          started = true;
+        }
+        if (b2 & 31u) {
+          Proj t = tab[(b2 & 31u) - 1];
+          t.x = F::mul(t.x, beta);
+          if (n2 != ((b2 & 0x80u) != 0)) t.y = F::template neg<4>(F::below4(t.y));
+          r = started ? EcQuadAdd<C>::add(r, t, role) : t;
           started = true;
         }
       }
-#endif
       return r;
     }
     // scalar given as packed Montgomery words (twiddle / coset tables) -> canonical words
@@ -324,7 +172,7 @@ namespace icicle_hip {
   }
 
   // stage q: pairs (i, i + 2^q) inside blocks of 2^(q+1); twiddle w_n^(pos * n / 2^(q+1)).
-  // Four lanes (one DPP quad) per butterfly: see EcNtt::mul_words<QUAD>. All four lanes load the same pair, lane 0 stores.
+  // Four lanes (one DPP quad) per butterfly: see EcNtt::mul_words_quad. All four lanes load the same pair, lane 0 stores.
   // gtabs != nullptr: the quads' 16-entry tables live in global memory (L2-resident: one 108 / 168-byte entry is read per
   // window, ~6 % of a chain's latency) instead of LDS. LDS holds 16 tables per 64-thread block = 27.6 / 43 KB, i.e. 5 / 3 waves
   // per CU = 20480 / 12288 butterflies in flight; a stage with more than that (2^16 points: 32768) took three rounds of
@@ -350,44 +198,24 @@ namespace icicle_hip {
     typename E::Proj* base = work + b * lay.n;
     const typename E::Proj u = live ? base[i] : E::proj_identity(); // (dead quads: not the slots the last live quad rewrites in place)
     typename E::Proj v = live ? base[i + half] : E::proj_identity();
-#ifdef ECNTT_OLD_MUL
-    if (pos != 0) {
-      const uint64_t max_mask = ((uint64_t)1 << lay.log_max) - 1;
-      uint64_t idx = (pos << (lay.logn - 1 - q)) << (lay.log_max - lay.logn);
-      if (lay.inverse) idx = (((uint64_t)1 << lay.log_max) - idx) & max_mask;
-      uint32_t k[8];
-      T::canonical_from_mont(k, tw + idx * 8);
-      v = T::mul_words_serial(v, k);
-    }
-#else
-    {
-      extern __shared__ uint32_t stage_tabs_raw[]; // [quad][multiple] when the tables are in LDS (dynamic size: 0 otherwise)
-      typename E::Proj* tab = gtabs ? gtabs + (size_t)(lane >> 2) * 16 : reinterpret_cast<typename E::Proj*>(stage_tabs_raw) + (size_t)(threadIdx.x >> 2) * 16;
-      const uint64_t max_mask = ((uint64_t)1 << lay.log_max) - 1;
-      uint64_t idx = (pos << (lay.logn - 1 - q)) << (lay.log_max - lay.logn);
-      if (lay.inverse) idx = (((uint64_t)1 << lay.log_max) - idx) & max_mask;
-      uint32_t k[8];
-      T::canonical_from_mont(k, tw + (pos != 0 ? idx : 0) * 8);
-      if (pos == 0) { // w^0 = 1: k = 1, the multiplication returns v itself (one table read, no doubling)
+    extern __shared__ uint32_t stage_tabs_raw[]; // [quad][multiple] when the tables are in LDS (dynamic size: 0 otherwise)
+    typename E::Proj* tab = gtabs ? gtabs + (size_t)(lane >> 2) * 16 : reinterpret_cast<typename E::Proj*>(stage_tabs_raw) + (size_t)(threadIdx.x >> 2) * 16;
+    const uint64_t max_mask = ((uint64_t)1 << lay.log_max) - 1;
+    uint64_t idx = (pos << (lay.logn - 1 - q)) << (lay.log_max - lay.logn);
+    if (lay.inverse) idx = (((uint64_t)1 << lay.log_max) - idx) & max_mask;
+    uint32_t k[8];
+    T::canonical_from_mont(k, tw + (pos != 0 ? idx : 0) * 8);
+    if (pos == 0) { // w^0 = 1: k = 1, the multiplication returns v itself (one table read, no doubling)
 #pragma unroll
-        for (int w = 0; w < 8; w++)
-          k[w] = w == 0 ? 1u : 0u;
-      }
-      v = T::mul_words_quad(v, k, role, tab);
+      for (int w = 0; w < 8; w++)
+        k[w] = w == 0 ? 1u : 0u;
     }
-#endif
-#ifdef ECNTT_NOQUADADD
-    if (live && role == 0) {
-      base[i] = E::add(u, v);
-      base[i + half] = E::add(u, T::neg(v));
-    }
-#else
-    const typename E::Proj s0 = QADD(u, v, role), s1 = QADD(u, T::neg(v), role);
+    v = T::mul_words_quad(v, k, role, tab);
+    const typename E::Proj s0 = EcQuadAdd<C>::add(u, v, role), s1 = EcQuadAdd<C>::add(u, T::neg(v), role);
     if (live && role == 0) {
       base[i] = s0;
       base[i + half] = s1;
     }
-#endif
   }
 
   // ---- radix-2^r "matrix form" stages: r radix-2 stages for the LATENCY of one scalar multiplication -----------------
@@ -460,10 +288,10 @@ namespace icicle_hip {
     const typename E::Proj* tg = terms + (grp * (R - 1)) * hr + u; // term (j, u) at tg[(j - 1) * hr]
     typename E::Proj ev = work[base], od = tg[(size_t)(hr - 1) * hr]; // A_0 ; T_{R/2}
     for (uint32_t j = 1; j < hr; j++)
-      ev = QADD(ev, tg[(size_t)(j - 1) * hr], role);
+      ev = EcQuadAdd<C>::add(ev, tg[(size_t)(j - 1) * hr], role);
     for (uint32_t j = hr + 1; j < R; j++)
-      od = QADD(od, tg[(size_t)(j - 1) * hr], role);
-    const typename E::Proj y0 = QADD(ev, od, role), y1 = QADD(ev, T::neg(od), role);
+      od = EcQuadAdd<C>::add(od, tg[(size_t)(j - 1) * hr], role);
+    const typename E::Proj y0 = EcQuadAdd<C>::add(ev, od, role), y1 = EcQuadAdd<C>::add(ev, T::neg(od), role);
     if (live && role == 0) {
       next[base + (uint64_t)u * L] = y0;
       next[base + (uint64_t)(u + hr) * L] = y1;

@@ -39,28 +39,15 @@ namespace icicle_hip {
     0x000000008000808bull, 0x800000000000008bull, 0x8000000000008089ull, 0x8000000000008003ull, 0x8000000000008002ull, 0x8000000000000080ull,
     0x000000000000800aull, 0x800000008000000aull, 0x8000000080008081ull, 0x8000000000008080ull, 0x0000000080000001ull, 0x8000000080008008ull};
 
-  // rotate left by a constant. Default: the compiler's 64-bit shift pair; -DICICLE_HIP_KECCAK_ALIGNBIT: two v_alignbit_b32 on the halves
-  // (profiles/hash_merkle_notes.md has the instruction counts of both).
+  // rotate left by a constant: the compiler's 64-bit shift pair. Two v_alignbit_b32 on the halves were tried and retired
+  // (profiles/hash_merkle_notes.md has the instruction counts of both, profiles/retired_variants.md the commit that still builds them).
   template <int N>
   __device__ __forceinline__ uint64_t rotl64(uint64_t v)
   {
     if constexpr (N == 0) {
       return v;
     } else {
-#ifdef ICICLE_HIP_KECCAK_ALIGNBIT
-      const uint32_t lo = (uint32_t)v, hi = (uint32_t)(v >> 32);
-      if constexpr (N == 32) {
-        return ((uint64_t)lo << 32) | hi;
-      } else if constexpr (N < 32) {
-        const uint32_t nh = __builtin_amdgcn_alignbit(hi, lo, 32 - N), nl = __builtin_amdgcn_alignbit(lo, hi, 32 - N);
-        return ((uint64_t)nh << 32) | nl;
-      } else {
-        const uint32_t nh = __builtin_amdgcn_alignbit(lo, hi, 64 - N), nl = __builtin_amdgcn_alignbit(hi, lo, 64 - N);
-        return ((uint64_t)nh << 32) | nl;
-      }
-#else
       return (v << N) | (v >> (64 - N));
-#endif
     }
   }
 

@@ -827,12 +827,7 @@ namespace icicle_hip {
       uint32_t w[PW];
 #pragma unroll
       for (int q = 0; q < PW / 4; q++) {
-#ifdef MSM_NT_GATHER // A/B: keep the once-used base points out of the L2 (tools/ab_lib.sh)
-        typedef uint32_t u32x4_t __attribute__((ext_vector_type(4)));
-        const u32x4_t v = __builtin_nontemporal_load(reinterpret_cast<const u32x4_t*>(p) + q);
-#else
         const uint4 v = p[q];
-#endif
         w[4 * q] = v.x;
         w[4 * q + 1] = v.y;
         w[4 * q + 2] = v.z;

@@ -29,9 +29,7 @@ namespace icicle_hip {
     return NG;
   }
 
-  #ifndef MSM_DEFAULT_GROUPS
-  #define MSM_DEFAULT_GROUPS 1 // window groups of the pipelined schedule (msm_run_single); ICICLE_HIP_MSM_GROUPS overrides
-  #endif
+  constexpr int MSM_DEFAULT_GROUPS = 1; // window groups of the pipelined schedule (msm_run_single); ICICLE_HIP_MSM_GROUPS overrides
   struct MsmPlan {
     int bits;    // scalar bits considered
     int c;       // window bits (of the widest windows)

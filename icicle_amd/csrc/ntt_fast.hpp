@@ -231,16 +231,6 @@ namespace icicle_hip {
       const uint64_t jnext = ((uint64_t)ct * TC + cB) / pd.cprime;
       const bool skip_wa = pd.pidx == 0 || agrp > 1; // (agrp > 1: w^(jnext a) differs per launch row, applied to the operands instead)
       const uint32_t wa = skip_wa ? 0u : tw_load(jnext * a * pd.tw_stride);
-#if defined(NTT_WIP_LOADS) // (rounds 1-3, kept for A/B builds: every factor loaded from the table)
-#pragma unroll
-      for (int m = 0; m < E; m++) {
-        const uint32_t k = (NR == 1) ? (uint32_t)m : baseT + ((uint32_t)m << QT);
-        if (pd.pidx == 0)
-          wip[m] = tw_load(jnext * k * pd.tw_stride);
-        else
-          wip[m] = S::mul(wa, tw_load(jnext * pd.n0 * k * pd.tw_stride));
-      }
-#else
       // The thread's E rows k = baseT + (m << QT) form an arithmetic progression, so its factors form a geometric one:
       // two table reads and E - 1 products instead of E reads. In pass 1 those reads are 4-byte gathers, a 64-byte sector each
       // and 8192 of them per block: with few batch rows per block to spread them over (small batches, the lane-native
@@ -253,7 +243,6 @@ namespace icicle_hip {
 #pragma unroll
       for (int m = 1; m < E; m++)
         wip[m] = S::mul(wip[m - 1], step);
-#endif
     }
 
     // ---- coset factors, once per block (they do not depend on the batch row) ------------------------

@@ -40,9 +40,9 @@ namespace {
     case 4:
     case 5:
     case 6: return math_cases::ec_case<C>(op, pts, n, aux, out);
-    case 7: { // the ECNTT butterflies' scalar multiplication (ecntt.hip mul_words_quad, one lane's arithmetic): aux[0..7] * pts[0] by the GLV
-              // split, 33 joint four-bit windows, four lazily reduced doublings per window with Y brought back below 4p for the complete addition
-      if constexpr (C::EXT_DEGREE == 1) {
+    case 7: { // the ECNTT's scalar multiplication (ecntt.hip mul_words_quad, one lane's arithmetic): aux[0..7] * pts[0] by the GLV split, 27 joint
+              // signed five-bit windows over the multiples 1..16, five complete projective doublings per window (ec_dbl_quad.hpp) and complete additions
+      if constexpr (has_small_b3<C>::value) {
         using Proj = typename E::Proj;
         const Proj p = E::words_are_zero(pts) ? E::proj_identity() : E::to_proj(load(pts));
         Proj tab[16];
@@ -52,69 +52,29 @@ namespace {
         const typename F::fe beta = F::from_const(C::GLV_BETA);
         Proj r = E::proj_identity();
         bool started = false;
-        if constexpr (C::B3_SMALL != 0) { // signed five-bit windows over the multiples 1..16, projective doublings (the device's WIN5 path)
-          Proj e = p;
-          for (int i = 0; i < 16; i++) {
-            tab[i] = e;
-            if (i < 15) e = (i == 0) ? EcDblSmallB<C>::dbl(p) : E::add(e, p);
-          }
-          uint32_t pk1[7], pk2[7];
-          glv_recode5(k1, pk1);
-          glv_recode5(k2, pk2);
-          for (int d = 26; d >= 0; d--) {
-            const uint32_t b1 = (pk1[d >> 2] >> ((d & 3) * 8)) & 0xFFu, b2 = (pk2[d >> 2] >> ((d & 3) * 8)) & 0xFFu;
-            if (started)
-              for (int q = 0; q < 5; q++)
-                r = EcDblSmallB<C>::dbl(r);
-            if (b1 & 31u) {
-              Proj t = tab[(b1 & 31u) - 1];
-              if (n1 != ((b1 & 0x80u) != 0)) t.y = F::template neg<4>(F::below4(t.y));
-              r = started ? E::add(r, t) : t;
-              started = true;
-            }
-            if (b2 & 31u) {
-              Proj t = tab[(b2 & 31u) - 1];
-              t.x = F::mul(t.x, beta);
-              if (n2 != ((b2 & 0x80u) != 0)) t.y = F::template neg<4>(F::below4(t.y));
-              r = started ? E::add(r, t) : t;
-              started = true;
-            }
-          }
-          Proj nr = r;
-          nr.y = F::template neg<4>(r.y);
-          E::store_proj_canonical(out, E::add(E::add(r, nr), r));
-          return 0;
-        }
-        Proj e = E::proj_identity();
+        Proj e = p;
         for (int i = 0; i < 16; i++) {
           tab[i] = e;
-          e = (i == 0) ? p : ((i == 1) ? E::dbl(p) : E::add(e, p));
+          if (i < 15) e = (i == 0) ? EcDblSmallB<C>::dbl(p) : E::add(e, p);
         }
-        for (int d = 32; d >= 0; d--) {
-          const uint32_t d1 = (k1[d >> 3] >> ((d & 7) * 4)) & 15u, d2 = (k2[d >> 3] >> ((d & 7) * 4)) & 15u;
-          if (started) {
-            if constexpr (C::B3_SMALL != 0) {
-              for (int q = 0; q < 4; q++)
-                r = EcDblSmallB<C>::dbl(r); // ec_dbl_quad.hpp: the quad form's operand flow on one lane
-            } else {
-              typename E::Jac j = E::to_jac(r);
-              for (int q = 0; q < 4; q++)
-                j = E::dbl_jac_lazy(j);
-              F::template cond_sub<16>(j.y);
-              j.y = F::below4(j.y);
-              r = E::from_jac(j);
-            }
-          }
-          if (d1) {
-            Proj t = tab[d1];
-            if (n1) t.y = F::template neg<4>(F::below4(t.y));
+        uint32_t pk1[7], pk2[7];
+        glv_recode5(k1, pk1);
+        glv_recode5(k2, pk2);
+        for (int d = 26; d >= 0; d--) {
+          const uint32_t b1 = (pk1[d >> 2] >> ((d & 3) * 8)) & 0xFFu, b2 = (pk2[d >> 2] >> ((d & 3) * 8)) & 0xFFu;
+          if (started)
+            for (int q = 0; q < 5; q++)
+              r = EcDblSmallB<C>::dbl(r); // the quad form's operand flow on one lane
+          if (b1 & 31u) {
+            Proj t = tab[(b1 & 31u) - 1];
+            if (n1 != ((b1 & 0x80u) != 0)) t.y = F::template neg<4>(F::below4(t.y));
             r = started ? E::add(r, t) : t;
             started = true;
           }
-          if (d2) {
-            Proj t = tab[d2];
+          if (b2 & 31u) {
+            Proj t = tab[(b2 & 31u) - 1];
             t.x = F::mul(t.x, beta);
-            if (n2) t.y = F::template neg<4>(F::below4(t.y));
+            if (n2 != ((b2 & 0x80u) != 0)) t.y = F::template neg<4>(F::below4(t.y));
             r = started ? E::add(r, t) : t;
             started = true;
           }

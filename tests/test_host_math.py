@@ -119,7 +119,7 @@ def test_ec_ops(lib, ci, c):
         assert run(5, [base[2]], [k])[0] == pyref.ec_mul(c, 1 << k, base[2])
     got, raw = run(5, [pyref.INF], [9])
     assert got == pyref.INF and raw[1] != 0
-    if ci in (0, 1, 4):  # the ECNTT butterflies' scalar multiplication: GLV split + joint windows + lazily reduced doublings (one lane's arithmetic of ecntt.hip)
+    if ci in (0, 1, 4):  # the ECNTT butterflies' scalar multiplication: GLV split + joint signed five-bit windows + complete projective doublings (one lane's arithmetic of ecntt.hip)
         rnd2 = random.Random(900 + ci)
         ks = [0, 1, 2, 15, 16, 17, c.r - 1, c.r - 2, c.r // 2, (1 << 128) - 1, 1 << 128, (1 << 200) + 12345] + [rnd2.randrange(c.r) for _ in range(25)]
         for k in ks:
