@@ -187,7 +187,24 @@ class MerkleTreeConfig(ctypes.Structure):
         return cls(None, False, False, False, 0, None)
 
 
+class PowConfig(ctypes.Structure):
+    """icicle::PowConfig (include/icicle/hash/pow.h:16-25), 32 bytes."""
+    _fields_ = [
+        ("stream", ctypes.c_void_p),
+        ("is_challenge_on_device", ctypes.c_bool),
+        ("padding_size", ctypes.c_uint32),
+        ("is_async", ctypes.c_bool),
+        ("ext", ctypes.c_void_p),
+    ]
+
+    @classmethod
+    def default(cls):
+        # default_pow_config() (pow.h:32)
+        return cls(None, False, 24, False, None)
+
+
 assert ctypes.sizeof(Device) == 68 and Device.id.offset == 64
+assert ctypes.sizeof(PowConfig) == 32 and [getattr(PowConfig, f).offset for f, _ in PowConfig._fields_] == [0, 8, 12, 16, 24]
 assert ctypes.sizeof(HashConfig) == 32 and HashConfig.are_inputs_on_device.offset == 16 and HashConfig.ext.offset == 24
 assert ctypes.sizeof(MerkleTreeConfig) == 24 and MerkleTreeConfig.padding_policy.offset == 12 and MerkleTreeConfig.ext.offset == 16
 assert ctypes.sizeof(MSMConfig) == 40 and MSMConfig.ext.offset == 32
@@ -251,6 +268,7 @@ API_SYMBOLS = (
     + [f"{pre}{c}_g2_{k}_convert_montgomery" for pre in ("", "icicle_hip_") for c in G2_CURVES for k in ("affine", "projective")]
     + ["icicle_hasher_hash", "icicle_hasher_delete", "icicle_merkle_tree_delete", "icicle_merkle_tree_build", "icicle_merkle_tree_get_proof",
        "icicle_merkle_tree_verify", "icicle_merkle_proof_delete", "icicle_merkle_proof_is_pruned"]
+    + ["proof_of_work", "proof_of_work_verify"]
 )
 # hash / Merkle functions that return a handle, a size or a byte pointer (tests/test_abi.py's header scan sees only the return types
 # of the lists above; tests/test_hash_cpu.py checks these against the header with a scan of its own): name -> restype
@@ -384,6 +402,10 @@ lib.icicle_merkle_proof_is_pruned.restype = ctypes.c_bool
 lib.icicle_merkle_proof_get_path.argtypes = [ctypes.c_void_p, _size_p]
 lib.icicle_merkle_proof_get_leaf.argtypes = [ctypes.c_void_p, _size_p, ctypes.POINTER(ctypes.c_uint64)]
 lib.icicle_merkle_proof_get_root.argtypes = [ctypes.c_void_p, _size_p]
+_u64_p = ctypes.POINTER(ctypes.c_uint64)
+lib.proof_of_work.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint32, ctypes.c_uint8, ctypes.POINTER(PowConfig), ctypes.POINTER(ctypes.c_bool), _u64_p, _u64_p]
+lib.proof_of_work_verify.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint32, ctypes.c_uint8, ctypes.POINTER(PowConfig), ctypes.c_uint64,
+                                     ctypes.POINTER(ctypes.c_bool), _u64_p]
 
 
 def multi_stats(reset=False):

@@ -1,8 +1,9 @@
-// Keccak / SHA3 / Blake2s / Blake3 batch hashing and Merkle trees on the device. The Blake compression and absorb code is blake.hpp,
-// the three message readers hash_readers.hpp (both also compile for the host); the kernels over them are below.
+// Keccak / SHA3 / Blake2s / Blake3 batch hashing, Merkle trees and the proof-of-work search on the device. The Blake compression and
+// absorb code is blake.hpp, the four message readers hash_readers.hpp (both also compile for the host); the kernels over them are below.
 //
 // C ABI of the reference: icicle/src/hash/hash_c_api.cpp (icicle_create_keccak_256 .. icicle_create_blake3, icicle_hasher_hash), src/hash/merkle_c_api.cpp
-// (icicle_merkle_tree_*, icicle_merkle_proof_*); configs include/icicle/hash/hash_config.h, include/icicle/merkle/merkle_tree_config.h;
+// (icicle_merkle_tree_*, icicle_merkle_proof_*), include/icicle/hash/pow.h (proof_of_work, proof_of_work_verify); configs
+// include/icicle/hash/hash_config.h, include/icicle/merkle/merkle_tree_config.h, pow.h;
 // tree / proof semantics backend/cpu/src/hash/cpu_merkle_tree.cpp:143-211,546-573 and include/icicle/merkle/merkle_tree.h:148-203.
 //
 // The permutation is written from FIPS 202:
@@ -78,7 +79,7 @@ namespace icicle_hip {
     }
   }
 
-  // where a lane's message bytes come from: ReadAligned, ReadBytes, ReadPadded (hash_readers.hpp)
+  // where a lane's message bytes come from: ReadAligned, ReadBytes, ReadPadded, ReadPow (hash_readers.hpp)
 
   // sponge over one message of `len` bytes: absorb whole blocks, then the last block with the domain suffix at byte len % rate and
   // 0x80 at the block's last byte (pad10*1). The digest is a[0 .. OUT_WORDS).
@@ -337,6 +338,54 @@ namespace icicle_hip {
     }
   }
 
+  // ---- proof of work ------------------------------------------------------------------------------------------------------------
+  // backend/cpu/src/hash/cpu_pow.cpp: the message of nonce n is challenge | n (8 bytes, little-endian) | padding_size zero bytes, its
+  // candidate the digest's first 8 bytes as a little-endian word; n solves when the candidate is below 2^(64 - solution_bits). The
+  // messages are never stored: a lane absorbs its nonce's message through ReadPow, so the search touches memory for the challenge
+  // (the same words for every lane) and for one result word.
+  template <int KIND, int RATE_WORDS>
+  __device__ __forceinline__ uint64_t pow_candidate(const ReadPow& rd, uint64_t len, uint32_t suffix)
+  {
+    if constexpr (KIND == HASH_KECCAK) {
+      uint64_t a[25];
+      keccak_msg<RATE_WORDS>(rd, len, suffix, a);
+      return a[0];
+    } else {
+      uint32_t h[8];
+      blake_msg<KIND>(rd, len, h);
+      return h[0] | (uint64_t)h[1] << 32;
+    }
+  }
+
+  // Nonces [base, base + span), one lane per nonce, grid-stride, so that the grid walks the span in ascending sweeps. *best is the
+  // smallest solving nonce seen so far (~0: none; the host never searches that nonce): a solving lane lowers it with a 64-bit
+  // atomicMin, so the span's result is its smallest solution whatever order the lanes ran in. A lane skips nonces above the best
+  // it last read, and leaves once the first nonce of its block's sweep is above it -- every sweep after that is too. The value
+  // read may be stale, which costs hashes and never a result. Nobody waits: a lane reads *best once per nonce of its own and
+  // goes on; the read for the next nonce is issued in front of the hash so that it is in flight beside it.
+  template <int KIND, int RATE_WORDS>
+  __global__ __launch_bounds__(256) void k_pow_search(const uint64_t* __restrict__ challenge, uint32_t size, uint64_t len, uint32_t suffix, uint64_t base, uint64_t span,
+                                                       uint64_t threshold, unsigned long long* best)
+  {
+    const uint64_t step = (uint64_t)gridDim.x * blockDim.x;
+    uint64_t cur = __hip_atomic_load(best, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < span; i += step) {
+      const uint64_t nonce = base + i; // base + span <= 2^64 - 1024: no wrap
+      if (nonce - threadIdx.x > cur) break;
+      const bool skip = nonce > cur;
+      cur = __hip_atomic_load(best, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      if (skip) continue;
+      if (pow_candidate<KIND, RATE_WORDS>(ReadPow{challenge, size, nonce}, len, suffix) < threshold) atomicMin(best, (unsigned long long)nonce);
+    }
+  }
+
+  // the candidate of one nonce: proof_of_work_verify, and the solver's mined_hash (no two lanes of the search write it)
+  template <int KIND, int RATE_WORDS>
+  __global__ __launch_bounds__(64) void k_pow_eval(const uint64_t* __restrict__ challenge, uint32_t size, uint64_t len, uint32_t suffix, uint64_t nonce, uint64_t* out)
+  {
+    if (blockIdx.x == 0 && threadIdx.x == 0) *out = pow_candidate<KIND, RATE_WORDS>(ReadPow{challenge, size, nonce}, len, suffix);
+  }
+
   // ---- host side ----------------------------------------------------------------------------------------------------------------
   struct Hasher {
     int kind;       // HASH_KECCAK, HASH_BLAKE2S, HASH_BLAKE3
@@ -481,6 +530,157 @@ namespace icicle_hip {
     } else if (!cfg->is_async) {
       HIP_TRY(hipStreamSynchronize(st), ICICLE_SYNCHRONIZATION_FAILED);
     }
+    return ICICLE_SUCCESS;
+  }
+
+  // ---- proof of work, host side --------------------------------------------------------------------------------------------------
+  using PowSearchFn = void (*)(const uint64_t*, uint32_t, uint64_t, uint32_t, uint64_t, uint64_t, uint64_t, unsigned long long*);
+  using PowEvalFn = void (*)(const uint64_t*, uint32_t, uint64_t, uint32_t, uint64_t, uint64_t*);
+  static PowSearchFn pow_search_kernel(const Hasher& h)
+  {
+    if (h.kind == HASH_BLAKE2S) return k_pow_search<HASH_BLAKE2S, 0>;
+    if (h.kind == HASH_BLAKE3) return k_pow_search<HASH_BLAKE3, 0>;
+    return h.rate_words == 17 ? k_pow_search<HASH_KECCAK, 17> : k_pow_search<HASH_KECCAK, 9>;
+  }
+  static PowEvalFn pow_eval_kernel(const Hasher& h)
+  {
+    if (h.kind == HASH_BLAKE2S) return k_pow_eval<HASH_BLAKE2S, 0>;
+    if (h.kind == HASH_BLAKE3) return k_pow_eval<HASH_BLAKE3, 0>;
+    return h.rate_words == 17 ? k_pow_eval<HASH_KECCAK, 17> : k_pow_eval<HASH_KECCAK, 9>;
+  }
+
+  // The reference's loop hashes 1024 nonces per round and stops in front of the round that would pass 2^64: the nonces it ever
+  // tries are [0, 2^64 - 1024). The same bound here keeps ~0 free as the "none yet" value of the result word.
+  constexpr uint64_t POW_NONCE_END = 0ull - 1024;
+  // Default nonces per launch for a message of one hash block, about half a millisecond of hashing: 2^22 for the Keccak sponges
+  // (0.76 ms at 5.5 G hashes/s), 2^24 for Blake2s and Blake3 (0.49 and 0.35 ms). Measured against 2^20 .. 2^32
+  // (profiles/hash_merkle_notes.md): a launch, the copy of the result word and the synchronisation cost some 20 us per span, which
+  // argues for long spans, but the waves of a grid do not advance in step, so a solution early in a long span is reported late --
+  // at 2^28 a 25-bit Keccak-256 solve took five times as long as at 2^22. Halved per doubling of the message's blocks.
+  constexpr int POW_SPAN_LOG2_KECCAK = 22, POW_SPAN_LOG2_BLAKE = 24, POW_SPAN_LOG2_MIN = 16, POW_SPAN_LOG2_MAX = 32, POW_SPANS_PER_LOOK = 16;
+
+  struct PowPlan {
+    uint64_t len, threshold, start, end; // nonces [start, end)
+    int span_log2;
+  };
+
+  // everything that can be refused without a device
+  static icicle_error_t pow_plan(const Hasher* h, const uint8_t* challenge, uint32_t challenge_size, uint8_t solution_bits, const icicle_pow_config_t* cfg,
+                                 PowPlan* p)
+  {
+    if (!h || !cfg || (!challenge && challenge_size)) return ICICLE_INVALID_POINTER;
+    if (solution_bits < 1 || solution_bits > 60) return ICICLE_INVALID_ARGUMENT;
+    p->len = (uint64_t)challenge_size + 8 + cfg->padding_size;
+    if (h->kind == HASH_BLAKE3 && p->len > BLAKE3_CHUNK) return ICICLE_INVALID_ARGUMENT; // one chunk: no tree inside a lane
+    p->threshold = 1ull << (64 - solution_bits);
+    const uint64_t block = h->kind == HASH_KECCAK ? 8ull * h->rate_words : 64, blocks = h->kind == HASH_KECCAK ? p->len / block + 1 : (p->len + block - 1) / block;
+    int span = h->kind == HASH_KECCAK ? POW_SPAN_LOG2_KECCAK : POW_SPAN_LOG2_BLAKE;
+    for (uint64_t b = 1; b < blocks && span > POW_SPAN_LOG2_MIN; b *= 2)
+      span--;
+    int lo = 0, hi = 0, count = 64;
+    if (cfg->ext) {
+      const ConfigExt* e = reinterpret_cast<const ConfigExt*>(cfg->ext);
+      span = e->get_int("hip_pow_span_log2", span);
+      lo = e->get_int("hip_pow_start_lo", 0), hi = e->get_int("hip_pow_start_hi", 0);
+      count = e->get_int("hip_pow_count_log2", 64);
+    }
+    if (span < 0 || span > POW_SPAN_LOG2_MAX || count < 0 || count > 64) return ICICLE_INVALID_ARGUMENT;
+    p->span_log2 = span;
+    p->start = (uint64_t)(uint32_t)hi << 32 | (uint32_t)lo;
+    p->end = POW_NONCE_END;
+    if (count < 64 && p->start + (1ull << count) >= p->start) p->end = std::min<uint64_t>(POW_NONCE_END, p->start + (1ull << count));
+    return ICICLE_SUCCESS;
+  }
+
+  // device words of one call: [0] the result word of the search, [1] the candidate of k_pow_eval, [2 ..] the challenge as ReadPow
+  // reads it. A challenge in device memory is copied there as well: it may lie at any address, and the copy is once per call.
+  static icicle_error_t pow_stage_device(TempBuf& buf, const uint8_t* challenge, uint32_t size, bool on_device, std::vector<uint64_t>& host_words, hipStream_t st)
+  {
+    const uint64_t words = pow_staging_words(size);
+    HIP_TRY(buf.alloc(8 * (2 + words), st), ICICLE_ALLOCATION_FAILED);
+    uint64_t* d = buf.as<uint64_t>() + 2;
+    if (on_device) {
+      HIP_TRY(hipMemsetAsync(d, 0, 8 * words, st), ICICLE_COPY_FAILED);
+      if (size) HIP_TRY(hipMemcpyAsync(d, challenge, size, hipMemcpyDeviceToDevice, st), ICICLE_COPY_FAILED);
+    } else {
+      host_words.resize(words);
+      pow_stage(challenge, size, host_words.data());
+      HIP_TRY(hipMemcpyAsync(d, host_words.data(), 8 * words, hipMemcpyHostToDevice, st), ICICLE_COPY_FAILED);
+    }
+    return ICICLE_SUCCESS;
+  }
+
+  static icicle_error_t pow_eval(const Hasher& h, const TempBuf& buf, uint32_t size, uint64_t len, uint64_t nonce, uint64_t* mined, hipStream_t st)
+  {
+    uint64_t* d = buf.as<uint64_t>();
+    pow_eval_kernel(h)<<<1, 64, 0, st>>>(d + 2, size, len, h.suffix, nonce, d + 1);
+    LAUNCH_CHECK("k_pow_eval", st);
+    HIP_TRY(hipMemcpyAsync(mined, d + 1, 8, hipMemcpyDeviceToHost, st), ICICLE_COPY_FAILED);
+    HIP_TRY(hipStreamSynchronize(st), ICICLE_SYNCHRONIZATION_FAILED);
+    return ICICLE_SUCCESS;
+  }
+
+  // Spans in ascending order, one launch each, and a look at the result word after every few of them: the first look that finds a
+  // nonce finds the smallest solution of the whole search, since atomicMin keeps the smallest of all spans launched so far. The outputs are host
+  // scalars, so the call returns with config->stream drained, whatever is_async says.
+  static icicle_error_t pow_solve(const Hasher* h, const uint8_t* challenge, uint32_t challenge_size, uint8_t solution_bits, const icicle_pow_config_t* cfg, bool* found,
+                                  uint64_t* nonce, uint64_t* mined_hash)
+  {
+    PowPlan p;
+    ICICLE_TRY(pow_plan(h, challenge, challenge_size, solution_bits, cfg, &p));
+    if (!found || !nonce || !mined_hash) return ICICLE_INVALID_POINTER;
+    ICICLE_TRY(bind_current_device());
+    hipStream_t st = (hipStream_t)cfg->stream;
+    TempBuf buf;
+    std::vector<uint64_t> host_words;
+    ICICLE_TRY(pow_stage_device(buf, challenge, challenge_size, cfg->is_challenge_on_device, host_words, st));
+    uint64_t* d = buf.as<uint64_t>();
+    HIP_TRY(hipMemsetAsync(d, 0xFF, 8, st), ICICLE_COPY_FAILED);
+    // as many blocks as the device holds at once, so that a sweep of the grid is one stretch of consecutive nonces in flight
+    const PowSearchFn kernel = pow_search_kernel(*h);
+    int dev = 0, cus = 0, per_cu = 0;
+    HIP_TRY(hipGetDevice(&dev), ICICLE_INVALID_DEVICE);
+    HIP_TRY(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev), ICICLE_INVALID_DEVICE);
+    HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, reinterpret_cast<const void*>(kernel), 256, 0), ICICLE_INVALID_DEVICE);
+    const uint64_t resident = (uint64_t)std::max(cus, 1) * std::max(per_cu, 1), span = 1ull << p.span_log2;
+    // Spans launched between two looks at the result word: 1, 2, 4, .. POW_SPANS_PER_LOOK. The spans of a group run one after the
+    // other in stream order; those behind a solution cost a launch each and no hashing, since their blocks leave at their first nonce.
+    uint64_t best = ~0ull, base = p.start;
+    for (int look = 0; base < p.end && best == ~0ull; look++) {
+      for (int g = std::min(1 << std::min(look, 30), POW_SPANS_PER_LOOK); g > 0 && base < p.end; g--) {
+        const uint64_t n = std::min<uint64_t>(span, p.end - base);
+        kernel<<<(unsigned)std::min<uint64_t>((n + 255) / 256, resident), 256, 0, st>>>(d + 2, challenge_size, p.len, h->suffix, base, n, p.threshold,
+                                                                                        reinterpret_cast<unsigned long long*>(d));
+        LAUNCH_CHECK("k_pow_search", st);
+        base += n;
+      }
+      HIP_TRY(hipMemcpyAsync(&best, d, 8, hipMemcpyDeviceToHost, st), ICICLE_COPY_FAILED);
+      HIP_TRY(hipStreamSynchronize(st), ICICLE_SYNCHRONIZATION_FAILED);
+    }
+    if (best == ~0ull) {
+      *found = false; // nonce and mined_hash stay as they were
+      return ICICLE_SUCCESS;
+    }
+    uint64_t mined = 0;
+    ICICLE_TRY(pow_eval(*h, buf, challenge_size, p.len, best, &mined, st));
+    *found = true, *nonce = best, *mined_hash = mined;
+    return ICICLE_SUCCESS;
+  }
+
+  static icicle_error_t pow_verify(const Hasher* h, const uint8_t* challenge, uint32_t challenge_size, uint8_t solution_bits, const icicle_pow_config_t* cfg,
+                                   uint64_t nonce, bool* is_correct, uint64_t* mined_hash)
+  {
+    PowPlan p;
+    ICICLE_TRY(pow_plan(h, challenge, challenge_size, solution_bits, cfg, &p));
+    if (!is_correct || !mined_hash) return ICICLE_INVALID_POINTER;
+    ICICLE_TRY(bind_current_device());
+    hipStream_t st = (hipStream_t)cfg->stream;
+    TempBuf buf;
+    std::vector<uint64_t> host_words;
+    ICICLE_TRY(pow_stage_device(buf, challenge, challenge_size, cfg->is_challenge_on_device, host_words, st));
+    uint64_t mined = 0;
+    ICICLE_TRY(pow_eval(*h, buf, challenge_size, p.len, nonce, &mined, st));
+    *mined_hash = mined, *is_correct = mined < p.threshold;
     return ICICLE_SUCCESS;
   }
 
@@ -792,6 +992,9 @@ static_assert(sizeof(icicle_merkle_tree_config_t) == 24 && offsetof(icicle_merkl
                 offsetof(icicle_merkle_tree_config_t, is_tree_on_device) == 9 && offsetof(icicle_merkle_tree_config_t, is_async) == 10 &&
                 offsetof(icicle_merkle_tree_config_t, padding_policy) == 12 && offsetof(icicle_merkle_tree_config_t, ext) == 16,
               "MerkleTreeConfig layout (include/icicle/merkle/merkle_tree_config.h)");
+static_assert(sizeof(icicle_pow_config_t) == 32 && offsetof(icicle_pow_config_t, is_challenge_on_device) == 8 && offsetof(icicle_pow_config_t, padding_size) == 12 &&
+                offsetof(icicle_pow_config_t, is_async) == 16 && offsetof(icicle_pow_config_t, ext) == 24,
+              "PowConfig layout (include/icicle/hash/pow.h)");
 
 #define HASH_GUARDED(expr, on_throw)                                                                                   \
   try {                                                                                                                \
@@ -821,6 +1024,18 @@ icicle_error_t icicle_hasher_delete(icicle_hasher_handle_t h)
   if (!h) return ICICLE_INVALID_POINTER;
   delete (Hasher*)h;
   return ICICLE_SUCCESS;
+}
+
+icicle_error_t proof_of_work(icicle_hasher_handle_t hasher, const uint8_t* challenge, uint32_t challenge_size, uint8_t solution_bits, const icicle_pow_config_t* config,
+                             bool* found, uint64_t* nonce, uint64_t* mined_hash)
+{
+  HASH_GUARDED(pow_solve((const Hasher*)hasher, challenge, challenge_size, solution_bits, config, found, nonce, mined_hash), ICICLE_ALLOCATION_FAILED)
+}
+
+icicle_error_t proof_of_work_verify(icicle_hasher_handle_t hasher, const uint8_t* challenge, uint32_t challenge_size, uint8_t solution_bits,
+                                    const icicle_pow_config_t* config, uint64_t nonce, bool* is_correct, uint64_t* mined_hash)
+{
+  HASH_GUARDED(pow_verify((const Hasher*)hasher, challenge, challenge_size, solution_bits, config, nonce, is_correct, mined_hash), ICICLE_ALLOCATION_FAILED)
 }
 
 icicle_merkle_tree_handle_t icicle_merkle_tree_create(const icicle_hasher_handle_t* layer_hashes, size_t layer_hashes_len, uint64_t leaf_element_size,

@@ -300,7 +300,8 @@ ICICLE_HIP_DECLARE_TRANSPOSE(stark252, matrix_transpose)
  * (HashConfig, 32 bytes), include/icicle/merkle/merkle_tree_config.h:11-37 (PaddingPolicy, MerkleTreeConfig, 24 bytes).
  * Keccak-f[1600] sponges: rate 136 bytes for the 256-bit digests, 72 bytes for the 512-bit ones; Keccak pads 0x01 .. 0x80,
  * SHA3 0x06 .. 0x80. Creating and deleting handles needs no GPU; hashing, build, get_proof and verify run on the device and
- * fail without one. Blake2s, Blake3, Poseidon, Poseidon2 and proof serialisation are not built.
+ * fail without one. Blake2s-256 and Blake3 hash through the same entry points; the proof-of-work solver and verifier over all six
+ * hashers follow the Merkle functions below. Poseidon, Poseidon2 and proof serialisation are not built.
  * ====================================================================================== */
 typedef struct {
   icicleStreamHandle stream;      /* 0  */
@@ -370,6 +371,36 @@ bool icicle_merkle_proof_is_pruned(icicle_merkle_proof_handle_t proof);         
 const uint8_t* icicle_merkle_proof_get_path(icicle_merkle_proof_handle_t proof, size_t* out_size); /* :47 */
 const uint8_t* icicle_merkle_proof_get_leaf(icicle_merkle_proof_handle_t proof, size_t* out_size, uint64_t* out_leaf_idx); /* :56 */
 const uint8_t* icicle_merkle_proof_get_root(icicle_merkle_proof_handle_t proof, size_t* out_size); /* :66 */
+
+/* ---- proof of work: include/icicle/hash/pow.h:16-87 (PowConfig, 32 bytes; proof_of_work, proof_of_work_verify), semantics
+ * backend/cpu/src/hash/cpu_pow.cpp. `const Hash&` and the `bool&` / `uint64_t&` results cross the ABI as pointers
+ * (wrappers/rust/icicle-hash/src/pow.rs:28-53). The message of nonce n is challenge[0, challenge_size) | n as 8 little-endian
+ * bytes | padding_size zero bytes; its candidate is the first 8 digest bytes as a little-endian word; n solves when the candidate
+ * is below 2^(64 - solution_bits). ---- */
+typedef struct {
+  icicleStreamHandle stream;      /* 0  */
+  bool is_challenge_on_device;    /* 8  */
+  uint32_t padding_size;          /* 12  default 24: a 32-byte challenge makes a 64-byte message */
+  bool is_async;                  /* 16  accepted and ignored: the results are host scalars, so both calls return with `stream` drained */
+  icicle_config_extension_t* ext; /* 24  all ints, all optional, foreign keys ignored:
+                                         "hip_pow_span_log2"  nonces per kernel launch, 0 .. 32 (default for a message of one hash block: 22 for the
+                                                              Keccak / SHA3 hashers, 24 for Blake2s / Blake3; one less per doubling of
+                                                              its blocks, at least 16)
+                                         "hip_pow_start_lo", "hip_pow_start_hi"  first nonce tried, hi << 32 | (uint32_t)lo (default 0)
+                                         "hip_pow_count_log2" nonces tried from the first one, 0 .. 64 (default 64: all of them) */
+} icicle_pow_config_t;
+
+/* The SMALLEST solving nonce among those tried, counting up from the first, and its candidate: *found = true, *nonce, *mined_hash.
+ * The nonces tried end at 2^64 - 1024, where the reference's loop of 1024-nonce rounds ends. When none solves: *found = false,
+ * *nonce and *mined_hash untouched. hasher: any of the six of icicle_create_*; Blake3 only while challenge_size + 8 + padding_size
+ * <= 1024 (one chunk), INVALID_ARGUMENT beyond. solution_bits outside 1 .. 60, or a key above out of range: INVALID_ARGUMENT. NULL
+ * hasher, config or result pointer, NULL challenge with challenge_size > 0: INVALID_POINTER. Argument errors are returned before the
+ * device is touched. The challenge may lie at any address, on the host or (is_challenge_on_device) on the device. */
+icicle_error_t proof_of_work(icicle_hasher_handle_t hasher, const uint8_t* challenge, uint32_t challenge_size, uint8_t solution_bits, const icicle_pow_config_t* config,
+                             bool* found, uint64_t* nonce, uint64_t* mined_hash); /* pow.h:52 */
+/* One hash: *mined_hash = the candidate of `nonce`, *is_correct = it is below the threshold. Same argument errors. */
+icicle_error_t proof_of_work_verify(icicle_hasher_handle_t hasher, const uint8_t* challenge, uint32_t challenge_size, uint8_t solution_bits,
+                                    const icicle_pow_config_t* config, uint64_t nonce, bool* is_correct, uint64_t* mined_hash); /* pow.h:79 */
 
 /* ---- backend-specific helpers (not part of the reference ABI) ---- */
 const char* icicle_hip_version(void);
