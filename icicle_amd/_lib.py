@@ -203,7 +203,41 @@ class PowConfig(ctypes.Structure):
         return cls(None, False, 24, False, None)
 
 
+class FriConfig(ctypes.Structure):
+    """icicle::FriConfig (include/icicle/fri/fri_config.h:16-25), 56 bytes."""
+    _fields_ = [
+        ("stream", ctypes.c_void_p),
+        ("folding_factor", ctypes.c_size_t),
+        ("stopping_degree", ctypes.c_size_t),
+        ("pow_bits", ctypes.c_size_t),
+        ("nof_queries", ctypes.c_size_t),
+        ("are_inputs_on_device", ctypes.c_bool),
+        ("is_async", ctypes.c_bool),
+        ("ext", ctypes.c_void_p),
+    ]
+
+    @classmethod
+    def default(cls):
+        # default_fri_config() (fri_config.h:35)
+        return cls(None, 2, 0, 16, 100, False, False, None)
+
+
+class FFIFriTranscriptConfig(ctypes.Structure):
+    """FFIFriTranscriptConfig (src/fri/fri_c_api.cpp:13-32), 96 bytes; built by icicle_amd.fri.FriTranscriptConfig."""
+    _fields_ = [
+        ("hasher", ctypes.c_void_p),
+        ("domain_separator_label", ctypes.c_void_p), ("domain_separator_label_len", ctypes.c_size_t),
+        ("round_challenge_label", ctypes.c_void_p), ("round_challenge_label_len", ctypes.c_size_t),
+        ("commit_phase_label", ctypes.c_void_p), ("commit_phase_label_len", ctypes.c_size_t),
+        ("nonce_label", ctypes.c_void_p), ("nonce_label_len", ctypes.c_size_t),
+        ("public_state", ctypes.c_void_p), ("public_state_len", ctypes.c_size_t),
+        ("seed_rng", ctypes.c_void_p),
+    ]
+
+
 assert ctypes.sizeof(Device) == 68 and Device.id.offset == 64
+assert ctypes.sizeof(FriConfig) == 56 and [getattr(FriConfig, f).offset for f, _ in FriConfig._fields_] == [0, 8, 16, 24, 32, 40, 41, 48]
+assert ctypes.sizeof(FFIFriTranscriptConfig) == 96 and FFIFriTranscriptConfig.seed_rng.offset == 88
 assert ctypes.sizeof(PowConfig) == 32 and [getattr(PowConfig, f).offset for f, _ in PowConfig._fields_] == [0, 8, 12, 16, 24]
 assert ctypes.sizeof(HashConfig) == 32 and HashConfig.are_inputs_on_device.offset == 16 and HashConfig.ext.offset == 24
 assert ctypes.sizeof(MerkleTreeConfig) == 24 and MerkleTreeConfig.padding_policy.offset == 12 and MerkleTreeConfig.ext.offset == 16
@@ -236,6 +270,11 @@ NTT_FIELDS = ["babybear", "koalabear"]
 SCALAR_NTT_FIELDS = ["bn254", "bls12_381", "bls12_377", "stark252"]  # NTT over a 256-bit field, 8-word elements
 BIG_VEC_FIELDS = SCALAR_NTT_FIELDS + ["grumpkin"]  # element-wise ops / Montgomery conversion over 8-word scalars
 GOLD = "goldilocks"  # 2-word elements, NTTConfigU64; extension field = 2 components
+# FRI (src/fri/fri_c_api.cpp): the functions that return an error code, per field and again with the prefix <field>_extension
+FRI_PREFIXES = [f"{f}{e}" for f in NTT_FIELDS for e in ("", "_extension")]
+FRI_FUNCTIONS = ["icicle_delete_fri_proof", "fri_proof_get_nof_queries", "fri_proof_get_nof_rounds", "fri_proof_get_round_proofs_for_query",
+                 "fri_proof_get_final_poly_size", "fri_proof_get_final_poly", "fri_proof_get_pow_nonce", "fri_merkle_tree_prove", "fri_merkle_tree_verify",
+                 "hip_fri_fold"]
 API_SYMBOLS = (
     [f"{c}_{s}" for c in CURVES for s in ("msm", "msm_precompute_bases", "hip_generate_affine_points", "hip_projective_sum")]
     + [f"{c}_g2_{s}" for c in G2_CURVES for s in ("msm", "msm_precompute_bases", "hip_generate_affine_points", "hip_projective_sum")]
@@ -269,6 +308,7 @@ API_SYMBOLS = (
     + ["icicle_hasher_hash", "icicle_hasher_delete", "icicle_merkle_tree_delete", "icicle_merkle_tree_build", "icicle_merkle_tree_get_proof",
        "icicle_merkle_tree_verify", "icicle_merkle_proof_delete", "icicle_merkle_proof_is_pruned"]
     + ["proof_of_work", "proof_of_work_verify"]
+    + [f"{p}_{s}" for p in FRI_PREFIXES for s in FRI_FUNCTIONS]
 )
 # hash / Merkle functions that return a handle, a size or a byte pointer (tests/test_abi.py's header scan sees only the return types
 # of the lists above; tests/test_hash_cpu.py checks these against the header with a scan of its own): name -> restype
@@ -284,6 +324,8 @@ _HASH_RESTYPES = {
 HASH_HANDLE_SYMBOLS = list(_HASH_RESTYPES)
 # the Blake factories (hash_c_api.cpp:123, :136), a table of their own: name -> restype
 BLAKE_HANDLE_SYMBOLS = {"icicle_create_blake2s": ctypes.c_void_p, "icicle_create_blake3": ctypes.c_void_p}
+# the two FRI functions that return a proof handle: name -> restype
+FRI_HANDLE_SYMBOLS = {f"{p}_{s}": ctypes.c_void_p for p in FRI_PREFIXES for s in ("icicle_initialize_fri_proof", "icicle_create_with_arguments_fri_proof")}
 
 if not os.path.exists(LIB_PATH):
     raise ImportError(
@@ -406,6 +448,23 @@ _u64_p = ctypes.POINTER(ctypes.c_uint64)
 lib.proof_of_work.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint32, ctypes.c_uint8, ctypes.POINTER(PowConfig), ctypes.POINTER(ctypes.c_bool), _u64_p, _u64_p]
 lib.proof_of_work_verify.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint32, ctypes.c_uint8, ctypes.POINTER(PowConfig), ctypes.c_uint64,
                                      ctypes.POINTER(ctypes.c_bool), _u64_p]
+for _s, _r in FRI_HANDLE_SYMBOLS.items():
+    getattr(lib, _s).restype = _r  # AttributeError if the symbol is missing
+for _p in FRI_PREFIXES:
+    getattr(lib, f"{_p}_icicle_initialize_fri_proof").argtypes = []
+    getattr(lib, f"{_p}_icicle_create_with_arguments_fri_proof").argtypes = [ctypes.c_void_p, ctypes.c_size_t, ctypes.c_size_t, ctypes.c_void_p, ctypes.c_size_t,
+                                                                             ctypes.c_uint64]
+    getattr(lib, f"{_p}_icicle_delete_fri_proof").argtypes = [ctypes.c_void_p]
+    for _s in ("fri_proof_get_nof_queries", "fri_proof_get_nof_rounds", "fri_proof_get_final_poly_size"):
+        getattr(lib, f"{_p}_{_s}").argtypes = [ctypes.c_void_p, _size_p]
+    getattr(lib, f"{_p}_fri_proof_get_round_proofs_for_query").argtypes = [ctypes.c_void_p, ctypes.c_size_t, ctypes.POINTER(ctypes.c_void_p)]
+    getattr(lib, f"{_p}_fri_proof_get_final_poly").argtypes = [ctypes.c_void_p, ctypes.POINTER(ctypes.c_void_p)]
+    getattr(lib, f"{_p}_fri_proof_get_pow_nonce").argtypes = [ctypes.c_void_p, _u64_p]
+    getattr(lib, f"{_p}_fri_merkle_tree_prove").argtypes = [ctypes.POINTER(FriConfig), ctypes.POINTER(FFIFriTranscriptConfig), ctypes.c_void_p, ctypes.c_size_t,
+                                                            ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_void_p]
+    getattr(lib, f"{_p}_fri_merkle_tree_verify").argtypes = [ctypes.POINTER(FriConfig), ctypes.POINTER(FFIFriTranscriptConfig), ctypes.c_void_p, ctypes.c_void_p,
+                                                             ctypes.c_void_p, ctypes.POINTER(ctypes.c_bool)]
+    getattr(lib, f"{_p}_hip_fri_fold").argtypes = [ctypes.c_void_p, ctypes.c_uint64, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_bool, ctypes.c_void_p]
 
 
 def multi_stats(reset=False):

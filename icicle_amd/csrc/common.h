@@ -341,6 +341,13 @@ namespace icicle_hip {
     }
   };
 
+  // ---- what fri.hip reads from ntt.hip and hash.hip ----
+  // the twiddle table of the calling thread's device (device memory, tw[j] = w_max^j in Montgomery form, j < 2^log_max) for
+  // field 0 = babybear, 1 = koalabear; false: no domain initialised. The pointer is handed out without a reference: the caller of
+  // the API keeps the domain alive (no <field>_ntt_release_domain) until the call that read it has returned, as for an NTT
+  bool ntt_domain_table(int field, const uint32_t** tw, int* log_max);
+  uint64_t hasher_default_chunk(icicle_hasher_handle_t h); // the hasher's default input size, 0 = none
+
   // ---- dominant-kernel timing with hipEvents on the launch stream (bench.py roofline figure) ----
   struct KernelTimer {
     static bool enabled();

@@ -398,6 +398,8 @@ namespace icicle_hip {
     bool multi_chunk(uint64_t len) const { return kind == HASH_BLAKE3 && len > BLAKE3_CHUNK; }
   };
 
+  uint64_t hasher_default_chunk(icicle_hasher_handle_t h) { return h ? reinterpret_cast<const Hasher*>(h)->chunk : 0; } // for fri.hip (common.h)
+
   static unsigned grid_for(uint64_t n) { return (unsigned)std::min<uint64_t>((n + 255) / 256, 1u << 22); }
 
   // Levels above the chaining values of n Blake3 messages of k chunks each (cv, 32 n k bytes): ping-pong between cv and a second

@@ -240,6 +240,21 @@ namespace icicle_hip {
     return ICICLE_SUCCESS;
   }
 
+  // The initialised domain's table for the fold of fri.hip (declared in common.h): field 0 = babybear, 1 = koalabear.
+  template <class PR>
+  static bool domain_table(const uint32_t** tw, int* log_max)
+  {
+    std::lock_guard<std::mutex> g(DomainStore<PR>::mtx());
+    auto it = DomainStore<PR>::map().find(current_device_id());
+    if (it == DomainStore<PR>::map().end() || !it->second.tw) return false;
+    *tw = it->second.tw, *log_max = it->second.log_max;
+    return true;
+  }
+  bool ntt_domain_table(int field, const uint32_t** tw, int* log_max)
+  {
+    return field == 0 ? domain_table<babybear_params>(tw, log_max) : domain_table<koalabear_params>(tw, log_max);
+  }
+
   // n == 1 and pure-copy helper with strides
   __global__ void k_copy_strided(const uint32_t* in, uint32_t* out, uint64_t count)
   {

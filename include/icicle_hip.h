@@ -301,7 +301,8 @@ ICICLE_HIP_DECLARE_TRANSPOSE(stark252, matrix_transpose)
  * Keccak-f[1600] sponges: rate 136 bytes for the 256-bit digests, 72 bytes for the 512-bit ones; Keccak pads 0x01 .. 0x80,
  * SHA3 0x06 .. 0x80. Creating and deleting handles needs no GPU; hashing, build, get_proof and verify run on the device and
  * fail without one. Blake2s-256 and Blake3 hash through the same entry points; the proof-of-work solver and verifier over all six
- * hashers follow the Merkle functions below. Poseidon, Poseidon2 and proof serialisation are not built.
+ * hashers follow the Merkle functions below, and FRI over BabyBear / KoalaBear, which composes all of them, follows the proof of work.
+ * Poseidon, Poseidon2 and proof serialisation (Merkle and FRI) are not built.
  * ====================================================================================== */
 typedef struct {
   icicleStreamHandle stream;      /* 0  */
@@ -401,6 +402,82 @@ icicle_error_t proof_of_work(icicle_hasher_handle_t hasher, const uint8_t* chall
 /* One hash: *mined_hash = the candidate of `nonce`, *is_correct = it is below the threshold. Same argument errors. */
 icicle_error_t proof_of_work_verify(icicle_hasher_handle_t hasher, const uint8_t* challenge, uint32_t challenge_size, uint8_t solution_bits,
                                     const icicle_pow_config_t* config, uint64_t nonce, bool* is_correct, uint64_t* mined_hash); /* pow.h:79 */
+
+/* ---- FRI over BabyBear and KoalaBear, scalar (F = S = one word) and quartic extension (F = 4 words, S = the base field):
+ * src/fri/fri_c_api.cpp:76-312 (scalar) and :314-563 (P_extension_), include/icicle/fri/fri_config.h:16-25 (FriConfig, 56 bytes),
+ * fri_c_api.cpp:13-32 (FFIFriTranscriptConfig, 96 bytes); protocol src/fri/fri.cpp, include/icicle/fri/fri_transcript.h,
+ * backend/cpu/include/cpu_fri_backend.h. Every layer of the commit phase lives in device memory: round r builds its tree
+ * (icicle_merkle_tree_build, leaves and tree on the device) over n >> r elements -- leaves hasher with chunk = one element, then
+ * log2(n) - r layers of the compress hasher --, hashes the transcript with icicle_hasher_hash, and folds with the challenge:
+ *   out[i] = (e[i] + e[i+h])/2 + alpha * ((e[i] - e[i+h])/2 * w_n^(-i)),  h = n/2,  w_n^(-i) from the initialised NTT domain.
+ * The last fold's output is the final polynomial; proof_of_work (default config) grinds pow_bits; the query phase opens
+ * q % (n>>r) and its symmetric position (q + (n>>r)/2) % (n>>r) in every round with icicle_merkle_tree_get_proof, not pruned.
+ * Queries come from a hand-written MT19937 seeded with the low 32 bits of the transcript digest (icicle_amd/csrc/fri_plan.h), so a
+ * proof does not depend on the C++ library. A proof stores 2 * nof_queries slots (query, symmetric); get_nof_queries returns that
+ * doubled number. The MerkleProof handles of get_round_proofs_for_query are borrowed from the proof and work with
+ * icicle_merkle_proof_get_*. The three serialisation functions are not built.
+ * INVALID_ARGUMENT, before the device is touched: folding_factor != 2, input_size zero or no power of two, nof_queries == 0 or
+ * > input_size / 2, compress arity (chunk / output size) != 2, and -- left undefined by the reference, whose final polynomial then
+ * stays zero -- stopping_degree + 1 no power of two or zero rounds (stopping_degree + 1 >= input_size). Two more of this backend: a
+ * leaves hasher whose chunk is not one element (4 or 16 bytes; the reference's tree build fails there), and pow_bits > 60
+ * (proof_of_work's range). A domain that is missing or smaller than input_size: INVALID_ARGUMENT. NULL config, transcript, hasher,
+ * seed, input or proof: INVALID_POINTER. The caller keeps the domain alive (no ntt_release_domain) until prove has returned.
+ * `stream` is honoured, is_async accepted; prove returns with the stream drained (the proof is host data), as proof_of_work does.
+ * verify: final-polynomial length, alphas from the proof's roots, proof of work, then per query and round both Merkle proofs
+ * (icicle_merkle_tree_verify), leaf indices, collinearity with w_n^(-1) from the field's own root of unity. The argument errors above
+ * that concern the configuration and the hashers are errors in verify too; everything about the proof itself -- its final polynomial's
+ * length, a number of slots other than 2 * nof_queries, rounds that differ between slots, a size 2^rounds * final size that does not
+ * fit nof_queries, words at or above p -- makes a wrong proof: *valid = false with SUCCESS. Stricter than the reference in one point:
+ * every slot of a round must carry the same root as slot 0, from which the round's challenge is derived (the reference compares each
+ * Merkle proof only with the root that proof itself carries). ---- */
+typedef struct {
+  icicleStreamHandle stream;      /* 0  */
+  size_t folding_factor;          /* 8   only 2 */
+  size_t stopping_degree;         /* 16  the final polynomial has stopping_degree + 1 coefficients */
+  size_t pow_bits;                /* 24  0 = no proof of work (default 16) */
+  size_t nof_queries;             /* 32  (default 100) */
+  bool are_inputs_on_device;      /* 40 */
+  bool is_async;                  /* 41 */
+  icicle_config_extension_t* ext; /* 48 */
+} icicle_fri_config_t;
+typedef struct {
+  icicle_hasher_handle_t hasher;         /* 0  */
+  const uint8_t* domain_separator_label; /* 8  */
+  size_t domain_separator_label_len;     /* 16 */
+  const uint8_t* round_challenge_label;  /* 24 */
+  size_t round_challenge_label_len;      /* 32 */
+  const uint8_t* commit_phase_label;     /* 40 */
+  size_t commit_phase_label_len;         /* 48 */
+  const uint8_t* nonce_label;            /* 56 */
+  size_t nonce_label_len;                /* 64 */
+  const uint8_t* public_state;           /* 72 */
+  size_t public_state_len;               /* 80 */
+  const uint32_t* seed_rng;              /* 88  one element of F, canonical */
+} icicle_fri_transcript_config_t;
+typedef struct icicle_fri_proof* icicle_fri_proof_handle_t;
+#define ICICLE_HIP_DECLARE_FRI(P)                                                                                      \
+  icicle_fri_proof_handle_t P##_icicle_initialize_fri_proof(void);                                                     \
+  icicle_fri_proof_handle_t P##_icicle_create_with_arguments_fri_proof(icicle_merkle_proof_handle_t** query_proofs, size_t nof_queries, size_t nof_rounds, \
+                                                                       const uint32_t* final_poly, size_t final_poly_size, uint64_t pow_nonce); \
+  icicle_error_t P##_icicle_delete_fri_proof(icicle_fri_proof_handle_t proof);                                         \
+  icicle_error_t P##_fri_proof_get_nof_queries(icicle_fri_proof_handle_t proof, size_t* nof_queries);                  \
+  icicle_error_t P##_fri_proof_get_nof_rounds(icicle_fri_proof_handle_t proof, size_t* nof_rounds);                    \
+  icicle_error_t P##_fri_proof_get_round_proofs_for_query(icicle_fri_proof_handle_t proof, size_t query_idx, icicle_merkle_proof_handle_t* proofs); \
+  icicle_error_t P##_fri_proof_get_final_poly_size(icicle_fri_proof_handle_t proof, size_t* result);                   \
+  icicle_error_t P##_fri_proof_get_final_poly(icicle_fri_proof_handle_t proof, uint32_t** final_poly);                 \
+  icicle_error_t P##_fri_proof_get_pow_nonce(icicle_fri_proof_handle_t proof, uint64_t* result);                       \
+  icicle_error_t P##_fri_merkle_tree_prove(const icicle_fri_config_t* fri_config, const icicle_fri_transcript_config_t* transcript_config, const uint32_t* input_data, \
+                                           size_t input_size, icicle_hasher_handle_t merkle_tree_leaves_hash, icicle_hasher_handle_t merkle_tree_compress_hash, \
+                                           uint64_t output_store_min_layer, icicle_fri_proof_handle_t fri_proof);      \
+  icicle_error_t P##_fri_merkle_tree_verify(const icicle_fri_config_t* fri_config, const icicle_fri_transcript_config_t* transcript_config, icicle_fri_proof_handle_t fri_proof, \
+                                            icicle_hasher_handle_t merkle_tree_leaves_hash, icicle_hasher_handle_t merkle_tree_compress_hash, bool* valid); \
+  /* backend-specific: one fold of n = 2^k elements into n / 2 (in, out and alpha on the host or all three on the device);        \
+   * INVALID_ARGUMENT: n no power of two, n < 2, the domain missing or smaller than n */                                         \
+  icicle_error_t P##_hip_fri_fold(const uint32_t* in, uint64_t n, const uint32_t* alpha, uint32_t* out, bool on_device, icicleStreamHandle stream);
+ICICLE_HIP_DECLARE_FRI(babybear)
+ICICLE_HIP_DECLARE_FRI(babybear_extension)
+ICICLE_HIP_DECLARE_FRI(koalabear)
+ICICLE_HIP_DECLARE_FRI(koalabear_extension)
 
 /* ---- backend-specific helpers (not part of the reference ABI) ---- */
 const char* icicle_hip_version(void);

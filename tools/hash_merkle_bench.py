@@ -7,8 +7,14 @@ the tool did before it knew other hashers.
 --pow times the proof-of-work solver instead: a search over 2^26 nonces that cannot succeed (60 bits, hip_pow_count_log2 = 26) beside the
 batch hash of 2^22 x 64 B in the same interleaved rounds, both as time per hash, and whole solves of the challenge bytes(range(32))
 at --pow-bits by nonces per launch (--pow-span-log2).
+--fri times the FRI prover (BabyBear extension, Blake2s trees and transcript, default config: 16 proof-of-work bits, 100 queries) at
+--fri-log-n sizes from a device input: the whole fri_merkle_tree_prove, and its stages run one by one through the public API on the
+same layers -- the tree builds, the folds, the proof of work, the 2 x queries x rounds get_proof calls of the query phase --, then the
+first fold's bytes per second (n + n/2 elements and n/2 twiddles) beside a device-to-device copy that moves the same byte count, in
+interleaved rounds of the same run.
 usage: tools/hash_merkle_bench.py [--hash keccak256 [blake2s blake3]] [--log-batch 22] [--log-leaves 22 10] [--top-max 0 256 1024] [--reps 5]
-       tools/hash_merkle_bench.py --pow [--hash keccak256 blake2s blake3] [--reps 9] [--pow-bits 20 25 30] [--pow-span-log2 24 28 32]"""
+       tools/hash_merkle_bench.py --pow [--hash keccak256 blake2s blake3] [--reps 9] [--pow-bits 20 25 30] [--pow-span-log2 24 28 32]
+       tools/hash_merkle_bench.py --fri [--fri-log-n 20 24] [--reps 5]"""
 import argparse
 import ctypes
 import os
@@ -104,8 +110,89 @@ def pow_bench(a):
             print(f"{name} solve {bits} bits, nonce {got[0][1]}: " + " | ".join(row))
 
 
+def fri_bench(a):
+    import icicle_amd
+    from icicle_amd import FriConfig, FriTranscriptConfig, MerkleTreeConfig, fri, ntt, runtime
+    from icicle_amd._lib import lib, check
+    from icicle_amd.hash import Hasher
+    from icicle_amd.merkle import MerkleTree
+    from icicle_amd.runtime import DeviceVec
+
+    runtime.set_device(0)
+    field, p, eb = "babybear", 0x78000001, 16
+    rng = np.random.default_rng(1)
+    th, lh, ch = Hasher.blake2s(), Hasher.blake2s(eb), Hasher.blake2s(64)
+    tc = FriTranscriptConfig.new_default_labels(th, 1)
+    med = lambda t: t[len(t) // 2]
+    for logn in a.fri_log_n:
+        n = 1 << logn
+        ntt.release_domain(field)
+        ntt.init_domain(field, ntt.get_root_of_unity(field, n))
+        d_x = DeviceVec.from_host(rng.integers(0, p, size=(n, 4), dtype=np.uint32))
+        cfg = FriConfig.default()
+        proofs = []
+        total = all_interleaved([lambda: proofs.append(icicle_amd.fri_merkle_tree_prove(field, cfg, tc, d_x, lh, ch, 0, extension=True))], a.reps)[0]
+        assert all(pr.pow_nonce == proofs[0].pow_nonce for pr in proofs)
+        rounds, queries = proofs[0].nof_rounds, cfg.nof_queries
+        del proofs
+        # the stages, one by one, on layers folded with a fixed challenge (the work does not depend on its value)
+        d_alpha = DeviceVec.from_host(np.array([5, 6, 7, 8], dtype=np.uint32))
+        layers = [d_x] + [DeviceVec(eb * (n >> r)) for r in range(1, rounds + 1)]
+
+        def folds():
+            for r in range(rounds):
+                fri.fri_fold(field, layers[r], d_alpha, extension=True, out=layers[r + 1])
+            runtime.device_synchronize()
+
+        mcfg = MerkleTreeConfig.default()
+        mcfg.is_tree_on_device = True
+        trees = []
+
+        def builds():
+            for t in trees:
+                t.close()
+            trees[:] = [MerkleTree([lh] + [ch] * (logn - r), eb).build(layers[r], cfg=mcfg) for r in range(rounds)]
+
+        challenge = np.frombuffer(b"domain_separator_label" + logn.to_bytes(4, "little") + bytes(eb) + b"nonce_label", dtype=np.uint8).copy()
+        picks = [int(q) for q in rng.integers(1, n + 1, queries)]
+
+        def query_phase():
+            for q in picks:
+                for r in range(rounds):
+                    size = n >> r
+                    for idx in (q % size, (q + size // 2) % size):
+                        trees[r].proof(layers[r], idx, False, mcfg).close()
+
+        folds()
+        st = all_interleaved([builds, folds, lambda: icicle_amd.pow_solve(th, challenge, cfg.pow_bits), query_phase], a.reps)
+        print(f"fri prove {field}_extension 2^{logn}, blake2s, {cfg.pow_bits} pow bits, {queries} queries, {rounds} rounds, device input: median {med(total):.3f} ms "
+              f"({total[0]:.3f} .. {total[-1]:.3f}) of {a.reps}")
+        for label, t in zip(("tree builds", "folds", "proof of work", f"query phase ({2 * queries * rounds} get_proof calls)"), st):
+            print(f"fri stage 2^{logn} {label}: median {med(t):.3f} ms ({t[0]:.3f} .. {t[-1]:.3f}), {100 * med(t) / med(total):.0f}% of the prove")
+        # the first fold against a copy of the same byte count: n + n/2 elements and n/2 twiddle words
+        moved = eb * n + eb * n // 2 + 4 * n // 2
+        d_src, d_dst = DeviceVec(moved // 2), DeviceVec(moved // 2)
+
+        def fold0():
+            fri.fri_fold(field, layers[0], d_alpha, extension=True, out=layers[1])
+            runtime.device_synchronize()
+
+        def copy():
+            check(lib.icicle_copy(d_dst.ptr, d_src.ptr, moved // 2))
+            runtime.device_synchronize()
+
+        f, c = all_interleaved([fold0, copy], max(a.reps, 9))
+        print(f"fri fold 2^{logn} -> 2^{logn - 1}: {moved / 2**20:.0f} MiB moved, median {med(f):.3f} ms ({f[0]:.3f} .. {f[-1]:.3f}) = {moved / med(f) / 1e9:.2f} TB/s | "
+              f"device-to-device copy of the same bytes: median {med(c):.3f} ms ({c[0]:.3f} .. {c[-1]:.3f}) = {moved / med(c) / 1e9:.2f} TB/s | fold / copy {med(f) / med(c):.2f}")
+        for t in trees:
+            t.close()
+        ntt.release_domain(field)
+
+
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--fri", action="store_true")
+    ap.add_argument("--fri-log-n", type=int, nargs="*", default=[20, 24])
     ap.add_argument("--pow", action="store_true")
     ap.add_argument("--pow-bits", type=int, nargs="*", default=[20, 25, 30])
     ap.add_argument("--pow-span-log2", type=int, nargs="*", default=[24, 28, 32])
@@ -117,6 +204,8 @@ def main():
     a = ap.parse_args()
     if a.pow:
         return pow_bench(a)
+    if a.fri:
+        return fri_bench(a)
     import icicle_amd
     from icicle_amd import runtime
     from icicle_amd._lib import lib
