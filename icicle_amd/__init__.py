@@ -4,9 +4,10 @@ The product is libicicle_hip.so (hand-written HIP, C ABI in include/icicle_hip.h
 the thin host-side mirror of the reference's wrapper API (wrappers/rust/icicle-core/src/{msm,ntt},
 icicle-runtime) used by the tests and bench.py. There is no CPU fallback anywhere in here.
 """
-from ._lib import IcicleError, Device, MSMConfig, NTTConfigU32, NTTConfigU64, NTTConfigU256, NTTInitDomainConfig, VecOpsConfig, HashConfig, MerkleTreeConfig, PowConfig, FriConfig, lib, LIB_PATH  # noqa: F401
-from . import runtime, msm, ntt, vecops, hash, merkle, fri  # noqa: F401
+from ._lib import IcicleError, Device, MSMConfig, NTTConfigU32, NTTConfigU64, NTTConfigU256, NTTInitDomainConfig, VecOpsConfig, HashConfig, MerkleTreeConfig, PowConfig, FriConfig, SumcheckConfig, lib, LIB_PATH  # noqa: F401
+from . import runtime, msm, ntt, vecops, hash, merkle, fri, sumcheck  # noqa: F401
 from .pow import pow_solve, pow_verify  # noqa: F401
 from .fri import FriTranscriptConfig, FriProof, fri_merkle_tree_prove, fri_merkle_tree_verify  # noqa: F401
+from .sumcheck import Symbol, ReturningValueProgram, SumcheckTranscriptConfig, Sumcheck, SumcheckProof  # noqa: F401
 
-__all__ = ["runtime", "msm", "ntt", "vecops", "hash", "merkle", "fri", "pow_solve", "pow_verify", "FriConfig", "FriTranscriptConfig", "FriProof", "fri_merkle_tree_prove", "fri_merkle_tree_verify", "HashConfig", "MerkleTreeConfig", "PowConfig", "VecOpsConfig", "IcicleError", "Device", "MSMConfig", "NTTConfigU32", "NTTConfigU64", "NTTConfigU256", "NTTInitDomainConfig"]
+__all__ = ["runtime", "msm", "ntt", "vecops", "hash", "merkle", "fri", "sumcheck", "Symbol", "ReturningValueProgram", "SumcheckConfig", "SumcheckTranscriptConfig", "Sumcheck", "SumcheckProof", "pow_solve", "pow_verify", "FriConfig", "FriTranscriptConfig", "FriProof", "fri_merkle_tree_prove", "fri_merkle_tree_verify", "HashConfig", "MerkleTreeConfig", "PowConfig", "VecOpsConfig", "IcicleError", "Device", "MSMConfig", "NTTConfigU32", "NTTConfigU64", "NTTConfigU256", "NTTInitDomainConfig"]

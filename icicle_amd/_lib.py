@@ -235,7 +235,38 @@ class FFIFriTranscriptConfig(ctypes.Structure):
     ]
 
 
+class SumcheckConfig(ctypes.Structure):
+    """icicle::SumcheckConfig (include/icicle/sumcheck/sumcheck_config.h), 40 bytes."""
+    _fields_ = [
+        ("stream", ctypes.c_void_p),
+        ("use_extension_field", ctypes.c_bool),
+        ("batch", ctypes.c_uint64),
+        ("are_inputs_on_device", ctypes.c_bool),
+        ("is_async", ctypes.c_bool),
+        ("ext", ctypes.c_void_p),
+    ]
+
+    @classmethod
+    def default(cls):
+        # default_sumcheck_config()
+        return cls(None, False, 1, False, False, None)
+
+
+class FFISumcheckTranscriptConfig(ctypes.Structure):
+    """TranscriptConfigFFI (src/sumcheck/sumcheck_c_api.cpp:14-24), 72 bytes; built by icicle_amd.sumcheck.SumcheckTranscriptConfig."""
+    _fields_ = [
+        ("hasher", ctypes.c_void_p),
+        ("domain_separator_label", ctypes.c_void_p), ("domain_separator_label_len", ctypes.c_size_t),
+        ("round_poly_label", ctypes.c_void_p), ("round_poly_label_len", ctypes.c_size_t),
+        ("round_challenge_label", ctypes.c_void_p), ("round_challenge_label_len", ctypes.c_size_t),
+        ("little_endian", ctypes.c_bool),
+        ("seed_rng", ctypes.c_void_p),
+    ]
+
+
 assert ctypes.sizeof(Device) == 68 and Device.id.offset == 64
+assert ctypes.sizeof(SumcheckConfig) == 40 and [getattr(SumcheckConfig, f).offset for f, _ in SumcheckConfig._fields_] == [0, 8, 16, 24, 25, 32]
+assert ctypes.sizeof(FFISumcheckTranscriptConfig) == 72 and FFISumcheckTranscriptConfig.little_endian.offset == 56 and FFISumcheckTranscriptConfig.seed_rng.offset == 64
 assert ctypes.sizeof(FriConfig) == 56 and [getattr(FriConfig, f).offset for f, _ in FriConfig._fields_] == [0, 8, 16, 24, 32, 40, 41, 48]
 assert ctypes.sizeof(FFIFriTranscriptConfig) == 96 and FFIFriTranscriptConfig.seed_rng.offset == 88
 assert ctypes.sizeof(PowConfig) == 32 and [getattr(PowConfig, f).offset for f, _ in PowConfig._fields_] == [0, 8, 12, 16, 24]
@@ -275,6 +306,12 @@ FRI_PREFIXES = [f"{f}{e}" for f in NTT_FIELDS for e in ("", "_extension")]
 FRI_FUNCTIONS = ["icicle_delete_fri_proof", "fri_proof_get_nof_queries", "fri_proof_get_nof_rounds", "fri_proof_get_round_proofs_for_query",
                  "fri_proof_get_final_poly_size", "fri_proof_get_final_poly", "fri_proof_get_pow_nonce", "fri_merkle_tree_prove", "fri_merkle_tree_verify",
                  "hip_fri_fold"]
+# Sumcheck, programs and symbols (src/sumcheck/sumcheck_c_api.cpp, src/program/program_c_api.cpp, src/symbol/symbol_api.cpp): the
+# functions that return an error code, per field; words of an element per field
+SUMCHECK_FIELDS = {"babybear": 1, "koalabear": 1, "bn254": 8, "bls12_381": 8}
+SUMCHECK_FUNCTIONS = ["sumcheck_delete", "hip_sumcheck_prove", "sumcheck_verify", "sumcheck_proof_get_poly_sizes", "sumcheck_proof_delete",
+                      "sumcheck_get_challenge_vector", "sumcheck_get_challenge_size", "generate_returning_value_program", "add_symbols", "sub_symbols",
+                      "multiply_symbols", "inverse_symbol"]
 API_SYMBOLS = (
     [f"{c}_{s}" for c in CURVES for s in ("msm", "msm_precompute_bases", "hip_generate_affine_points", "hip_projective_sum")]
     + [f"{c}_g2_{s}" for c in G2_CURVES for s in ("msm", "msm_precompute_bases", "hip_generate_affine_points", "hip_projective_sum")]
@@ -309,6 +346,7 @@ API_SYMBOLS = (
        "icicle_merkle_tree_verify", "icicle_merkle_proof_delete", "icicle_merkle_proof_is_pruned"]
     + ["proof_of_work", "proof_of_work_verify"]
     + [f"{p}_{s}" for p in FRI_PREFIXES for s in FRI_FUNCTIONS]
+    + [f"{p}_{s}" for p in SUMCHECK_FIELDS for s in SUMCHECK_FUNCTIONS] + ["delete_program", "icicle_hip_sumcheck_time_rounds", "icicle_hip_sumcheck_round_times"]
 )
 # hash / Merkle functions that return a handle, a size or a byte pointer (tests/test_abi.py's header scan sees only the return types
 # of the lists above; tests/test_hash_cpu.py checks these against the header with a scan of its own): name -> restype
@@ -326,6 +364,10 @@ HASH_HANDLE_SYMBOLS = list(_HASH_RESTYPES)
 BLAKE_HANDLE_SYMBOLS = {"icicle_create_blake2s": ctypes.c_void_p, "icicle_create_blake3": ctypes.c_void_p}
 # the two FRI functions that return a proof handle: name -> restype
 FRI_HANDLE_SYMBOLS = {f"{p}_{s}": ctypes.c_void_p for p in FRI_PREFIXES for s in ("icicle_initialize_fri_proof", "icicle_create_with_arguments_fri_proof")}
+# the sumcheck, program and symbol functions that return a handle or a pointer: name -> restype
+SUMCHECK_HANDLE_SYMBOLS = {f"{p}_{s}": ctypes.c_void_p for p in SUMCHECK_FIELDS
+                           for s in ("sumcheck_create", "sumcheck_get_proof", "sumcheck_proof_create", "sumcheck_proof_get_round_poly_at",
+                                     "create_predefined_returning_value_program", "create_input_symbol", "create_scalar_symbol", "copy_symbol")}
 
 if not os.path.exists(LIB_PATH):
     raise ImportError(
@@ -465,6 +507,35 @@ for _p in FRI_PREFIXES:
     getattr(lib, f"{_p}_fri_merkle_tree_verify").argtypes = [ctypes.POINTER(FriConfig), ctypes.POINTER(FFIFriTranscriptConfig), ctypes.c_void_p, ctypes.c_void_p,
                                                              ctypes.c_void_p, ctypes.POINTER(ctypes.c_bool)]
     getattr(lib, f"{_p}_hip_fri_fold").argtypes = [ctypes.c_void_p, ctypes.c_uint64, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_bool, ctypes.c_void_p]
+for _s, _r in SUMCHECK_HANDLE_SYMBOLS.items():
+    getattr(lib, _s).restype = _r  # AttributeError if the symbol is missing
+_void_pp = ctypes.POINTER(ctypes.c_void_p)
+lib.delete_program.argtypes = [ctypes.c_void_p]
+lib.icicle_hip_sumcheck_time_rounds.argtypes = [ctypes.c_bool]
+lib.icicle_hip_sumcheck_round_times.argtypes = [ctypes.POINTER(ctypes.c_double), ctypes.c_int, ctypes.POINTER(ctypes.c_int)]
+for _p in SUMCHECK_FIELDS:
+    _prove_args = [ctypes.c_void_p, _void_pp, ctypes.c_uint64, ctypes.c_uint64, ctypes.c_void_p, ctypes.c_void_p, ctypes.POINTER(FFISumcheckTranscriptConfig),
+                   ctypes.POINTER(SumcheckConfig)]
+    getattr(lib, f"{_p}_sumcheck_create").argtypes = []
+    getattr(lib, f"{_p}_sumcheck_delete").argtypes = [ctypes.c_void_p]
+    getattr(lib, f"{_p}_sumcheck_get_proof").argtypes = _prove_args
+    getattr(lib, f"{_p}_hip_sumcheck_prove").argtypes = _prove_args + [ctypes.c_void_p]
+    getattr(lib, f"{_p}_sumcheck_verify").argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.POINTER(FFISumcheckTranscriptConfig),
+                                                      ctypes.POINTER(ctypes.c_bool)]
+    getattr(lib, f"{_p}_sumcheck_proof_create").argtypes = [_void_pp, ctypes.c_uint64, ctypes.c_uint64]
+    getattr(lib, f"{_p}_sumcheck_proof_get_poly_sizes").argtypes = [ctypes.c_void_p, _u64_p, _u64_p]
+    getattr(lib, f"{_p}_sumcheck_proof_get_round_poly_at").argtypes = [ctypes.c_void_p, ctypes.c_uint64]
+    getattr(lib, f"{_p}_sumcheck_proof_delete").argtypes = [ctypes.c_void_p]
+    getattr(lib, f"{_p}_sumcheck_get_challenge_vector").argtypes = [ctypes.c_void_p, ctypes.c_void_p, _size_p]
+    getattr(lib, f"{_p}_sumcheck_get_challenge_size").argtypes = [ctypes.c_void_p, _size_p]
+    getattr(lib, f"{_p}_create_predefined_returning_value_program").argtypes = [ctypes.c_int]
+    getattr(lib, f"{_p}_generate_returning_value_program").argtypes = [_void_pp, ctypes.c_int, _void_pp]
+    getattr(lib, f"{_p}_create_input_symbol").argtypes = [ctypes.c_int]
+    getattr(lib, f"{_p}_create_scalar_symbol").argtypes = [ctypes.c_void_p]
+    getattr(lib, f"{_p}_copy_symbol").argtypes = [ctypes.c_void_p]
+    for _s in ("add_symbols", "sub_symbols", "multiply_symbols"):
+        getattr(lib, f"{_p}_{_s}").argtypes = [ctypes.c_void_p, ctypes.c_void_p, _void_pp]
+    getattr(lib, f"{_p}_inverse_symbol").argtypes = [ctypes.c_void_p, _void_pp]
 
 
 def multi_stats(reset=False):

@@ -301,8 +301,9 @@ ICICLE_HIP_DECLARE_TRANSPOSE(stark252, matrix_transpose)
  * Keccak-f[1600] sponges: rate 136 bytes for the 256-bit digests, 72 bytes for the 512-bit ones; Keccak pads 0x01 .. 0x80,
  * SHA3 0x06 .. 0x80. Creating and deleting handles needs no GPU; hashing, build, get_proof and verify run on the device and
  * fail without one. Blake2s-256 and Blake3 hash through the same entry points; the proof-of-work solver and verifier over all six
- * hashers follow the Merkle functions below, and FRI over BabyBear / KoalaBear, which composes all of them, follows the proof of work.
- * Poseidon, Poseidon2 and proof serialisation (Merkle and FRI) are not built.
+ * hashers follow the Merkle functions below, and FRI over BabyBear / KoalaBear, which composes all of them, follows the proof of work;
+ * sumcheck, whose transcript hashes through the same entry points, follows FRI.
+ * Poseidon, Poseidon2 and proof serialisation (Merkle, FRI and sumcheck) are not built.
  * ====================================================================================== */
 typedef struct {
   icicleStreamHandle stream;      /* 0  */
@@ -478,6 +479,89 @@ ICICLE_HIP_DECLARE_FRI(babybear)
 ICICLE_HIP_DECLARE_FRI(babybear_extension)
 ICICLE_HIP_DECLARE_FRI(koalabear)
 ICICLE_HIP_DECLARE_FRI(koalabear_extension)
+
+/* ---- Sumcheck, programs and symbols: src/sumcheck/sumcheck_c_api.cpp, src/program/program_c_api.cpp, src/symbol/symbol_api.cpp,
+ * include/icicle/sumcheck/sumcheck_config.h (SumcheckConfig, 40 bytes), TranscriptConfigFFI (72 bytes). Over babybear, koalabear
+ * (one word per element) and the bn254, bls12_381 scalar fields (eight words), canonical elements.
+ * The prover takes nof_mle_polynomials tables of mle_polynomial_size = 2^L elements, a combine function g of that many inputs with
+ * polynomial degree d, and the claimed sum; the proof is L round polynomials of d + 1 evaluations at x = 0..d. Round r >= 1 first
+ * folds adjacent elements, T_r[j] = T_{r-1}[2j] + alpha_r (T_{r-1}[2j+1] - T_{r-1}[2j]); alpha_0 = 0 is recorded in the challenge
+ * vector and never used, alpha_r = F(H(message of round r - 1)) with F the whole digest as one little-endian integer mod p
+ * (transcript bytes: INTEGRATION.md). verify: R_0[0] + R_0[1] = claimed_sum, and R_r(alpha_{r+1}) = R_{r+1}[0] + R_{r+1}[1] for
+ * r < L - 1; the last round polynomial is not checked against anything, as in the reference. A proof no prover makes (no rounds,
+ * round polynomials of different or impossible lengths, a word at or above p) is a wrong proof: *is_verified = false with SUCCESS.
+ * Programs: the predefined AB_MINUS_C (id 0: inputs A, B, C, degree 2) and EQ_X_AB_MINUS_C (id 1: A, B, C, E, E (A B - C), degree 3),
+ * or a function built from symbols -- input, constant, add, sub, multiply, inverse -- and compiled by
+ * <field>_generate_returning_value_program(parameters, nof_parameters, &program): the inputs' symbols followed by the return value's.
+ * Symbols belong to the library; every generate call frees all symbols made so far. Degree: input 1, constant 0, add / sub the
+ * larger, multiply the sum, inverse -1 (and -1 wherever it is used).
+ * <field>_hip_sumcheck_prove is <field>_sumcheck_get_proof writing into a proof made by the caller and returning the error
+ * (get_proof returns NULL on any failure). INVALID_ARGUMENT, before the device is touched: mle_polynomial_size no power of two or
+ * < 2, nof_mle_polynomials not the program's input count or above 8, degree below 1 or above 6, more than 20 variables (parameters
+ * + constants + one per operation; the return value's node takes the output parameter's slot), use_extension_field, a program of
+ * another field. NULL pointers: INVALID_POINTER. `batch` is ignored, as the reference ignores it; `stream` is honoured; prove
+ * returns with the stream drained (the proof is host data). The caller's polynomials are never written.
+ * get_challenge_vector copies min(*size, the vector's length) elements and stores that count in *size.
+ * The three serialisation functions, proof_print and the extension_ / rns_ variants are not built. ---- */
+typedef struct {
+  icicleStreamHandle stream;      /* 0  */
+  bool use_extension_field;       /* 8   must be false */
+  uint64_t batch;                 /* 16  ignored */
+  bool are_inputs_on_device;      /* 24 */
+  bool is_async;                  /* 25 */
+  icicle_config_extension_t* ext; /* 32 */
+} icicle_sumcheck_config_t;
+typedef struct {
+  icicle_hasher_handle_t hasher;         /* 0  */
+  const uint8_t* domain_separator_label; /* 8  */
+  size_t domain_separator_label_len;     /* 16 */
+  const uint8_t* round_poly_label;       /* 24 */
+  size_t round_poly_label_len;           /* 32 */
+  const uint8_t* round_challenge_label;  /* 40 */
+  size_t round_challenge_label_len;      /* 48 */
+  bool little_endian;                    /* 56  carried, unused (as in the reference) */
+  const uint32_t* seed_rng;              /* 64  one element of F, canonical */
+} icicle_sumcheck_transcript_config_t;
+typedef struct icicle_sumcheck* icicle_sumcheck_handle_t;
+typedef struct icicle_sumcheck_proof* icicle_sumcheck_proof_handle_t;
+typedef struct icicle_program* icicle_program_handle_t;
+typedef struct icicle_symbol* icicle_symbol_handle_t;
+icicle_error_t delete_program(icicle_program_handle_t program);
+#define ICICLE_HIP_DECLARE_SUMCHECK(P)                                                                                 \
+  icicle_sumcheck_handle_t P##_sumcheck_create(void);                                                                  \
+  icicle_error_t P##_sumcheck_delete(icicle_sumcheck_handle_t sumcheck);                                               \
+  icicle_sumcheck_proof_handle_t P##_sumcheck_get_proof(icicle_sumcheck_handle_t sumcheck, const uint32_t* const* mle_polynomials, uint64_t mle_polynomial_size, \
+                                                        uint64_t nof_mle_polynomials, const uint32_t* claimed_sum, icicle_program_handle_t combine_function, \
+                                                        const icicle_sumcheck_transcript_config_t* transcript_config, const icicle_sumcheck_config_t* sumcheck_config); \
+  icicle_error_t P##_hip_sumcheck_prove(icicle_sumcheck_handle_t sumcheck, const uint32_t* const* mle_polynomials, uint64_t mle_polynomial_size, \
+                                        uint64_t nof_mle_polynomials, const uint32_t* claimed_sum, icicle_program_handle_t combine_function, \
+                                        const icicle_sumcheck_transcript_config_t* transcript_config, const icicle_sumcheck_config_t* sumcheck_config, \
+                                        icicle_sumcheck_proof_handle_t proof);                                         \
+  icicle_error_t P##_sumcheck_verify(icicle_sumcheck_handle_t sumcheck, icicle_sumcheck_proof_handle_t proof, const uint32_t* claimed_sum, \
+                                     const icicle_sumcheck_transcript_config_t* transcript_config, bool* is_verified); \
+  icicle_sumcheck_proof_handle_t P##_sumcheck_proof_create(uint32_t** polys, uint64_t nof_polynomials, uint64_t poly_size); \
+  icicle_error_t P##_sumcheck_proof_get_poly_sizes(icicle_sumcheck_proof_handle_t proof, uint64_t* poly_size, uint64_t* nof_polys); \
+  uint32_t* P##_sumcheck_proof_get_round_poly_at(icicle_sumcheck_proof_handle_t proof, uint64_t index);                \
+  icicle_error_t P##_sumcheck_proof_delete(icicle_sumcheck_proof_handle_t proof);                                      \
+  icicle_error_t P##_sumcheck_get_challenge_vector(icicle_sumcheck_handle_t sumcheck, uint32_t* challenge_vector, size_t* challenge_vector_size); \
+  icicle_error_t P##_sumcheck_get_challenge_size(icicle_sumcheck_handle_t sumcheck, size_t* challenge_size);           \
+  icicle_program_handle_t P##_create_predefined_returning_value_program(int pre_def);                                  \
+  icicle_error_t P##_generate_returning_value_program(icicle_symbol_handle_t* parameters, int nof_parameters, icicle_program_handle_t* program); \
+  icicle_symbol_handle_t P##_create_input_symbol(int in_idx);                                                          \
+  icicle_symbol_handle_t P##_create_scalar_symbol(const uint32_t* constant);                                           \
+  icicle_symbol_handle_t P##_copy_symbol(icicle_symbol_handle_t other);                                                \
+  icicle_error_t P##_add_symbols(icicle_symbol_handle_t op_a, icicle_symbol_handle_t op_b, icicle_symbol_handle_t* res); \
+  icicle_error_t P##_sub_symbols(icicle_symbol_handle_t op_a, icicle_symbol_handle_t op_b, icicle_symbol_handle_t* res); \
+  icicle_error_t P##_multiply_symbols(icicle_symbol_handle_t op_a, icicle_symbol_handle_t op_b, icicle_symbol_handle_t* res); \
+  icicle_error_t P##_inverse_symbol(icicle_symbol_handle_t input, icicle_symbol_handle_t* output);
+ICICLE_HIP_DECLARE_SUMCHECK(babybear)
+ICICLE_HIP_DECLARE_SUMCHECK(koalabear)
+ICICLE_HIP_DECLARE_SUMCHECK(bn254)
+ICICLE_HIP_DECLARE_SUMCHECK(bls12_381)
+/* backend-specific, for timing tools: while enabled, every prove records device events around each round's two launches; round_times
+ * copies the last proof's times (milliseconds, at most `capacity` of them) and stores the number of rounds it has in *rounds */
+icicle_error_t icicle_hip_sumcheck_time_rounds(bool enable);
+icicle_error_t icicle_hip_sumcheck_round_times(double* ms, int capacity, int* rounds);
 
 /* ---- backend-specific helpers (not part of the reference ABI) ---- */
 const char* icicle_hip_version(void);
