@@ -303,6 +303,9 @@ BIG_VEC_FIELDS = SCALAR_NTT_FIELDS + ["grumpkin"]  # element-wise ops / Montgome
 GOLD = "goldilocks"  # 2-word elements, NTTConfigU64; extension field = 2 components
 # FRI (src/fri/fri_c_api.cpp): the functions that return an error code, per field and again with the prefix <field>_extension
 FRI_PREFIXES = [f"{f}{e}" for f in NTT_FIELDS for e in ("", "_extension")]
+# the same functions over the wider fields (fri_wide.hip): prefix -> uint32 words of one element
+FRI_WIDE_WORDS = {GOLD: 2, f"{GOLD}_extension": 4, "stark252": 8, "bn254": 8, "bls12_381": 8, "bls12_377": 8}
+FRI_WIDE_PREFIXES = list(FRI_WIDE_WORDS)
 FRI_FUNCTIONS = ["icicle_delete_fri_proof", "fri_proof_get_nof_queries", "fri_proof_get_nof_rounds", "fri_proof_get_round_proofs_for_query",
                  "fri_proof_get_final_poly_size", "fri_proof_get_final_poly", "fri_proof_get_pow_nonce", "fri_merkle_tree_prove", "fri_merkle_tree_verify",
                  "hip_fri_fold"]
@@ -345,7 +348,7 @@ API_SYMBOLS = (
     + ["icicle_hasher_hash", "icicle_hasher_delete", "icicle_merkle_tree_delete", "icicle_merkle_tree_build", "icicle_merkle_tree_get_proof",
        "icicle_merkle_tree_verify", "icicle_merkle_proof_delete", "icicle_merkle_proof_is_pruned"]
     + ["proof_of_work", "proof_of_work_verify"]
-    + [f"{p}_{s}" for p in FRI_PREFIXES for s in FRI_FUNCTIONS]
+    + [f"{p}_{s}" for p in FRI_PREFIXES + FRI_WIDE_PREFIXES for s in FRI_FUNCTIONS]
     + [f"{p}_{s}" for p in SUMCHECK_FIELDS for s in SUMCHECK_FUNCTIONS] + ["delete_program", "icicle_hip_sumcheck_time_rounds", "icicle_hip_sumcheck_round_times"]
 )
 # hash / Merkle functions that return a handle, a size or a byte pointer (tests/test_abi.py's header scan sees only the return types
@@ -363,7 +366,7 @@ HASH_HANDLE_SYMBOLS = list(_HASH_RESTYPES)
 # the Blake factories (hash_c_api.cpp:123, :136), a table of their own: name -> restype
 BLAKE_HANDLE_SYMBOLS = {"icicle_create_blake2s": ctypes.c_void_p, "icicle_create_blake3": ctypes.c_void_p}
 # the two FRI functions that return a proof handle: name -> restype
-FRI_HANDLE_SYMBOLS = {f"{p}_{s}": ctypes.c_void_p for p in FRI_PREFIXES for s in ("icicle_initialize_fri_proof", "icicle_create_with_arguments_fri_proof")}
+FRI_HANDLE_SYMBOLS = {f"{p}_{s}": ctypes.c_void_p for p in FRI_PREFIXES + FRI_WIDE_PREFIXES for s in ("icicle_initialize_fri_proof", "icicle_create_with_arguments_fri_proof")}
 # the sumcheck, program and symbol functions that return a handle or a pointer: name -> restype
 SUMCHECK_HANDLE_SYMBOLS = {f"{p}_{s}": ctypes.c_void_p for p in SUMCHECK_FIELDS
                            for s in ("sumcheck_create", "sumcheck_get_proof", "sumcheck_proof_create", "sumcheck_proof_get_round_poly_at",
@@ -492,7 +495,7 @@ lib.proof_of_work_verify.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_
                                      ctypes.POINTER(ctypes.c_bool), _u64_p]
 for _s, _r in FRI_HANDLE_SYMBOLS.items():
     getattr(lib, _s).restype = _r  # AttributeError if the symbol is missing
-for _p in FRI_PREFIXES:
+for _p in FRI_PREFIXES + FRI_WIDE_PREFIXES:
     getattr(lib, f"{_p}_icicle_initialize_fri_proof").argtypes = []
     getattr(lib, f"{_p}_icicle_create_with_arguments_fri_proof").argtypes = [ctypes.c_void_p, ctypes.c_size_t, ctypes.c_size_t, ctypes.c_void_p, ctypes.c_size_t,
                                                                              ctypes.c_uint64]

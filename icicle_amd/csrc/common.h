@@ -346,6 +346,9 @@ namespace icicle_hip {
   // field 0 = babybear, 1 = koalabear; false: no domain initialised. The pointer is handed out without a reference: the caller of
   // the API keeps the domain alive (no <field>_ntt_release_domain) until the call that read it has returned, as for an NTT
   bool ntt_domain_table(int field, const uint32_t** tw, int* log_max);
+  // the same of ntt_big.hip's BigDomain: field 0 = bn254, 1 = bls12_381, 2 = bls12_377, 3 = stark252 (8 words per entry, packed
+  // Montgomery), 4 = goldilocks (2 words, canonical); for the fold of fri_wide.hip
+  bool ntt_big_domain_table(int field, const uint32_t** tw, int* log_max);
   uint64_t hasher_default_chunk(icicle_hasher_handle_t h); // the hasher's default input size, 0 = none
 
   // ---- dominant-kernel timing with hipEvents on the launch stream (bench.py roofline figure) ----

@@ -1,6 +1,6 @@
 // Host-only part of FRI (fri.hip): the parameter checks, the round and tree shapes, the bytes the transcript hashes, the map from
-// a digest to a field element, and the query sampler. No HIP in here, so tests/fri_host_harness.cpp compiles it with g++ and
-// compares it with the Python model (tests/fri_model.py).
+// a digest to a field element, and the query sampler. No HIP in here, so tests/fri_host_harness.cpp and
+// tests/fri_wide_host_harness.cpp compile it with g++ and compare it with the Python models (tests/fri_model.py, fri_model_wide.py).
 //
 // Reference: icicle/src/fri/fri.cpp:329-431 (shapes, check_if_valid), include/icicle/fri/fri_transcript.h (entry_0, the round,
 // proof-of-work and query-phase inputs), include/icicle/utils/rand_gen.h (std::mt19937 + std::uniform_int_distribution<size_t>).
@@ -131,6 +131,52 @@ namespace icicle_hip {
       for (int b = 0; b < 4; b++)
         if ((size_t)(4 * k + b) < len) w |= (uint32_t)digest[4 * k + b] << (8 * b);
       out[k] = w % p;
+    }
+  }
+
+  // F(digest) of the fields wider than 32 bits (the reference's from(bytes, size): math/modular_arithmetic.h, goldilocks.h). A scalar
+  // of `nw` words: the whole digest as one little-endian integer mod p, 32- and 64-byte digests alike -- bit by bit from the top,
+  // r = 2r + bit with one conditional subtraction, so no wide division is needed. p: nw words, nw <= 8.
+  inline void fri_wide_from_digest(const uint8_t* digest, size_t len, const uint32_t* p, int nw, uint32_t* out)
+  {
+    uint32_t r[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+    for (size_t bit = 8 * len; bit-- > 0;) {
+      uint32_t carry = (digest[bit >> 3] >> (bit & 7)) & 1u;
+      for (int i = 0; i < nw; i++) {
+        const uint32_t top = r[i] >> 31;
+        r[i] = (r[i] << 1) | carry;
+        carry = top;
+      }
+      bool ge = carry != 0; // 2r + bit reached 2^(32 nw) > p
+      if (!ge) {
+        ge = true; // equal to p
+        for (int i = nw - 1; i >= 0; i--)
+          if (r[i] != p[i]) {
+            ge = r[i] > p[i];
+            break;
+          }
+      }
+      if (ge) {
+        uint64_t borrow = 0;
+        for (int i = 0; i < nw; i++) {
+          const uint64_t d = (uint64_t)r[i] - p[i] - borrow;
+          r[i] = (uint32_t)d;
+          borrow = (d >> 63) & 1;
+        }
+      }
+    }
+    for (int i = 0; i < nw; i++)
+      out[i] = r[i];
+  }
+  // Goldilocks' quadratic extension (complex_extension.h): coefficient k is the little-endian u64 at bytes 8k .. 8k+7 mod p, so only
+  // the first 16 bytes count; a digest shorter than that gives zero, as the reference does. p: two words, out: four.
+  inline void fri_gold_ext_from_digest(const uint8_t* digest, size_t len, const uint32_t* p, uint32_t* out)
+  {
+    for (int k = 0; k < 2; k++) {
+      if (len < 16)
+        out[2 * k] = out[2 * k + 1] = 0;
+      else
+        fri_wide_from_digest(digest + 8 * k, 8, p, 2, out + 2 * k);
     }
   }
 

@@ -259,6 +259,28 @@ namespace icicle_hip {
     return ICICLE_SUCCESS;
   }
 
+  // The initialised domain's table for the fold of fri_wide.hip (declared in common.h).
+  template <class PR>
+  static bool big_domain_table(const uint32_t** tw, int* log_max)
+  {
+    std::lock_guard<std::mutex> g(BigDomainStore<PR>::mtx());
+    auto it = BigDomainStore<PR>::map().find(current_device_id());
+    if (it == BigDomainStore<PR>::map().end() || !it->second.tw) return false;
+    *tw = it->second.tw, *log_max = it->second.log_max;
+    return true;
+  }
+  bool ntt_big_domain_table(int field, const uint32_t** tw, int* log_max)
+  {
+    switch (field) {
+    case 0: return big_domain_table<bn254_fr_params>(tw, log_max);
+    case 1: return big_domain_table<bls12_381_fr_params>(tw, log_max);
+    case 2: return big_domain_table<bls12_377_fr_params>(tw, log_max);
+    case 3: return big_domain_table<stark252_fr_params>(tw, log_max);
+    case 4: return big_domain_table<goldilocks_params>(tw, log_max);
+    default: return false;
+    }
+  }
+
   template <class PR>
   static icicle_error_t big_release_domain_run()
   {

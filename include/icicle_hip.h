@@ -301,7 +301,7 @@ ICICLE_HIP_DECLARE_TRANSPOSE(stark252, matrix_transpose)
  * Keccak-f[1600] sponges: rate 136 bytes for the 256-bit digests, 72 bytes for the 512-bit ones; Keccak pads 0x01 .. 0x80,
  * SHA3 0x06 .. 0x80. Creating and deleting handles needs no GPU; hashing, build, get_proof and verify run on the device and
  * fail without one. Blake2s-256 and Blake3 hash through the same entry points; the proof-of-work solver and verifier over all six
- * hashers follow the Merkle functions below, and FRI over BabyBear / KoalaBear, which composes all of them, follows the proof of work;
+ * hashers follow the Merkle functions below, and FRI over every field with an NTT, which composes all of them, follows the proof of work;
  * sumcheck, whose transcript hashes through the same entry points, follows FRI.
  * Poseidon, Poseidon2 and proof serialisation (Merkle, FRI and sumcheck) are not built.
  * ====================================================================================== */
@@ -479,6 +479,18 @@ ICICLE_HIP_DECLARE_FRI(babybear)
 ICICLE_HIP_DECLARE_FRI(babybear_extension)
 ICICLE_HIP_DECLARE_FRI(koalabear)
 ICICLE_HIP_DECLARE_FRI(koalabear_extension)
+/* The same over the wider fields that have an NTT, with the same functions, structs and rules: Goldilocks (an element is 8 bytes)
+ * and its quadratic extension (16 bytes: a0 + a1 u with u^2 = 7, constant term first), stark252 and the scalar fields of BN254,
+ * BLS12-381 and BLS12-377 (32 bytes). Elements are canonical little-endian words; the leaves hasher's chunk is one element (8, 16 or
+ * 32 bytes), seed_rng is one element. F(digest) is the reference's from(bytes, size): a scalar is the whole digest as one
+ * little-endian integer mod p, an extension element takes coefficient k from bytes 8k .. 8k+7 mod p. The twiddles come from the
+ * domain of <field>_ntt_init_domain on the current device (goldilocks_extension uses goldilocks'). */
+ICICLE_HIP_DECLARE_FRI(goldilocks)
+ICICLE_HIP_DECLARE_FRI(goldilocks_extension)
+ICICLE_HIP_DECLARE_FRI(stark252)
+ICICLE_HIP_DECLARE_FRI(bn254)
+ICICLE_HIP_DECLARE_FRI(bls12_381)
+ICICLE_HIP_DECLARE_FRI(bls12_377)
 
 /* ---- Sumcheck, programs and symbols: src/sumcheck/sumcheck_c_api.cpp, src/program/program_c_api.cpp, src/symbol/symbol_api.cpp,
  * include/icicle/sumcheck/sumcheck_config.h (SumcheckConfig, 40 bytes), TranscriptConfigFFI (72 bytes). Over babybear, koalabear

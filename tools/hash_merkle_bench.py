@@ -7,14 +7,15 @@ the tool did before it knew other hashers.
 --pow times the proof-of-work solver instead: a search over 2^26 nonces that cannot succeed (60 bits, hip_pow_count_log2 = 26) beside the
 batch hash of 2^22 x 64 B in the same interleaved rounds, both as time per hash, and whole solves of the challenge bytes(range(32))
 at --pow-bits by nonces per launch (--pow-span-log2).
---fri times the FRI prover (BabyBear extension, Blake2s trees and transcript, default config: 16 proof-of-work bits, 100 queries) at
---fri-log-n sizes from a device input: the whole fri_merkle_tree_prove, and its stages run one by one through the public API on the
+--fri times the FRI prover (--field, default the BabyBear extension; Blake2s trees and transcript, default config: 16 proof-of-work
+bits, 100 queries) at --fri-log-n sizes from a device input: the whole fri_merkle_tree_prove, and its stages run one by one through the public API on the
 same layers -- the tree builds, the folds, the proof of work, the 2 x queries x rounds get_proof calls of the query phase --, then the
-first fold's bytes per second (n + n/2 elements and n/2 twiddles) beside a device-to-device copy that moves the same byte count, in
+first fold's bytes per second (n + n/2 elements and n/2 twiddles of the field's table) beside a device-to-device copy that moves the same byte count, in
 interleaved rounds of the same run.
 usage: tools/hash_merkle_bench.py [--hash keccak256 [blake2s blake3]] [--log-batch 22] [--log-leaves 22 10] [--top-max 0 256 1024] [--reps 5]
        tools/hash_merkle_bench.py --pow [--hash keccak256 blake2s blake3] [--reps 9] [--pow-bits 20 25 30] [--pow-span-log2 24 28 32]
-       tools/hash_merkle_bench.py --fri [--fri-log-n 20 24] [--reps 5]"""
+       tools/hash_merkle_bench.py --fri [--field babybear_extension|goldilocks|goldilocks_extension|stark252|bn254|bls12_381|bls12_377]
+                                        [--fri-log-n 20 24] [--reps 5]"""
 import argparse
 import ctypes
 import os
@@ -119,7 +120,12 @@ def fri_bench(a):
     from icicle_amd.runtime import DeviceVec
 
     runtime.set_device(0)
-    field, p, eb = "babybear", 0x78000001, 16
+    # prefix -> field, extension, words of an element, words of a twiddle, a bound below p for every 32-bit word of a random element
+    kinds = {"babybear_extension": ("babybear", True, 4, 1, 0x78000001), "goldilocks": ("goldilocks", False, 2, 2, 0xFFFFFFFF),
+             "goldilocks_extension": ("goldilocks", True, 4, 2, 0xFFFFFFFF), "stark252": ("stark252", False, 8, 8, 0x08000000),
+             "bn254": ("bn254", False, 8, 8, 0x30644E72), "bls12_381": ("bls12_381", False, 8, 8, 0x73EDA753), "bls12_377": ("bls12_377", False, 8, 8, 0x12AB655E)}
+    field, ext, words, tw_words, bound = kinds[a.field]
+    eb = 4 * words
     rng = np.random.default_rng(1)
     th, lh, ch = Hasher.blake2s(), Hasher.blake2s(eb), Hasher.blake2s(64)
     tc = FriTranscriptConfig.new_default_labels(th, 1)
@@ -128,20 +134,20 @@ def fri_bench(a):
         n = 1 << logn
         ntt.release_domain(field)
         ntt.init_domain(field, ntt.get_root_of_unity(field, n))
-        d_x = DeviceVec.from_host(rng.integers(0, p, size=(n, 4), dtype=np.uint32))
+        d_x = DeviceVec.from_host(rng.integers(0, bound, size=(n, words), dtype=np.uint32))  # every word below p's top word: canonical
         cfg = FriConfig.default()
         proofs = []
-        total = all_interleaved([lambda: proofs.append(icicle_amd.fri_merkle_tree_prove(field, cfg, tc, d_x, lh, ch, 0, extension=True))], a.reps)[0]
+        total = all_interleaved([lambda: proofs.append(icicle_amd.fri_merkle_tree_prove(field, cfg, tc, d_x, lh, ch, 0, extension=ext))], a.reps)[0]
         assert all(pr.pow_nonce == proofs[0].pow_nonce for pr in proofs)
         rounds, queries = proofs[0].nof_rounds, cfg.nof_queries
         del proofs
         # the stages, one by one, on layers folded with a fixed challenge (the work does not depend on its value)
-        d_alpha = DeviceVec.from_host(np.array([5, 6, 7, 8], dtype=np.uint32))
+        d_alpha = DeviceVec.from_host(np.arange(5, 5 + words, dtype=np.uint32))
         layers = [d_x] + [DeviceVec(eb * (n >> r)) for r in range(1, rounds + 1)]
 
         def folds():
             for r in range(rounds):
-                fri.fri_fold(field, layers[r], d_alpha, extension=True, out=layers[r + 1])
+                fri.fri_fold(field, layers[r], d_alpha, extension=ext, out=layers[r + 1])
             runtime.device_synchronize()
 
         mcfg = MerkleTreeConfig.default()
@@ -165,16 +171,16 @@ def fri_bench(a):
 
         folds()
         st = all_interleaved([builds, folds, lambda: icicle_amd.pow_solve(th, challenge, cfg.pow_bits), query_phase], a.reps)
-        print(f"fri prove {field}_extension 2^{logn}, blake2s, {cfg.pow_bits} pow bits, {queries} queries, {rounds} rounds, device input: median {med(total):.3f} ms "
+        print(f"fri prove {a.field} 2^{logn}, blake2s, {cfg.pow_bits} pow bits, {queries} queries, {rounds} rounds, device input: median {med(total):.3f} ms "
               f"({total[0]:.3f} .. {total[-1]:.3f}) of {a.reps}")
         for label, t in zip(("tree builds", "folds", "proof of work", f"query phase ({2 * queries * rounds} get_proof calls)"), st):
             print(f"fri stage 2^{logn} {label}: median {med(t):.3f} ms ({t[0]:.3f} .. {t[-1]:.3f}), {100 * med(t) / med(total):.0f}% of the prove")
-        # the first fold against a copy of the same byte count: n + n/2 elements and n/2 twiddle words
-        moved = eb * n + eb * n // 2 + 4 * n // 2
+        # the first fold against a copy of the same byte count: n + n/2 elements and n/2 twiddles
+        moved = eb * n + eb * n // 2 + 4 * tw_words * n // 2
         d_src, d_dst = DeviceVec(moved // 2), DeviceVec(moved // 2)
 
         def fold0():
-            fri.fri_fold(field, layers[0], d_alpha, extension=True, out=layers[1])
+            fri.fri_fold(field, layers[0], d_alpha, extension=ext, out=layers[1])
             runtime.device_synchronize()
 
         def copy():
@@ -193,6 +199,8 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--fri", action="store_true")
     ap.add_argument("--fri-log-n", type=int, nargs="*", default=[20, 24])
+    ap.add_argument("--field", default="babybear_extension",
+                    choices=["babybear_extension", "goldilocks", "goldilocks_extension", "stark252", "bn254", "bls12_381", "bls12_377"])
     ap.add_argument("--pow", action="store_true")
     ap.add_argument("--pow-bits", type=int, nargs="*", default=[20, 25, 30])
     ap.add_argument("--pow-span-log2", type=int, nargs="*", default=[24, 28, 32])
