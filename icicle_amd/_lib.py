@@ -347,6 +347,7 @@ API_SYMBOLS = (
     + [f"{pre}{c}_g2_{k}_convert_montgomery" for pre in ("", "icicle_hip_") for c in G2_CURVES for k in ("affine", "projective")]
     + ["icicle_hasher_hash", "icicle_hasher_delete", "icicle_merkle_tree_delete", "icicle_merkle_tree_build", "icicle_merkle_tree_get_proof",
        "icicle_merkle_tree_verify", "icicle_merkle_proof_delete", "icicle_merkle_proof_is_pruned"]
+    + ["icicle_hip_merkle_tree_get_proofs", "icicle_hip_merkle_tree_verify_batch"]
     + ["proof_of_work", "proof_of_work_verify"]
     + [f"{p}_{s}" for p in FRI_PREFIXES + FRI_WIDE_PREFIXES for s in FRI_FUNCTIONS]
     + [f"{p}_{s}" for p in SUMCHECK_FIELDS for s in SUMCHECK_FUNCTIONS] + ["delete_program", "icicle_hip_sumcheck_time_rounds", "icicle_hip_sumcheck_round_times"]
@@ -480,6 +481,9 @@ lib.icicle_merkle_tree_get_root.argtypes = [ctypes.c_void_p, _size_p]
 lib.icicle_merkle_tree_get_proof.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_uint64, ctypes.c_bool,
                                              ctypes.POINTER(MerkleTreeConfig), ctypes.c_void_p]
 lib.icicle_merkle_tree_verify.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.POINTER(ctypes.c_bool)]
+lib.icicle_hip_merkle_tree_get_proofs.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64, ctypes.POINTER(ctypes.c_uint64), ctypes.c_uint64, ctypes.c_bool,
+                                                  ctypes.POINTER(MerkleTreeConfig), ctypes.POINTER(ctypes.c_void_p)]
+lib.icicle_hip_merkle_tree_verify_batch.argtypes = [ctypes.c_void_p, ctypes.POINTER(ctypes.c_void_p), ctypes.c_uint64, ctypes.POINTER(ctypes.c_bool)]
 lib.icicle_merkle_proof_create.argtypes = []
 lib.icicle_merkle_proof_create_with_data.argtypes = [ctypes.c_bool, ctypes.c_int64, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p, ctypes.c_size_t,
                                                      ctypes.c_void_p, ctypes.c_size_t]

@@ -1,5 +1,6 @@
 // The FRI protocol over any field kind: the proof object, the prover and the verifier of the reference's C ABI
-// (src/fri/fri_c_api.cpp), composed from what hash.hip provides, and the macro that defines a prefix's entry points. Included by
+// (src/fri/fri_c_api.cpp), composed from what hash.hip provides -- the query phase and the verifier on its batched openings and
+// verification, one call per round --, and the macro that defines a prefix's entry points. Included by
 // fri.hip (the 31-bit fields) and fri_wide.hip (Goldilocks, the 256-bit fields), which supply the field kind K:
 //
 //   K::WORDS                                      uint32 words of one element in memory (canonical, little-endian)
@@ -214,17 +215,19 @@ namespace icicle_hip {
     // query phase
     ICICLE_TRY(transcript_hash(tc->hasher, transcript.query_input(cfg->pow_bits != 0, reinterpret_cast<const uint8_t*>(alpha), EB, nonce), st, &digest));
     const std::vector<uint64_t> queries = fri_draw_queries(digest.data(), cfg->nof_queries, plan.final_size, plan.n);
+    // one batch of openings per round: the round's 2 * nof_queries leaf indices in slot order (query, symmetric)
     FriProofObj fresh;
     fresh.slots.assign(2 * queries.size(), std::vector<icicle_merkle_proof_handle_t>(plan.rounds, nullptr));
-    for (size_t j = 0; j < queries.size(); j++)
-      for (uint32_t r = 0; r < plan.rounds; r++)
-        for (int sym = 0; sym < 2; sym++) {
-          icicle_merkle_proof_handle_t mp = icicle_merkle_proof_create();
-          if (!mp) return ICICLE_ALLOCATION_FAILED;
-          fresh.slots[2 * j + sym][r] = mp;
-          ICICLE_TRY(icicle_merkle_tree_get_proof(trees[r].h, reinterpret_cast<const uint8_t*>(layer[r]), plan.round_size(r) * EB,
-                                                  fri_leaf_index(queries[j], plan.round_size(r), sym != 0), false, &mc, mp));
-        }
+    std::vector<uint64_t> indices(2 * queries.size());
+    std::vector<icicle_merkle_proof_handle_t> opened(2 * queries.size());
+    for (uint32_t r = 0; r < plan.rounds; r++) {
+      for (size_t s = 0; s < opened.size(); s++) {
+        if (!(opened[s] = fresh.slots[s][r] = icicle_merkle_proof_create())) return ICICLE_ALLOCATION_FAILED;
+        indices[s] = fri_leaf_index(queries[s / 2], plan.round_size(r), (s & 1) != 0);
+      }
+      ICICLE_TRY(icicle_hip_merkle_tree_get_proofs(trees[r].h, reinterpret_cast<const uint8_t*>(layer[r]), plan.round_size(r) * EB, indices.data(), indices.size(), false,
+                                                   &mc, opened.data()));
+    }
     HIP_TRY(hipStreamSynchronize(st), ICICLE_SYNCHRONIZATION_FAILED);
     proof->clear();
     proof->slots.swap(fresh.slots);
@@ -301,6 +304,23 @@ namespace icicle_hip {
     std::vector<TreeHandle> trees(rounds);
     for (uint32_t r = 0; r < rounds; r++)
       if (!trees[r].create(leaves, compress, plan.tree_layers(r), EB, 0)) return ICICLE_INVALID_ARGUMENT;
+    // every Merkle proof of a round in one batch; a proof that does not fit the tree's shape (INVALID_ARGUMENT) is a wrong proof.
+    // A batch shares one pruned flag, so a proof object that mixes pruned and full openings takes one batch per flag.
+    std::vector<icicle_merkle_proof_handle_t> batch;
+    std::vector<uint8_t> batch_ok; // bool, with an address
+    for (uint32_t r = 0; r < rounds; r++)
+      for (int flag = 0; flag < 2; flag++) {
+        batch.clear();
+        for (const auto& q : proof->slots)
+          if (icicle_merkle_proof_is_pruned(q[r]) == (flag != 0)) batch.push_back(q[r]);
+        if (batch.empty()) continue;
+        batch_ok.assign(batch.size(), 0);
+        const icicle_error_t e = icicle_hip_merkle_tree_verify_batch(trees[r].h, batch.data(), batch.size(), reinterpret_cast<bool*>(batch_ok.data()));
+        if (e == ICICLE_INVALID_ARGUMENT) return ICICLE_SUCCESS;
+        ICICLE_TRY(e);
+        for (uint8_t ok : batch_ok)
+          if (!ok) return ICICLE_SUCCESS;
+      }
     for (size_t j = 0; j < queries.size(); j++)
       for (uint32_t r = 0; r < rounds; r++) {
         const uint64_t size = plan.round_size(r), idx = fri_leaf_index(queries[j], size, false), idx_sym = fri_leaf_index(queries[j], size, true);
@@ -308,11 +328,6 @@ namespace icicle_hip {
         const uint8_t* leaf[2];
         uint64_t leaf_idx[2];
         for (int s = 0; s < 2; s++) {
-          bool ok = false;
-          const icicle_error_t e = icicle_merkle_tree_verify(trees[r].h, mp[s], &ok);
-          if (e == ICICLE_INVALID_ARGUMENT) return ICICLE_SUCCESS; // a proof that does not fit the tree's shape
-          ICICLE_TRY(e);
-          if (!ok) return ICICLE_SUCCESS;
           size_t leaf_size = 0;
           leaf[s] = icicle_merkle_proof_get_leaf(mp[s], &leaf_size, &leaf_idx[s]);
           if (!leaf[s] || leaf_size != EB) return ICICLE_SUCCESS;

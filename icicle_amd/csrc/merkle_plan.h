@@ -1,6 +1,6 @@
 // Host-only arithmetic of the Merkle tree (hash.hip): layer counts, padding extents, the sub-tree a proof recomputes and the
 // byte offsets of a proof's path. No HIP in here, so tests/merkle_plan_harness.cpp compiles it with g++ and compares it with
-// the Python model (tests/merkle_model.py).
+// the Python model (tests/merkle_model.py). The same arithmetic for batched openings, as one host-and-device function, is merkle_batch.h.
 //
 // Notation (reference: icicle/backend/cpu/src/hash/cpu_merkle_tree.cpp:18-51): layer i hashes n_i chunks of c_i bytes into
 // digests of o_i bytes; c_{i+1} % o_i == 0 ("each layer output size must divide the next layer input size"), the arity of

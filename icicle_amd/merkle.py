@@ -1,5 +1,6 @@
 """Merkle trees on the device: mirror of wrappers/rust/icicle-core/src/merkle (MerkleTree, MerkleProof, MerkleTreeConfig,
-PaddingPolicy) over icicle_merkle_tree_* / icicle_merkle_proof_* (include/icicle_hip.h)."""
+PaddingPolicy) over icicle_merkle_tree_* / icicle_merkle_proof_* (include/icicle_hip.h), and this backend's batched openings and verification
+(MerkleTree.proofs, MerkleTree.verify_batch)."""
 import ctypes
 
 import numpy as np
@@ -110,6 +111,25 @@ class MerkleTree:
         ok = ctypes.c_bool(False)
         check(lib.icicle_merkle_tree_verify(self.handle, proof.handle, ctypes.byref(ok)), "icicle_merkle_tree_verify")
         return bool(ok.value)
+
+    def proofs(self, leaves, leaf_indices, pruned=False, cfg=None, size=None) -> list:
+        """one MerkleProof per index, each as proof() returns it, from one call (icicle_hip_merkle_tree_get_proofs): the indices
+        may repeat and come in any order"""
+        cfg = cfg or MerkleTreeConfig.default()
+        ptr, cfg.is_leaves_on_device, size = _leaves(leaves, size)
+        idx = [int(i) for i in leaf_indices]
+        out = [MerkleProof() for _ in idx]
+        check(lib.icicle_hip_merkle_tree_get_proofs(self.handle, ptr, size, (ctypes.c_uint64 * len(idx))(*idx), len(idx), pruned, ctypes.byref(cfg),
+                                                    (ctypes.c_void_p * len(idx))(*[p.handle for p in out])), "icicle_hip_merkle_tree_get_proofs")
+        return out
+
+    def verify_batch(self, proofs) -> list:
+        """verify() of every proof, from one call (icicle_hip_merkle_tree_verify_batch); all pruned or all full"""
+        proofs = list(proofs)
+        ok = (ctypes.c_bool * len(proofs))()
+        check(lib.icicle_hip_merkle_tree_verify_batch(self.handle, (ctypes.c_void_p * len(proofs))(*[p.handle for p in proofs]), len(proofs), ok),
+              "icicle_hip_merkle_tree_verify_batch")
+        return [bool(v) for v in ok]
 
     def close(self):
         if self.handle is not None:

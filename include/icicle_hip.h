@@ -374,6 +374,28 @@ const uint8_t* icicle_merkle_proof_get_path(icicle_merkle_proof_handle_t proof, 
 const uint8_t* icicle_merkle_proof_get_leaf(icicle_merkle_proof_handle_t proof, size_t* out_size, uint64_t* out_leaf_idx); /* :56 */
 const uint8_t* icicle_merkle_proof_get_root(icicle_merkle_proof_handle_t proof, size_t* out_size); /* :66 */
 
+/* ---- this backend's own: many openings, many verifications per call (the reference has no such call) ----
+ * get_proofs: proofs[i] comes out byte for byte as icicle_merkle_tree_get_proof(tree, leaves, leaves_size, leaf_indices[i], is_pruned,
+ * config, proofs[i]) leaves it, for every configuration that call accepts. leaf_indices is a host array, in any order, repeats
+ * allowed; proofs are `count` handles of icicle_merkle_proof_create. With the stored layers in device memory ONE kernel gathers the
+ * on-path groups of all proofs (and, for device leaves, the leaf chunks and the LastValue element) into count staging records,
+ * which come back in one copy into pinned memory behind the one synchronisation of config->stream (is_async or not); pieces that
+ * live on the host (a tree in pinned memory, host leaves) are copied on the host. Launches, copies and synchronisations do not
+ * grow with count; with output_store_min_layer > 0 the layers below it are re-hashed once per DISTINCT sub-tree among the indices.
+ * NULL tree, config, leaves, leaf_indices, proofs or proofs[i]: INVALID_POINTER. A tree not built, leaves the tree's build would refuse,
+ * any index at or beyond the capacity, count * (bytes of one proof's pieces) beyond 2^40: INVALID_ARGUMENT. Both before the device is touched,
+ * and with every proof object untouched. count == 0: SUCCESS, nothing done. */
+icicle_error_t icicle_hip_merkle_tree_get_proofs(icicle_merkle_tree_handle_t tree, const uint8_t* leaves, uint64_t leaves_size, const uint64_t* leaf_indices, uint64_t count,
+                                                 bool is_pruned, const icicle_merkle_tree_config_t* config, icicle_merkle_proof_handle_t* proofs);
+/* valid[i] = what icicle_merkle_tree_verify(tree, proofs[i], &v) would set. One upload of all proofs' layer inputs, one hash launch
+ * per layer over all proofs (layer 0: one per distinct leaf size), pruned proofs' digests scattered into the next layer's inputs by
+ * one launch per layer, one copy back, one synchronisation (the null stream, as the single call); the comparisons run on the host.
+ * All proofs share one pruned flag: a mix is INVALID_ARGUMENT. Where the single call returns an error for some proof (an empty leaf,
+ * a path of the wrong size, leaf_idx * leaf_element_size beyond 64 bits) the batch returns the first such error in index order and
+ * every valid[i] is false. A root of the wrong size makes that one proof invalid. NULL tree, proofs, valid or proofs[i]:
+ * INVALID_POINTER. count == 0: SUCCESS. The tree need not be built. */
+icicle_error_t icicle_hip_merkle_tree_verify_batch(icicle_merkle_tree_handle_t tree, const icicle_merkle_proof_handle_t* proofs, uint64_t count, bool* valid);
+
 /* ---- proof of work: include/icicle/hash/pow.h:16-87 (PowConfig, 32 bytes; proof_of_work, proof_of_work_verify), semantics
  * backend/cpu/src/hash/cpu_pow.cpp. `const Hash&` and the `bool&` / `uint64_t&` results cross the ABI as pointers
  * (wrappers/rust/icicle-hash/src/pow.rs:28-53). The message of nonce n is challenge[0, challenge_size) | n as 8 little-endian
@@ -412,7 +434,7 @@ icicle_error_t proof_of_work_verify(icicle_hasher_handle_t hasher, const uint8_t
  * log2(n) - r layers of the compress hasher --, hashes the transcript with icicle_hasher_hash, and folds with the challenge:
  *   out[i] = (e[i] + e[i+h])/2 + alpha * ((e[i] - e[i+h])/2 * w_n^(-i)),  h = n/2,  w_n^(-i) from the initialised NTT domain.
  * The last fold's output is the final polynomial; proof_of_work (default config) grinds pow_bits; the query phase opens
- * q % (n>>r) and its symmetric position (q + (n>>r)/2) % (n>>r) in every round with icicle_merkle_tree_get_proof, not pruned.
+ * q % (n>>r) and its symmetric position (q + (n>>r)/2) % (n>>r) in every round, not pruned, with ONE icicle_hip_merkle_tree_get_proofs per round.
  * Queries come from a hand-written MT19937 seeded with the low 32 bits of the transcript digest (icicle_amd/csrc/fri_plan.h), so a
  * proof does not depend on the C++ library. A proof stores 2 * nof_queries slots (query, symmetric); get_nof_queries returns that
  * doubled number. The MerkleProof handles of get_round_proofs_for_query are borrowed from the proof and work with
@@ -424,8 +446,8 @@ icicle_error_t proof_of_work_verify(icicle_hasher_handle_t hasher, const uint8_t
  * (proof_of_work's range). A domain that is missing or smaller than input_size: INVALID_ARGUMENT. NULL config, transcript, hasher,
  * seed, input or proof: INVALID_POINTER. The caller keeps the domain alive (no ntt_release_domain) until prove has returned.
  * `stream` is honoured, is_async accepted; prove returns with the stream drained (the proof is host data), as proof_of_work does.
- * verify: final-polynomial length, alphas from the proof's roots, proof of work, then per query and round both Merkle proofs
- * (icicle_merkle_tree_verify), leaf indices, collinearity with w_n^(-1) from the field's own root of unity. The argument errors above
+ * verify: final-polynomial length, alphas from the proof's roots, proof of work, then per round all Merkle proofs
+ * (one icicle_hip_merkle_tree_verify_batch), then per query and round leaf indices, collinearity with w_n^(-1) from the field's own root of unity. The argument errors above
  * that concern the configuration and the hashers are errors in verify too; everything about the proof itself -- its final polynomial's
  * length, a number of slots other than 2 * nof_queries, rounds that differ between slots, a size 2^rounds * final size that does not
  * fit nof_queries, words at or above p -- makes a wrong proof: *valid = false with SUCCESS. Stricter than the reference in one point:

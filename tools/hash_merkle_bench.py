@@ -9,13 +9,18 @@ batch hash of 2^22 x 64 B in the same interleaved rounds, both as time per hash,
 at --pow-bits by nonces per launch (--pow-span-log2).
 --fri times the FRI prover (--field, default the BabyBear extension; Blake2s trees and transcript, default config: 16 proof-of-work
 bits, 100 queries) at --fri-log-n sizes from a device input: the whole fri_merkle_tree_prove, and its stages run one by one through the public API on the
-same layers -- the tree builds, the folds, the proof of work, the 2 x queries x rounds get_proof calls of the query phase --, then the
+same layers -- the tree builds, the folds, the proof of work, the query phase as one batch of openings per round (MerkleTree.proofs) and,
+beside it, the same openings as 2 x queries x rounds get_proof calls --, the whole fri_merkle_tree_verify of the proof, then the
 first fold's bytes per second (n + n/2 elements and n/2 twiddles of the field's table) beside a device-to-device copy that moves the same byte count, in
 interleaved rounds of the same run.
+--openings times batched Merkle openings and verification against loops of single calls for the same indices (--open-counts, default
+200 and 4000 random indices with repeats) on a Blake2s tree over 2^--open-log-leaves 16-byte leaves kept on the device: MerkleTree.proofs
+beside a loop of MerkleTree.proof, MerkleTree.verify_batch beside a loop of MerkleTree.verify, in interleaved rounds.
 usage: tools/hash_merkle_bench.py [--hash keccak256 [blake2s blake3]] [--log-batch 22] [--log-leaves 22 10] [--top-max 0 256 1024] [--reps 5]
        tools/hash_merkle_bench.py --pow [--hash keccak256 blake2s blake3] [--reps 9] [--pow-bits 20 25 30] [--pow-span-log2 24 28 32]
        tools/hash_merkle_bench.py --fri [--field babybear_extension|goldilocks|goldilocks_extension|stark252|bn254|bls12_381|bls12_377]
-                                        [--fri-log-n 20 24] [--reps 5]"""
+                                        [--fri-log-n 20 24] [--reps 5]
+       tools/hash_merkle_bench.py --openings [--open-log-leaves 20] [--open-counts 200 4000] [--reps 5]"""
 import argparse
 import ctypes
 import os
@@ -163,18 +168,31 @@ def fri_bench(a):
         picks = [int(q) for q in rng.integers(1, n + 1, queries)]
 
         def query_phase():
+            for r in range(rounds):
+                size = n >> r
+                for pr in trees[r].proofs(layers[r], [i for q in picks for i in (q % size, (q + size // 2) % size)], False, mcfg):
+                    pr.close()
+
+        def query_phase_single_calls():
             for q in picks:
                 for r in range(rounds):
                     size = n >> r
                     for idx in (q % size, (q + size // 2) % size):
                         trees[r].proof(layers[r], idx, False, mcfg).close()
 
+        proof = icicle_amd.fri_merkle_tree_prove(field, cfg, tc, d_x, lh, ch, 0, extension=ext)
+
+        def verify():
+            assert icicle_amd.fri_merkle_tree_verify(field, cfg, tc, proof, lh, ch, extension=ext)
+
         folds()
-        st = all_interleaved([builds, folds, lambda: icicle_amd.pow_solve(th, challenge, cfg.pow_bits), query_phase], a.reps)
+        st = all_interleaved([builds, folds, lambda: icicle_amd.pow_solve(th, challenge, cfg.pow_bits), query_phase, query_phase_single_calls, verify], a.reps)
         print(f"fri prove {a.field} 2^{logn}, blake2s, {cfg.pow_bits} pow bits, {queries} queries, {rounds} rounds, device input: median {med(total):.3f} ms "
               f"({total[0]:.3f} .. {total[-1]:.3f}) of {a.reps}")
-        for label, t in zip(("tree builds", "folds", "proof of work", f"query phase ({2 * queries * rounds} get_proof calls)"), st):
+        for label, t in zip(("tree builds", "folds", "proof of work", f"query phase ({rounds} get_proofs calls of {2 * queries} openings)"), st):
             print(f"fri stage 2^{logn} {label}: median {med(t):.3f} ms ({t[0]:.3f} .. {t[-1]:.3f}), {100 * med(t) / med(total):.0f}% of the prove")
+        print(f"fri 2^{logn} the same openings as {2 * queries * rounds} get_proof calls (not part of the prove): median {med(st[4]):.3f} ms ({st[4][0]:.3f} .. {st[4][-1]:.3f})")
+        print(f"fri verify {a.field} 2^{logn}: median {med(st[5]):.3f} ms ({st[5][0]:.3f} .. {st[5][-1]:.3f}) of {a.reps}")
         # the first fold against a copy of the same byte count: n + n/2 elements and n/2 twiddles
         moved = eb * n + eb * n // 2 + 4 * tw_words * n // 2
         d_src, d_dst = DeviceVec(moved // 2), DeviceVec(moved // 2)
@@ -195,8 +213,51 @@ def fri_bench(a):
         ntt.release_domain(field)
 
 
+def openings_bench(a):
+    from icicle_amd import MerkleTreeConfig, runtime
+    from icicle_amd.hash import Hasher
+    from icicle_amd.merkle import MerkleTree
+    from icicle_amd.runtime import DeviceVec
+
+    runtime.set_device(0)
+    rng = np.random.default_rng(1)
+    logl, eb = a.open_log_leaves, 16
+    n = 1 << logl
+    d_leaves = DeviceVec.from_host(rng.integers(0, 256, eb * n, dtype=np.uint8))
+    cfg = MerkleTreeConfig.default()
+    cfg.is_tree_on_device = True
+    tree = MerkleTree([Hasher.blake2s(eb)] + [Hasher.blake2s(64)] * logl, eb).build(d_leaves, cfg=cfg)
+    med = lambda t: t[len(t) // 2]
+    for count in a.open_counts:
+        indices = [int(v) for v in rng.integers(0, n, count)]
+        for pruned in (False, True):
+            proofs = tree.proofs(d_leaves, indices, pruned, cfg)
+            assert tree.verify_batch(proofs) == [True] * count
+
+            def batch():
+                for pr in tree.proofs(d_leaves, indices, pruned, cfg):
+                    pr.close()
+
+            def singles():
+                for i in indices:
+                    tree.proof(d_leaves, i, pruned, cfg).close()
+
+            def verify_singles():
+                assert all(tree.verify(pr) for pr in proofs)
+
+            ts = all_interleaved([batch, singles, lambda: tree.verify_batch(proofs), verify_singles], a.reps)
+            kind = "pruned" if pruned else "full"
+            for label, b, s in (("get_proofs", ts[0], ts[1]), ("verify_batch", ts[2], ts[3])):
+                print(f"openings blake2s 2^{logl} x {eb} B leaves, {count} indices, {kind}: {label} median {med(b):.3f} ms ({b[0]:.3f} .. {b[-1]:.3f}) | "
+                      f"{count} single calls median {med(s):.3f} ms ({s[0]:.3f} .. {s[-1]:.3f}) | single / batch {med(s) / med(b):.1f}")
+    tree.close()
+
+
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--openings", action="store_true")
+    ap.add_argument("--open-log-leaves", type=int, default=20)
+    ap.add_argument("--open-counts", type=int, nargs="*", default=[200, 4000])
     ap.add_argument("--fri", action="store_true")
     ap.add_argument("--fri-log-n", type=int, nargs="*", default=[20, 24])
     ap.add_argument("--field", default="babybear_extension",
@@ -214,6 +275,8 @@ def main():
         return pow_bench(a)
     if a.fri:
         return fri_bench(a)
+    if a.openings:
+        return openings_bench(a)
     import icicle_amd
     from icicle_amd import runtime
     from icicle_amd._lib import lib
