@@ -5,9 +5,11 @@ the thin host-side mirror of the reference's wrapper API (wrappers/rust/icicle-c
 icicle-runtime) used by the tests and bench.py. There is no CPU fallback anywhere in here.
 """
 from ._lib import IcicleError, Device, MSMConfig, NTTConfigU32, NTTConfigU64, NTTConfigU256, NTTInitDomainConfig, VecOpsConfig, HashConfig, MerkleTreeConfig, PowConfig, FriConfig, SumcheckConfig, lib, LIB_PATH  # noqa: F401
-from . import runtime, msm, ntt, vecops, hash, merkle, fri, sumcheck  # noqa: F401
+from . import runtime, msm, ntt, vecops, hash, merkle, fri, sumcheck, program  # noqa: F401
 from .pow import pow_solve, pow_verify  # noqa: F401
 from .fri import FriTranscriptConfig, FriProof, fri_merkle_tree_prove, fri_merkle_tree_verify  # noqa: F401
 from .sumcheck import Symbol, ReturningValueProgram, SumcheckTranscriptConfig, Sumcheck, SumcheckProof  # noqa: F401
+from .program import Program  # noqa: F401
+from .vecops import execute_program  # noqa: F401
 
-__all__ = ["runtime", "msm", "ntt", "vecops", "hash", "merkle", "fri", "sumcheck", "Symbol", "ReturningValueProgram", "SumcheckConfig", "SumcheckTranscriptConfig", "Sumcheck", "SumcheckProof", "pow_solve", "pow_verify", "FriConfig", "FriTranscriptConfig", "FriProof", "fri_merkle_tree_prove", "fri_merkle_tree_verify", "HashConfig", "MerkleTreeConfig", "PowConfig", "VecOpsConfig", "IcicleError", "Device", "MSMConfig", "NTTConfigU32", "NTTConfigU64", "NTTConfigU256", "NTTInitDomainConfig"]
+__all__ = ["runtime", "msm", "ntt", "vecops", "hash", "merkle", "fri", "sumcheck", "program", "Symbol", "ReturningValueProgram", "Program", "execute_program", "SumcheckConfig", "SumcheckTranscriptConfig", "Sumcheck", "SumcheckProof", "pow_solve", "pow_verify", "FriConfig", "FriTranscriptConfig", "FriProof", "fri_merkle_tree_prove", "fri_merkle_tree_verify", "HashConfig", "MerkleTreeConfig", "PowConfig", "VecOpsConfig", "IcicleError", "Device", "MSMConfig", "NTTConfigU32", "NTTConfigU64", "NTTConfigU256", "NTTInitDomainConfig"]

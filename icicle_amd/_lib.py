@@ -315,6 +315,8 @@ SUMCHECK_FIELDS = {"babybear": 1, "koalabear": 1, "bn254": 8, "bls12_381": 8}
 SUMCHECK_FUNCTIONS = ["sumcheck_delete", "hip_sumcheck_prove", "sumcheck_verify", "sumcheck_proof_get_poly_sizes", "sumcheck_proof_delete",
                       "sumcheck_get_challenge_vector", "sumcheck_get_challenge_size", "generate_returning_value_program", "add_symbols", "sub_symbols",
                       "multiply_symbols", "inverse_symbol"]
+# execute_program and the general program (src/vec_ops.cpp:566, src/program/program_c_api.cpp:48): the functions that return an error code
+PROGRAM_FUNCTIONS = ["generate_program", "execute_program"]
 API_SYMBOLS = (
     [f"{c}_{s}" for c in CURVES for s in ("msm", "msm_precompute_bases", "hip_generate_affine_points", "hip_projective_sum")]
     + [f"{c}_g2_{s}" for c in G2_CURVES for s in ("msm", "msm_precompute_bases", "hip_generate_affine_points", "hip_projective_sum")]
@@ -351,6 +353,7 @@ API_SYMBOLS = (
     + ["proof_of_work", "proof_of_work_verify"]
     + [f"{p}_{s}" for p in FRI_PREFIXES + FRI_WIDE_PREFIXES for s in FRI_FUNCTIONS]
     + [f"{p}_{s}" for p in SUMCHECK_FIELDS for s in SUMCHECK_FUNCTIONS] + ["delete_program", "icicle_hip_sumcheck_time_rounds", "icicle_hip_sumcheck_round_times"]
+    + [f"{p}_{s}" for p in SUMCHECK_FIELDS for s in PROGRAM_FUNCTIONS]
 )
 # hash / Merkle functions that return a handle, a size or a byte pointer (tests/test_abi.py's header scan sees only the return types
 # of the lists above; tests/test_hash_cpu.py checks these against the header with a scan of its own): name -> restype
@@ -372,6 +375,8 @@ FRI_HANDLE_SYMBOLS = {f"{p}_{s}": ctypes.c_void_p for p in FRI_PREFIXES + FRI_WI
 SUMCHECK_HANDLE_SYMBOLS = {f"{p}_{s}": ctypes.c_void_p for p in SUMCHECK_FIELDS
                            for s in ("sumcheck_create", "sumcheck_get_proof", "sumcheck_proof_create", "sumcheck_proof_get_round_poly_at",
                                      "create_predefined_returning_value_program", "create_input_symbol", "create_scalar_symbol", "copy_symbol")}
+# program_c_api.cpp:35: name -> restype
+PROGRAM_HANDLE_SYMBOLS = {f"{p}_create_predefined_program": ctypes.c_void_p for p in SUMCHECK_FIELDS}
 
 if not os.path.exists(LIB_PATH):
     raise ImportError(
@@ -543,6 +548,10 @@ for _p in SUMCHECK_FIELDS:
     for _s in ("add_symbols", "sub_symbols", "multiply_symbols"):
         getattr(lib, f"{_p}_{_s}").argtypes = [ctypes.c_void_p, ctypes.c_void_p, _void_pp]
     getattr(lib, f"{_p}_inverse_symbol").argtypes = [ctypes.c_void_p, _void_pp]
+    getattr(lib, f"{_p}_create_predefined_program").restype = PROGRAM_HANDLE_SYMBOLS[f"{_p}_create_predefined_program"]
+    getattr(lib, f"{_p}_create_predefined_program").argtypes = [ctypes.c_int]
+    getattr(lib, f"{_p}_generate_program").argtypes = [_void_pp, ctypes.c_int, _void_pp]
+    getattr(lib, f"{_p}_execute_program").argtypes = [_void_pp, ctypes.c_uint64, ctypes.c_void_p, ctypes.c_uint64, ctypes.POINTER(VecOpsConfig)]
 
 
 def multi_stats(reset=False):

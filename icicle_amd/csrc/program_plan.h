@@ -84,10 +84,11 @@ namespace icicle_hip {
   {
   public:
     // params: the inputs' symbols followed by the return value's. false: an input index outside the inputs, a constant of another
-    // width, or more than 255 variables
-    bool run(const std::vector<SymRef>& params, int words, CompiledProgram* out)
+    // width, or more than 255 variables. general: a program with any number of outputs (program.h), in which every parameter is
+    // an input as well; the instruction list is made the same way.
+    bool run(const std::vector<SymRef>& params, int words, CompiledProgram* out, bool general = false)
     {
-      m_out = out, m_words = words, m_ok = true;
+      m_out = out, m_words = words, m_ok = true, m_general = general;
       *out = CompiledProgram{};
       out->nof_parameters = (int)params.size();
       if (params.empty()) return false;
@@ -122,7 +123,7 @@ namespace icicle_hip {
         m_out->constants.push_back(n->constant);
         m_var[n.get()] = m_out->nof_parameters + m_out->nof_constants++;
       } else if (n->op == PROG_INPUT) {
-        if (n->input_idx < 0 || n->input_idx >= m_out->nof_inputs()) m_ok = false;
+        if (n->input_idx < 0 || n->input_idx >= (m_general ? m_out->nof_parameters : m_out->nof_inputs())) m_ok = false;
         m_var[n.get()] = n->input_idx;
       }
     }
@@ -144,7 +145,7 @@ namespace icicle_hip {
     }
     CompiledProgram* m_out = nullptr;
     int m_words = 1;
-    bool m_ok = true;
+    bool m_ok = true, m_general = false;
     std::map<SymNode*, int> m_var;
     std::set<SymNode*> m_seen;
   };

@@ -19,6 +19,7 @@
 #include "smallfield.hpp"
 #include "bigfield.hpp"
 #include "sumcheck_plan.h"
+#include "program_device.hpp"
 #include <atomic>
 #include <cstring>
 #include <memory>
@@ -27,83 +28,11 @@
 
 namespace icicle_hip {
 
-#define SC_D __device__ __forceinline__
-#define SC_HD __host__ __device__ __forceinline__
-
   constexpr int SC_BLOCK = 128;        // lanes of a round block (predefined programs)
   constexpr int SC_INTERP_BLOCK = 64;  // one wave: the variable file of a user program lives in LDS
   constexpr unsigned SC_MAX_GRID = 2048;
   constexpr int SC_MAX_ACC = PROG_MAX_DEGREE + 1;
   constexpr int SC_MAX_CONSTS = PROG_MAX_VARS - 2;
-
-  // ---- the two kinds of field behind one interface: elem = what a lane holds, W = words of an element in memory ----
-  template <class PR>
-  struct ScSmall {
-    using S = SmallField<PR>;
-    using elem = uint32_t;
-    static constexpr int W = 1, REGS = 1;
-    static SC_HD elem zero() { return 0; }
-    static SC_HD elem add(elem a, elem b) { return S::add(a, b); }
-    static SC_HD elem sub(elem a, elem b) { return S::sub(a, b); }
-    static SC_HD elem mul(elem a, elem b) { return S::mul(a, b); } // a b / R
-    static SC_HD elem r2() { return PR::R2; }
-    static SC_HD elem mont_one() { return PR::ONE; }
-    static SC_HD elem plain_one() { return 1; }
-    static SC_HD elem load(const uint32_t* w) { return w[0]; }
-    static SC_HD void store(uint32_t* w, elem a) { w[0] = a; }
-    static SC_HD uint32_t& reg(elem& a, int) { return a; }
-    static HostField host_field()
-    {
-      const uint32_t p = PR::P;
-      return HostField(&p, 1);
-    }
-  };
-  // values below 4p between operations (lazy reduction, bigfield.hpp): a product of two such is below 1.25p
-  template <class PR>
-  struct ScBig {
-    using F = FieldOps<PR>;
-    using elem = Fe<PR>;
-    static constexpr int W = 8, REGS = PR::NL;
-    static SC_HD elem zero() { return F::zero(); }
-    static SC_HD elem add(const elem& a, const elem& b)
-    {
-      elem r = F::add(a, b);
-      F::template cond_sub<4>(r);
-      return r;
-    }
-    static SC_HD elem sub(const elem& a, const elem& b)
-    {
-      elem r = F::template sub<4>(a, b);
-      F::template cond_sub<4>(r);
-      return r;
-    }
-    static SC_HD elem mul(const elem& a, const elem& b) { return F::mul(a, b); }
-    static SC_HD elem r2() { return F::r2(); }
-    static SC_HD elem mont_one() { return F::one(); }
-    static SC_HD elem plain_one() { return F::plain_one(); }
-    static SC_HD elem load(const uint32_t* w) { return F::unpack(w); }
-    static SC_HD void store(uint32_t* w, const elem& a) { F::pack(w, F::reduce(a)); }
-    static SC_HD uint32_t& reg(elem& a, int i) { return a.l[i]; }
-    static HostField host_field() { return HostField(PR::P32, 8); }
-  };
-  template <class PR>
-  struct ScFieldOf;
-  template <>
-  struct ScFieldOf<babybear_params> {
-    using type = ScSmall<babybear_params>;
-  };
-  template <>
-  struct ScFieldOf<koalabear_params> {
-    using type = ScSmall<koalabear_params>;
-  };
-  template <>
-  struct ScFieldOf<bn254_fr_params> {
-    using type = ScBig<bn254_fr_params>;
-  };
-  template <>
-  struct ScFieldOf<bls12_381_fr_params> {
-    using type = ScBig<bls12_381_fr_params>;
-  };
 
   struct ScPolys {
     const uint32_t* in[PROG_MAX_INPUTS]; // T_{r-1} (a folding round) or T_0 (round 0), 16-byte aligned
@@ -389,10 +318,6 @@ namespace icicle_hip {
   }
 
   // ---- objects behind the handles ----------------------------------------------------------------------------------------------------
-  struct ProgramObj {
-    int words = 0; // of the field it was made for
-    CompiledProgram prog;
-  };
   struct SymbolObj {
     int words = 0;
     SymRef node;
@@ -439,7 +364,8 @@ namespace icicle_hip {
     *res = symbol_new(words, sym_op(PROG_INV, x->node, nullptr));
     return ICICLE_SUCCESS;
   }
-  static icicle_error_t program_generate(int words, icicle_symbol_handle_t* params, int nof_parameters, icicle_program_handle_t* program)
+  // general: a program with any number of outputs (<field>_generate_program), else the last parameter is the return value
+  static icicle_error_t program_generate(int words, icicle_symbol_handle_t* params, int nof_parameters, icicle_program_handle_t* program, bool general = false)
   {
     if (!params || !program) return ICICLE_INVALID_POINTER;
     *program = nullptr;
@@ -452,7 +378,7 @@ namespace icicle_hip {
     }
     std::unique_ptr<ProgramObj> obj(new ProgramObj);
     obj->words = words;
-    const bool ok = ProgramCompiler().run(nodes, words, &obj->prog);
+    const bool ok = ProgramCompiler().run(nodes, words, &obj->prog, general);
     symbols_release();
     if (!ok) return ICICLE_INVALID_ARGUMENT;
     *program = (icicle_program_handle_t)obj.release();
@@ -807,6 +733,14 @@ extern "C" icicle_error_t delete_program(icicle_program_handle_t program)
   extern "C" icicle_error_t P##_generate_returning_value_program(icicle_symbol_handle_t* parameters, int nof_parameters, icicle_program_handle_t* program)    \
   {                                                                                                                    \
     SC_GUARDED(program_generate(ScFieldOf<PR>::type::W, parameters, nof_parameters, program))                          \
+  }                                                                                                                    \
+  extern "C" icicle_program_handle_t P##_create_predefined_program(int pre_def)                                        \
+  {                                                                                                                    \
+    return P##_create_predefined_returning_value_program(pre_def); /* one object serves both kinds */                 \
+  }                                                                                                                    \
+  extern "C" icicle_error_t P##_generate_program(icicle_symbol_handle_t* parameters, int nof_parameters, icicle_program_handle_t* program)                    \
+  {                                                                                                                    \
+    SC_GUARDED(program_generate(ScFieldOf<PR>::type::W, parameters, nof_parameters, program, true))                    \
   }                                                                                                                    \
   extern "C" icicle_symbol_handle_t P##_create_input_symbol(int in_idx)                                                \
   {                                                                                                                    \

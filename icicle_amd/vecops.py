@@ -114,3 +114,18 @@ def matrix_transpose(field, inp, nof_rows: int, nof_cols: int, cfg=None, out=Non
     name = f"{field}_extension_matrix_transpose" if extension else f"{field}_matrix_transpose"
     check(getattr(lib, name)(ip, nof_rows, nof_cols, ctypes.byref(cfg), op_), name)
     return out
+
+
+def execute_program(field, data, program, cfg=None, size=None):
+    """data: one vector per parameter of `program` (program.Program or sumcheck.ReturningValueProgram), all NumPy uint32 arrays on the
+    host or all on the device (DeviceVec, or an int: a device address, then with `size`); the parameters the program writes are written in place. `size` = elements per batch entry."""
+    cfg = cfg or VecOpsConfig.default()
+    ptrs = [_ptr(d) for d in data]
+    assert ptrs and len({dev for _, dev in ptrs}) == 1, "parameters must be all on the host or all on the device"
+    cfg.is_a_on_device = cfg.is_b_on_device = cfg.is_result_on_device = ptrs[0][1]
+    if size is None:
+        assert not isinstance(data[0], int), "a raw device address has no size: pass size"
+        size = data[0].nbytes // (4 * _WORDS[field]) // max(1, cfg.batch_size)
+    table = (ctypes.c_void_p * len(ptrs))(*[p for p, _ in ptrs])
+    check(getattr(lib, f"{field}_execute_program")(table, len(ptrs), program.handle, size, ctypes.byref(cfg)), f"{field}_execute_program")
+    return data

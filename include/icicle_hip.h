@@ -302,8 +302,10 @@ ICICLE_HIP_DECLARE_TRANSPOSE(stark252, matrix_transpose)
  * SHA3 0x06 .. 0x80. Creating and deleting handles needs no GPU; hashing, build, get_proof and verify run on the device and
  * fail without one. Blake2s-256 and Blake3 hash through the same entry points; the proof-of-work solver and verifier over all six
  * hashers follow the Merkle functions below, and FRI over every field with an NTT, which composes all of them, follows the proof of work;
- * sumcheck, whose transcript hashes through the same entry points, follows FRI.
- * Poseidon, Poseidon2 and proof serialisation (Merkle, FRI and sumcheck) are not built.
+ * sumcheck, whose transcript hashes through the same entry points, follows FRI; execute_program, which runs the same programs over
+ * vectors, follows sumcheck.
+ * Poseidon, Poseidon2, proof serialisation (Merkle, FRI and sumcheck) and the extension_ / rns_ variants of execute_program are not
+ * built.
  * ====================================================================================== */
 typedef struct {
   icicleStreamHandle stream;      /* 0  */
@@ -596,6 +598,33 @@ ICICLE_HIP_DECLARE_SUMCHECK(bls12_381)
  * copies the last proof's times (milliseconds, at most `capacity` of them) and stores the number of rounds it has in *rounds */
 icicle_error_t icicle_hip_sumcheck_time_rounds(bool enable);
 icicle_error_t icicle_hip_sumcheck_round_times(double* ms, int capacity, int* rounds);
+
+/* ---- execute_program: include/icicle/vec_ops.h:404, src/vec_ops.cpp:566, src/program/program_c_api.cpp:35, :48. Over the fields that
+ * have the symbol functions above. A program has nof_parameters parameters, each a vector of size * batch_size canonical elements
+ * (columns_batch changes nothing: the operation is element-wise); any of them may be read, written or both.
+ * <field>_create_predefined_program(pre_def): AB_MINUS_C (id 0: parameters A, B, C and the output A B - C) or EQ_X_AB_MINUS_C (id 1:
+ * A, B, C, E and the output E (A B - C)); NULL for any other id. <field>_generate_program(parameters, nof_parameters, &program):
+ * parameters[i] is the symbol whose value parameter i has afterwards -- the input symbol i itself for a parameter the program leaves
+ * alone. It frees all symbols made so far; delete_program deletes both kinds of program, and execute_program accepts both.
+ * Per element: the variables are the parameters' values, then the constants, then the intermediates; the instructions run in the
+ * reference's order (parameters in order, each subtree in post-order, operand 1 before operand 2, a COPY where a parameter's node
+ * already lives elsewhere); every parameter an instruction wrote is stored back. A parameter read after it was overwritten sees the
+ * new value. inverse(0) = 0. One launch per call; a parameter the program does not read is not loaded, one it does not write is not
+ * stored, and with host data only those are copied. config->is_a_on_device governs every pointer in data; stream and is_async as
+ * in the other vector operations. A pointer may be passed for two parameters (all loads of an element precede its stores);
+ * partial overlap is undefined.
+ * Before the device is touched: INVALID_POINTER for a NULL program, config, data or data[i]; INVALID_ARGUMENT for nof_params other
+ * than the program's, a program of a field of another element size, and a program with more values alive at once, constants
+ * included, than the variable file holds: 64 for the one-word fields, 24 for the eight-word ones. size = 0: SUCCESS.
+ * The extension_ and rns_ variants and the other fields are not built. ---- */
+#define ICICLE_HIP_DECLARE_EXECUTE_PROGRAM(P)                                                                          \
+  icicle_program_handle_t P##_create_predefined_program(int pre_def);                                                  \
+  icicle_error_t P##_generate_program(icicle_symbol_handle_t* parameters, int nof_parameters, icicle_program_handle_t* program); \
+  icicle_error_t P##_execute_program(void** data, uint64_t nof_params, icicle_program_handle_t program, uint64_t size, const icicle_vec_ops_config_t* config);
+ICICLE_HIP_DECLARE_EXECUTE_PROGRAM(babybear)
+ICICLE_HIP_DECLARE_EXECUTE_PROGRAM(koalabear)
+ICICLE_HIP_DECLARE_EXECUTE_PROGRAM(bn254)
+ICICLE_HIP_DECLARE_EXECUTE_PROGRAM(bls12_381)
 
 /* ---- backend-specific helpers (not part of the reference ABI) ---- */
 const char* icicle_hip_version(void);
