@@ -334,7 +334,7 @@ API_SYMBOLS = (
        for op in ("vector_add", "vector_sub", "vector_mul", "scalar_mul_vec", "scalar_add_vec", "scalar_sub_vec", "bit_reverse")]
     + [f"{pre}{f}_matrix_transpose" for pre in ("", "icicle_hip_") for f in NTT_FIELDS + BIG_VEC_FIELDS + [GOLD]]
     + [f"{pre}{f}_extension_matrix_transpose" for pre in ("", "icicle_hip_") for f in NTT_FIELDS + [GOLD]]
-    + ["icicle_hip_msm_plan", "icicle_hip_msm_plan_info", "icicle_hip_version", "icicle_hip_kernel_timing", "icicle_hip_enable_kernel_timing", "icicle_hip_set_device",
+    + ["icicle_hip_msm_plan", "icicle_hip_msm_plan_info", "icicle_hip_ecntt_plan_info", "icicle_hip_version", "icicle_hip_kernel_timing", "icicle_hip_enable_kernel_timing", "icicle_hip_set_device",
        "icicle_hip_ubench_mixed_add", "icicle_hip_ubench_gather", "icicle_hip_ubench_ntt_pass", "icicle_hip_selftest_inplace_products", "icicle_hip_selftest_quad_group_ops", "icicle_hip_release_workspace", "icicle_hip_workspace_bytes",
        "icicle_hip_msm_release_resident_bases", "icicle_hip_multi_stats", "icicle_hip_multi_stats2", "icicle_hip_collectives_info", "icicle_hip_test_set_virtual_devices", "icicle_hip_test_set_no_peer_access",
        "icicle_hip_set_collectives_library", "icicle_hip_test_inject_failure",
@@ -461,6 +461,7 @@ lib.icicle_hip_kernel_timing.argtypes = [ctypes.c_int, ctypes.c_bool, ctypes.POI
 lib.icicle_hip_enable_kernel_timing.argtypes = [ctypes.c_bool]
 lib.icicle_hip_msm_plan.argtypes = [ctypes.c_int, ctypes.c_int, ctypes.POINTER(MSMConfig), ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_int)]
 lib.icicle_hip_msm_plan_info.argtypes = [ctypes.c_int, ctypes.c_int, ctypes.POINTER(MSMConfig), ctypes.c_int, ctypes.POINTER(ctypes.c_int)]
+lib.icicle_hip_ecntt_plan_info.argtypes = [ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_bool, ctypes.c_bool, ctypes.POINTER(ctypes.c_int)]
 lib.icicle_hip_ubench_mixed_add.argtypes = [ctypes.c_int, ctypes.POINTER(ctypes.c_double)]
 lib.icicle_hip_ubench_ntt_pass.argtypes = [ctypes.c_int, ctypes.POINTER(ctypes.c_double)]
 lib.icicle_hip_ubench_gather.argtypes = [ctypes.c_uint64, ctypes.c_uint64, ctypes.POINTER(ctypes.c_double)]

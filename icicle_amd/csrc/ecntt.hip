@@ -391,26 +391,20 @@ namespace icicle_hip {
     k_ecntt_load<C><<<(unsigned)((tot + 63) / 64), 64, 0, st>>>(d_in, work, lay);
     LAUNCH_CHECK("k_ecntt_load", st);
     // per-point factors outside the butterflies (forward coset on the way in; 1/N [and the coset] on the way out): k_ecntt_scale
+    const EcnttRoute rt = ecntt_route(sizeof(Proj), logn, tot, lay.inverse != 0, lay.coset != 0, ecntt_env_overrides()); // (ntt_plan.h)
     const uint64_t scale_quads = ((tot * 4 + 63) / 64) * 16;
-    const bool scale_gtab = tot > (uint64_t)(sizeof(Proj) > 120 ? 12288 : 20480); // more points than LDS-resident tables allow in flight
+    const bool scale_gtab = rt.scale_gtab; // more points than LDS-resident tables allow in flight
     // ONE scratch buffer (d_terms) serves the scale tables, the stage tables and the matrix-form terms: they are never alive
     // at the same time on the stream (rounds 1-4 kept the scale tables next to the stage scratch: 2^20 BLS12-381 points took
     // 2.4 GB + 1.2 GB for a 151 MB transform). Sized once, for the largest of the three.
-    static const int forced_r = getenv("ICICLE_HIP_ECNTT_RADIX_LOG") ? atoi(getenv("ICICLE_HIP_ECNTT_RADIX_LOG")) : 0;
-    // product budget of a matrix-form stage: 16384 quads is the knee for transforms of up to 2^13 points (2^12: 2.04 ms against 2.71 at 32768),
-    // from 2^14 points a second radix-4 stage pays (2^14: 6.49 -> 6.02 ms); profiles/r06_ecntt_quads_budget.txt, re-measured on the round-6 chain
-    static const uint64_t budget_env = getenv("ICICLE_HIP_ECNTT_QUADS") ? (uint64_t)atoll(getenv("ICICLE_HIP_ECNTT_QUADS")) : 0;
-    const uint64_t budget = budget_env ? budget_env : (tot >= 16384 ? 32768 : 16384);
-    static const int gtab_mode = getenv("ICICLE_HIP_ECNTT_GTABS") ? atoi(getenv("ICICLE_HIP_ECNTT_GTABS")) : -1; // 0 / 1 force, -1 auto
-    int widths[64];
-    const int nst = ecntt_stage_plan(logn, tot, budget, forced_r, widths);
-    const int rmax = nst ? widths[0] : 1; // (widths are non-increasing)
+    const int* widths = rt.widths;
+    const int nst = rt.nst, rmax = rt.rmax; // (widths are non-increasing)
     const uint64_t stage_quads = ((tot / 2 * 4 + 63) / 64) * 16; // quads launched per radix-2 stage (incl. the padding of the last block)
-    const bool stage_gtab = gtab_mode >= 0 ? gtab_mode != 0 : tot / 2 > (uint64_t)(sizeof(Proj) > 120 ? 12288 : 20480);
+    const bool stage_gtab = rt.stage_gtab;
     {
       size_t need = 0;
-      if (scale_gtab && (lay.inverse || lay.coset)) need = std::max(need, (size_t)scale_quads * 16 * sizeof(Proj));
-      if (rmax == 1 && stage_gtab) need = std::max(need, (size_t)stage_quads * 16 * sizeof(Proj));
+      if (scale_gtab) need = std::max(need, (size_t)scale_quads * 16 * sizeof(Proj));
+      if (stage_gtab) need = std::max(need, (size_t)stage_quads * 16 * sizeof(Proj));
       if (rmax > 1 && logn > 0) need = std::max(need, (size_t)(tot * ((1ull << rmax) - 1) / 2) * sizeof(Proj)); // n (R - 1) / 2 products of the widest stage
       if (need) HIP_TRY(d_terms.alloc(need, st), ICICLE_ALLOCATION_FAILED);
     }
@@ -486,3 +480,19 @@ using namespace icicle_hip;
 DEFINE_ECNTT(bn254)
 DEFINE_ECNTT(bls12_381)
 DEFINE_ECNTT(bls12_377)
+
+// the route <curve>_ecntt would take in this process, environment overrides included (ntt_plan.h ecntt_route): out[0] = number of
+// stages, out[1] = rmax, out[2] = stage_gtab, out[3] = a scale pass runs, out[4] = scale_gtab, out[5 + i] = width of stage i
+extern "C" icicle_error_t icicle_hip_ecntt_plan_info(int point_bytes, int size, int batch, bool inverse, bool coset, int* out)
+{
+  if (!out) return ICICLE_INVALID_POINTER;
+  if (point_bytes <= 0 || size <= 0 || (size & (size - 1)) != 0) return ICICLE_INVALID_ARGUMENT;
+  int logn = 0;
+  while ((1 << logn) < size)
+    logn++;
+  const EcnttRoute rt = ecntt_route((size_t)point_bytes, logn, (uint64_t)size * (uint64_t)std::max(1, batch), inverse, coset, ecntt_env_overrides());
+  out[0] = rt.nst, out[1] = rt.rmax, out[2] = rt.stage_gtab ? 1 : 0, out[3] = rt.scale_runs ? 1 : 0, out[4] = rt.scale_gtab ? 1 : 0;
+  for (int i = 0; i < rt.nst; i++)
+    out[5 + i] = rt.widths[i];
+  return ICICLE_SUCCESS;
+}

@@ -7,6 +7,7 @@
 #pragma once
 #include <algorithm>
 #include <cstdint>
+#include <cstdlib>
 
 namespace icicle_hip {
 
@@ -383,6 +384,49 @@ namespace icicle_hip {
     for (int si = 0; si < nst; si++)
       widths[si] = logn / nst + (si < logn % nst ? 1 : 0);
     return nst;
+  }
+  // ---- ECNTT route (ecntt.hip ecntt_run): every decision that picks a kernel or the place of its tables, from the total point
+  // count tot = size * batch and the size of a point in the kernels' form (108 bytes: bn254, 168: the BLS curves) ----
+  struct EcnttOverrides { // ICICLE_HIP_ECNTT_RADIX_LOG / _QUADS / _GTABS; 0 / 0 / -1 = not set
+    int forced_r = 0;
+    uint64_t budget = 0;
+    int gtab_mode = -1; // 0 / 1 force the radix-2 stage tables into LDS / global memory, -1 auto
+  };
+  static inline EcnttOverrides ecntt_env_overrides() // (read once per process)
+  {
+    static const EcnttOverrides ov = [] {
+      EcnttOverrides o;
+      if (const char* s = getenv("ICICLE_HIP_ECNTT_RADIX_LOG")) o.forced_r = atoi(s);
+      if (const char* s = getenv("ICICLE_HIP_ECNTT_QUADS")) o.budget = (uint64_t)atoll(s);
+      if (const char* s = getenv("ICICLE_HIP_ECNTT_GTABS")) o.gtab_mode = atoi(s);
+      return o;
+    }();
+    return ov;
+  }
+  struct EcnttRoute {
+    uint64_t budget; // product budget of a matrix-form stage, in quads
+    int nst;         // stages; widths[0 .. nst) are non-increasing and sum to logn
+    int widths[64];
+    int rmax;        // widths[0] (1 for a one-point transform): 1 = k_ecntt_stage (radix 2), else k_ecntt_terms + k_ecntt_sums
+    bool stage_gtab; // the radix-2 stages keep their quads' 16-entry tables in global memory instead of LDS (rmax == 1 only)
+    bool scale_runs; // k_ecntt_scale runs: the forward coset factors on the way in, 1 / N [and the coset] on the way out
+    bool scale_gtab; // ... with its tables in global memory
+  };
+  // Budget: 16384 quads is the knee for transforms of up to 2^13 points (2^12: 2.04 ms against 2.71 at 32768), from 2^14 points a
+  // second radix-4 stage pays (2^14: 6.49 -> 6.02 ms); profiles/r06_ecntt_quads_budget.txt. Tables: LDS holds 16 of them per
+  // 64-thread block, i.e. 5 / 3 waves per CU = 20480 / 12288 quads in flight for 108 / 168-byte points; a launch with more quads
+  // than that keeps them in global memory (k_ecntt_stage). A radix-2 stage has tot / 2 quads, a scale pass tot.
+  static inline EcnttRoute ecntt_route(size_t point_bytes, int logn, uint64_t tot, bool inverse, bool coset, const EcnttOverrides& ov)
+  {
+    EcnttRoute rt;
+    rt.budget = ov.budget ? ov.budget : (tot >= 16384 ? 32768 : 16384);
+    rt.nst = ecntt_stage_plan(logn, tot, rt.budget, ov.forced_r, rt.widths);
+    rt.rmax = rt.nst ? rt.widths[0] : 1;
+    const uint64_t lds_quads = point_bytes > 120 ? 12288 : 20480;
+    rt.stage_gtab = rt.rmax == 1 && (ov.gtab_mode >= 0 ? ov.gtab_mode != 0 : tot / 2 > lds_quads);
+    rt.scale_runs = inverse || coset;
+    rt.scale_gtab = rt.scale_runs && tot > lds_quads;
+    return rt;
   }
   // exponent (mod M = 2^(q0 + r)) of the twiddle that term (j, u) of a radix-2^r stage at q0 multiplies A_j[pos] with:
   // Y[pos + L k] = sum_j w_M^(rev_r(j) (pos + L k)) A_j[pos], k = u or u + R/2 (the latter with the sign (-1)^rev_r(j))

@@ -636,6 +636,12 @@ icicle_error_t icicle_hip_msm_plan(int msm_size, int scalar_bits, const icicle_m
  * their point negated, icicle/backend/cpu/src/curve/cpu_msm.hpp:276-277), buckets per window slot, buckets in use, segment size,
  * windows per precomputed-table entry. force_windows = MSMConfig.ext "hip_msm_windows" (0: the cost model decides, as msm() does). */
 icicle_error_t icicle_hip_msm_plan_info(int msm_size, int scalar_bits, const icicle_msm_config_t* config, int force_windows, int* out);
+/* The route <curve>_ecntt would take in this process for size * batch points of point_bytes each in the kernels' form (108: bn254,
+ * 168: bls12_381 / bls12_377), for tests: out[0] = number of stages, out[1] = rmax (width of the widest stage; 1 = the radix-2 kernel,
+ * more = the matrix form), out[2] = 1 if the radix-2 stages keep their tables in global memory instead of LDS, out[3] = 1 if a scale
+ * pass runs (inverse, or coset: a coset generator other than 1), out[4] = 1 if that pass keeps its tables in global memory,
+ * out[5 + i] = width of stage i. `out` holds 5 + log2(size) ints. ICICLE_HIP_ECNTT_RADIX_LOG / _QUADS / _GTABS are taken into account. */
+icicle_error_t icicle_hip_ecntt_plan_info(int point_bytes, int size, int batch, bool inverse, bool coset, int* out);
 /* Device-side synthetic input generator for benchmarks: fills `out` (device or host per flag) with
  * `n` DISTINCT affine points (k0 + i) * G in the reference's canonical affine layout. */
 icicle_error_t bn254_hip_generate_affine_points(void* out, int n, uint64_t k0, bool out_on_device, icicleStreamHandle stream);

@@ -393,3 +393,17 @@ extern "C" int ecntt_plan_check(void)
       }
   return 0;
 }
+
+// ECNTT route (ntt_plan.h ecntt_route, what ecntt_run launches) for one shape and one set of overrides: out[0] = stages, out[1] = rmax,
+// out[2] = stage_gtab, out[3] = scale pass runs, out[4] = scale_gtab, out[5] = budget, out[6 + i] = width of stage i. logn and tot are
+// separate arguments so that a test can put tot on either side of a boundary whatever the transform size (the function reads tot only).
+extern "C" int ecntt_route_probe(int point_bytes, int logn, uint64_t tot, int inverse, int coset, int forced_r, uint64_t budget, int gtab_mode, int* out)
+{
+  EcnttOverrides ov;
+  ov.forced_r = forced_r, ov.budget = budget, ov.gtab_mode = gtab_mode;
+  const EcnttRoute rt = ecntt_route((size_t)point_bytes, logn, tot, inverse != 0, coset != 0, ov);
+  out[0] = rt.nst, out[1] = rt.rmax, out[2] = rt.stage_gtab, out[3] = rt.scale_runs, out[4] = rt.scale_gtab, out[5] = (int)rt.budget;
+  for (int i = 0; i < rt.nst; i++)
+    out[6 + i] = rt.widths[i];
+  return 0;
+}

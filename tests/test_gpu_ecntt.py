@@ -107,24 +107,35 @@ def test_ecntt_device_and_errors(env, hip):
         N.ecntt(cname, x, N.FORWARD, size=1 << (DOMAIN_LOG + 1))  # larger than the domain
 
 
-@pytest.mark.parametrize("radix_log", [1, 2, 3, 4, 5])
-def test_ecntt_every_stage_radix_vs_reference(hip, radix_log):
+# (curve, ICICLE_HIP_ECNTT_RADIX_LOG, ICICLE_HIP_ECNTT_GTABS or None): the five bn254 children, and three per BLS curve
+STAGE_CHILDREN = [pytest.param("bn254", r, None, id=str(r)) for r in (1, 2, 3, 4, 5)] + [
+    pytest.param(c, r, g, id=f"{c}-r{r}" + ("" if g is None else f"-gtabs{g}"))
+    for c in ("bls12_381", "bls12_377") for r, g in ((1, 0), (1, 1), (2, None))]
+
+
+@pytest.mark.parametrize("cname,radix_log,gtabs", STAGE_CHILDREN)
+def test_ecntt_every_stage_radix_vs_reference(hip, cname, radix_log, gtabs):
     """the radix-2^r matrix-form stages (icicle_amd/csrc/ecntt.hip: k_ecntt_terms / k_ecntt_sums) with r forced through
     ICICLE_HIP_ECNTT_RADIX_LOG (read once per process, hence a child process): 2^7 and 2^9 points -- uneven stage widths, e.g.
-    r = 4: 4 + 3 and 3 + 3 + 3 -- forward and inverse, a batch, bit-reversed orderings and a coset, against the reference CPU backend"""
+    r = 4: 4 + 3 and 3 + 3 + 3 -- forward and inverse, a batch, bit-reversed orderings and a coset, against the reference CPU backend.
+    On the BLS curves (14-limb points, 168 bytes): r = 1 with ICICLE_HIP_ECNTT_GTABS=0 -- k_ecntt_stage at stages 0..8 with real twiddles
+    and doubling chains, tables in LDS; r = 1 with GTABS=1 -- the same with the tables in global memory; r = 2 -- widths 2,2,2,1 and
+    2,2,2,2,1, the width-1 matrix-form stage (16 tables per block, 43008 bytes of dynamic LDS). Those children put one identity and one
+    Z != 1 representative into every case. Every child asserts the forced route with icicle_hip_ecntt_plan_info."""
     import os
     import subprocess
     import sys
 
     code = r"""
-import sys, numpy as np
+import ctypes, sys, numpy as np
 sys.path.insert(0, %r)
 import icicle_amd as hip
 from icicle_amd import ntt as N, runtime
+from icicle_amd._lib import lib
 from oracle import pyref, ref
-from tests.util import to_words
+from tests.util import from_words, to_words
 runtime.set_device(0)
-cname = "bn254"
+cname, radix_log, gtabs = %r, %r, %r
 C, F = pyref.CURVES[cname], pyref.NTT_FIELDS[cname]
 refc, sf = ref.RefCurve(cname), ref.RefScalarNttField(cname)
 root = N.get_root_of_unity(cname, 1 << 9)
@@ -132,8 +143,24 @@ N.init_domain(cname, root); sf.init_domain(root)
 L = C.limbs_q
 for logn, batch, columns, ordering, direction, coset in ((7, 1, False, 0, 0, 1), (7, 3, True, 3, 1, 5), (9, 1, False, 1, 1, 1), (9, 2, False, 2, 0, 11)):
     n = 1 << logn
+    # the route this process takes: stages of width min(r, logn) spread as evenly as possible; forced table placement applies to r = 1
+    rmax = min(5, radix_log, logn)
+    nst = (logn + rmax - 1) // rmax
+    widths = [logn // nst + (1 if i < logn %% nst else 0) for i in range(nst)]
+    info = (ctypes.c_int * 40)()
+    assert lib.icicle_hip_ecntt_plan_info(108 if L == 8 else 168, n, batch, bool(direction), coset != 1, info) == 0
+    assert list(info[5:5 + info[0]]) == widths and info[1] == widths[0], (list(info[:16]), widths)
+    assert info[2] == (1 if widths[0] == 1 and gtabs == 1 else 0) and info[3] == int(bool(direction) or coset != 1) and info[4] == 0, list(info[:5])
+    if radix_log == 2: assert widths[-1] == 1 and widths[0] == 2
     base = refc.generate_affine_points(n * batch)
-    x = np.ascontiguousarray(np.concatenate([base, np.tile(to_words([1], L), (n * batch, 1))], axis=1).astype(np.uint32)).reshape(-1)
+    x = np.ascontiguousarray(np.concatenate([base, np.tile(to_words([1], L), (n * batch, 1))], axis=1).astype(np.uint32))
+    if cname != "bn254":
+        i0, i1 = (5 * logn + 3) %% (n * batch), (11 * logn + 70) %% (n * batch)
+        x[i0] = np.concatenate([to_words([0], L)[0], to_words([1], L)[0], to_words([0], L)[0]])  # the identity (0 : 1 : 0)
+        lam = 0x1234567890ABCDEF1234567 + logn
+        px, py = from_words(x[i1, :L]), from_words(x[i1, L:2 * L])
+        x[i1] = to_words([px * lam %% C.q, py * lam %% C.q, lam], L).reshape(-1)  # the same point as (lam x : lam y : lam)
+    x = x.reshape(-1)
     cfg = hip.NTTConfigU256.default()
     cfg.batch_size, cfg.columns_batch, cfg.ordering = batch, columns, ordering
     cfg.set_coset_gen(coset)
@@ -141,10 +168,13 @@ for logn, batch, columns, ordering, direction, coset in ((7, 1, False, 0, 0, 1),
     exp = refc.ecntt(x, n, direction, batch=batch, columns_batch=columns, ordering=ordering, coset_gen=coset)
     assert np.array_equal(refc.to_affine(got.reshape(-1, 3 * L)), refc.to_affine(exp.reshape(-1, 3 * L))), (logn, batch, columns, ordering, direction, coset)
 print("RADIX OK")
-""" % os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+""" % (os.path.dirname(os.path.dirname(os.path.abspath(__file__))), cname, radix_log, gtabs)
     env = dict(os.environ)
     env["ICICLE_HIP_ECNTT_RADIX_LOG"] = str(radix_log)
-    r = subprocess.run([sys.executable, "-c", code], capture_output=True, text=True, env=env, timeout=600)
+    env.pop("ICICLE_HIP_ECNTT_GTABS", None)
+    if gtabs is not None:
+        env["ICICLE_HIP_ECNTT_GTABS"] = str(gtabs)
+    r = subprocess.run([sys.executable, "-c", code], capture_output=True, text=True, env=env, timeout=240)
     assert r.returncode == 0 and "RADIX OK" in r.stdout, r.stdout[-1500:] + r.stderr[-3000:]
 
 

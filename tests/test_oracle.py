@@ -208,3 +208,41 @@ def test_reference_goldilocks_matches_golden_and_definition():
         assert [int(v) for v in g["inv_RN_coset"].view("<u8")[:1024]] == pyref.ntt_naive(F, row, pyref.omega(F, 10), inverse=True, coset_gen=cg, ordering="RN")
     finally:
         rf.release_domain()
+
+
+@pytest.mark.parametrize("cname", ["bn254", "bls12_381"])
+def test_reference_ecntt_is_representative_independent_on_the_route_inputs(cname):
+    """the premise of tests/test_gpu_ecntt_routes.py, on the reference alone: for the 37 16-point transforms of tests/ecntt_inputs.py --
+    identities as (0 : lam : 0), Z != 1 representatives, equal and opposite points, sums that cancel -- the reference CPU backend gives
+    the same group elements as for their normalised forms (Z = 1, (0 : 1 : 0)) under both call configurations, and for transforms 0..10,
+    whose scalars are known, NTT(k)_i G computed in Python integers"""
+    from tests import ecntt_inputs as EI
+
+    C = pyref.CURVES[cname]
+    L = C.limbs_q
+    refc, sf = ref.RefCurve(cname), ref.RefScalarNttField(cname)
+    slots, scalars = EI.transforms(cname)
+    assert len(slots) == EI.COUNT and all(len(s) == EI.N for s in slots) and len(scalars) == EI.KNOWN
+    x = np.stack([EI.words(C, s) for s in slots])
+    xn = np.stack([EI.words(C, s, normalised=True) for s in slots])
+    assert not np.array_equal(x, xn) and len({xx.tobytes() for xx in x}) == EI.COUNT  # 37 distinct inputs, some not normalised
+    for row, s in zip(x, slots):  # the words are what they claim to be
+        assert [pyref.proj_to_affine(C, *(from_words(w[i * L:(i + 1) * L]) for i in range(3))) for w in row] == [p for p, _ in s]
+    sf.init_domain(sf.get_root_of_unity(EI.N))
+    try:
+        for call in (EI.FORWARD_CALL, EI.INVERSE_CALL):
+            direction, ordering, columns, coset = call
+            out = []
+            for inp in (x, xn):
+                y = refc.ecntt(EI.tile(inp, EI.COUNT, columns).reshape(-1), EI.N, direction, batch=EI.COUNT, columns_batch=columns, ordering=ordering, coset_gen=coset)
+                aff = refc.to_affine(y.reshape(-1, 3 * L))
+                out.append(aff.reshape(EI.N, EI.COUNT, -1).transpose(1, 0, 2) if columns else aff.reshape(EI.COUNT, EI.N, -1))
+            assert np.array_equal(out[0], out[1]), (cname, call)
+            for t, ks in enumerate(scalars):
+                assert np.array_equal(out[0][t], EI.expected_from_scalars(cname, ks, bool(direction), EI.ORD[ordering], coset)), (cname, call, t)
+            # the transforms are computed one by one: a batch of 37 equals 37 single calls (the tiling of the GPU test leans on it)
+            for t in (3, 10, 24):
+                y1 = refc.ecntt(np.ascontiguousarray(x[t]).reshape(-1), EI.N, direction, ordering=ordering, coset_gen=coset)
+                assert np.array_equal(refc.to_affine(y1.reshape(-1, 3 * L)), out[0][t])
+    finally:
+        sf.release_domain()
