@@ -332,6 +332,8 @@ API_SYMBOLS = (
     + [f"icicle_hip_{GOLD}_{s}" for s in ("ntt", "extension_ntt", "ntt_init_domain", "ntt_release_domain", "get_root_of_unity_from_domain")]
     + [f"{pre}{f}_{op}" for pre in ("", "icicle_hip_") for f in NTT_FIELDS + BIG_VEC_FIELDS + [GOLD]
        for op in ("vector_add", "vector_sub", "vector_mul", "scalar_mul_vec", "scalar_add_vec", "scalar_sub_vec", "bit_reverse")]
+    + [f"{f}_{op}" for f in NTT_FIELDS + BIG_VEC_FIELDS + [GOLD] for op in ("vector_inv", "vector_div", "vector_sum", "vector_product")]
+    + ["icicle_hip_vector_inv_tile"]
     + [f"{pre}{f}_matrix_transpose" for pre in ("", "icicle_hip_") for f in NTT_FIELDS + BIG_VEC_FIELDS + [GOLD]]
     + [f"{pre}{f}_extension_matrix_transpose" for pre in ("", "icicle_hip_") for f in NTT_FIELDS + [GOLD]]
     + ["icicle_hip_msm_plan", "icicle_hip_msm_plan_info", "icicle_hip_ecntt_plan_info", "icicle_hip_version", "icicle_hip_kernel_timing", "icicle_hip_enable_kernel_timing", "icicle_hip_set_device",
@@ -452,6 +454,10 @@ for _f in NTT_FIELDS + BIG_VEC_FIELDS + [GOLD]:
     for _op in ("vector_add", "vector_sub", "vector_mul", "scalar_mul_vec", "scalar_add_vec", "scalar_sub_vec"):
         getattr(lib, f"{_f}_{_op}").argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64, ctypes.POINTER(VecOpsConfig), ctypes.c_void_p]
     getattr(lib, f"{_f}_bit_reverse").argtypes = [ctypes.c_void_p, ctypes.c_uint64, ctypes.POINTER(VecOpsConfig), ctypes.c_void_p]
+    for _op in ("vector_inv", "vector_sum", "vector_product"):
+        getattr(lib, f"{_f}_{_op}").argtypes = [ctypes.c_void_p, ctypes.c_uint64, ctypes.POINTER(VecOpsConfig), ctypes.c_void_p]
+    getattr(lib, f"{_f}_vector_div").argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64, ctypes.POINTER(VecOpsConfig), ctypes.c_void_p]
+lib.icicle_hip_vector_inv_tile.argtypes = [ctypes.c_int]
 for _n in API_SYMBOLS:
     if _n.endswith("matrix_transpose"):
         getattr(lib, _n).argtypes = [ctypes.c_void_p, ctypes.c_uint32, ctypes.c_uint32, ctypes.POINTER(VecOpsConfig), ctypes.c_void_p]

@@ -10,74 +10,9 @@
 // columns_batch), :536-560 (bit reverse per batch entry). Values are plain (non-Montgomery) residues and
 // stay so: products are computed as montmul(montmul(a, b), R^2).
 // All of these are HBM-bound streams (2 reads + 1 write per element, or 1 + 1 for bit_reverse).
-#include "common.h"
-#include "bigfield.hpp"
-#include "smallfield.hpp"
-#include "goldfield.hpp"
+#include "vecops_elem.hpp" // SmallElem / BigElem / GoldElem, Staged, finish_out
 
 namespace icicle_hip {
-
-  enum { VOP_ADD = 0, VOP_SUB = 1, VOP_MUL = 2 };
-
-  template <class PR>
-  struct SmallElem {
-    using S = SmallField<PR>;
-    static constexpr int W = 1;
-    struct T {
-      uint32_t v;
-    };
-    static __device__ __forceinline__ T load(const uint32_t* p) { return T{*p}; }
-    static __device__ __forceinline__ void store(uint32_t* p, const T& x) { *p = x.v; }
-    static __device__ __forceinline__ T apply(int op, const T& a, const T& b)
-    {
-      if (op == VOP_ADD) return T{S::add(a.v, b.v)};
-      if (op == VOP_SUB) return T{S::sub(a.v, b.v)};
-      return T{S::mul(S::mul(a.v, b.v), PR::R2)};
-    }
-  };
-
-  template <class PR>
-  struct BigElem {
-    using F = FieldOps<PR>;
-    static constexpr int W = F::N32;
-    using T = typename F::fe;
-    static __device__ __forceinline__ T load(const uint32_t* p)
-    {
-      uint32_t w[W];
-#pragma unroll
-      for (int i = 0; i < W; i++)
-        w[i] = p[i];
-      return F::unpack(w);
-    }
-    static __device__ __forceinline__ void store(uint32_t* p, const T& x)
-    {
-      uint32_t w[W];
-      F::pack(w, F::reduce(x));
-#pragma unroll
-      for (int i = 0; i < W; i++)
-        p[i] = w[i];
-    }
-    static __device__ __forceinline__ T apply(int op, const T& a, const T& b)
-    {
-      if (op == VOP_ADD) return F::add(a, b);
-      if (op == VOP_SUB) return F::template sub<2>(a, b);
-      return F::mul(F::mul(a, b), F::from_const(PR::R2));
-    }
-  };
-
-  struct GoldElem { // goldilocks: canonical 64-bit values, goldfield.hpp
-    using F = FieldOps<goldilocks_params>;
-    static constexpr int W = 2;
-    using T = GoldFe;
-    static __device__ __forceinline__ T load(const uint32_t* p) { return F::unpack(p); }
-    static __device__ __forceinline__ void store(uint32_t* p, const T& x) { F::pack(p, x); }
-    static __device__ __forceinline__ T apply(int op, const T& a, const T& b)
-    {
-      if (op == VOP_ADD) return F::add(a, b);
-      if (op == VOP_SUB) return F::template sub<2>(a, b);
-      return F::mul(a, b);
-    }
-  };
 
   // out[i] = a[ai(i)] op b[i]; a_scalar: a holds one scalar per batch entry
   template <class EL>
@@ -108,33 +43,6 @@ namespace icicle_hip {
 #pragma unroll
     for (int i = 0; i < W; i++)
       out[dst * W + i] = w[i];
-  }
-
-  struct Staged { // host <-> device staging of one operand
-    TempBuf buf;
-    const uint32_t* dev = nullptr;
-    icicle_error_t in(const void* p, bool on_device, size_t bytes, hipStream_t st)
-    {
-      if (on_device) {
-        dev = (const uint32_t*)p;
-        return ICICLE_SUCCESS;
-      }
-      HIP_TRY(buf.alloc(bytes, st), ICICLE_ALLOCATION_FAILED);
-      HIP_TRY(hipMemcpyAsync(buf.ptr(), p, bytes, hipMemcpyHostToDevice, st), ICICLE_COPY_FAILED);
-      dev = buf.as<uint32_t>();
-      return ICICLE_SUCCESS;
-    }
-  };
-
-  static icicle_error_t finish_out(void* output, uint32_t* d_out, bool on_device, bool is_async, size_t bytes, hipStream_t st)
-  {
-    if (!on_device) {
-      HIP_TRY(hipMemcpyAsync(output, d_out, bytes, hipMemcpyDeviceToHost, st), ICICLE_COPY_FAILED);
-      HIP_TRY(hipStreamSynchronize(st), ICICLE_SYNCHRONIZATION_FAILED);
-    } else if (!is_async) {
-      HIP_TRY(hipStreamSynchronize(st), ICICLE_SYNCHRONIZATION_FAILED);
-    }
-    return ICICLE_SUCCESS;
   }
 
   template <class EL>

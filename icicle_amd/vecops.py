@@ -91,6 +91,49 @@ def scalar_sub_vec(field, scalars, b, cfg=None, out=None, size=None):
     return _vec2("scalar_sub_vec", field, scalars, b, size, cfg, out)
 
 
+def vector_div(field, a, b, cfg=None, out=None, size=None):
+    """a[i] / b[i], with x / 0 = 0; in place allowed (out is a or b)"""
+    return _vec2("vector_div", field, a, b, size, cfg, out)
+
+
+def _vec1(op: str, field: str, a, size, cfg, out, reduces: bool):
+    """vector_inv (one output element per input element) and vector_sum / vector_product (one per batch entry, [batch, words])"""
+    cfg = cfg or VecOpsConfig.default()
+    ap, cfg.is_a_on_device = _ptr(a)
+    batch = max(1, cfg.batch_size)
+    if size is None:
+        assert not isinstance(a, int), "a raw device address has no size: pass size"
+        size = a.nbytes // (4 * _WORDS[field]) // batch
+    if out is None:
+        if reduces:
+            out = np.zeros((batch, _WORDS[field]), np.uint32)
+        else:
+            out = np.zeros_like(a) if isinstance(a, np.ndarray) else np.zeros((size * batch, _WORDS[field]), np.uint32)
+    op_, cfg.is_result_on_device = _ptr(out)
+    check(getattr(lib, f"{field}_{op}")(ap, size, ctypes.byref(cfg), op_), f"{field}_{op}")
+    return out
+
+
+def vector_inv(field, a, cfg=None, out=None, size=None):
+    """1 / a[i], with 1 / 0 = 0; in place allowed (out is a)"""
+    return _vec1("vector_inv", field, a, size, cfg, out, False)
+
+
+def vector_sum(field, a, cfg=None, out=None, size=None):
+    """the sum of each batch entry (element j of entry k at k * size + j, or at j * batch_size + k with columns_batch): [batch, words]"""
+    return _vec1("vector_sum", field, a, size, cfg, out, True)
+
+
+def vector_product(field, a, cfg=None, out=None, size=None):
+    """the product of each batch entry, laid out like vector_sum's: [batch, words]"""
+    return _vec1("vector_product", field, a, size, cfg, out, True)
+
+
+def vector_inv_tile(field) -> int:
+    """how many neighbouring elements of `field` share one inversion in vector_inv / vector_div"""
+    return lib.icicle_hip_vector_inv_tile(_WORDS[field])
+
+
 def bit_reverse(field, inp, cfg=None, out=None, size=None):
     cfg = cfg or VecOpsConfig.default()
     ip, cfg.is_a_on_device = _ptr(inp)

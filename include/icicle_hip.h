@@ -274,6 +274,29 @@ ICICLE_HIP_DECLARE_VEC_ARITH(koalabear)
 ICICLE_HIP_DECLARE_VEC_ARITH(bn254)
 ICICLE_HIP_DECLARE_VEC_ARITH(bls12_381)
 
+/* Inversion, division, sum and product of field vectors, for the fields above and the ones declared with them further down
+ * (src/vec_ops.cpp:250 vector_inv, :217 vector_div, :40 vector_sum, :9 vector_product; CPU backend
+ * backend/cpu/src/field/cpu_vec_ops.cpp:158-201, 386-503). Elements are canonical words in and out; `size` is per batch entry.
+ *  - vector_inv / vector_div are element-wise over size * batch_size elements (columns_batch changes nothing):
+ *    output[i] = vec_a[i] * vec_b[i]^-1. The inverse of zero is zero, so a / 0 = 0 and inv(0) = 0, and a zero disturbs no other
+ *    element. In place is allowed (output == vec_a, for vector_div also output == vec_b); partial overlap is undefined.
+ *    The elements of a tile of icicle_hip_vector_inv_tile(words) neighbours share one a^(p-2) chain (Montgomery's trick).
+ *  - vector_sum / vector_product write batch_size contiguous elements: entry k reduces its elements j < size, found at
+ *    k * size + j, or at j * batch_size + k with columns_batch. The result is the same bytes on every run.
+ *  - config: is_a_on_device, is_b_on_device, is_result_on_device, stream and is_async as for vector_mul. NULL config gives
+ *    ICICLE_INVALID_POINTER, then size == 0 gives ICICLE_SUCCESS with nothing written, then a NULL vector ICICLE_INVALID_POINTER. */
+#define ICICLE_HIP_DECLARE_VEC_INV(F)                                                                                  \
+  icicle_error_t F##_vector_inv(const void* vec_a, uint64_t size, const icicle_vec_ops_config_t* config, void* output); \
+  icicle_error_t F##_vector_div(const void* vec_a, const void* vec_b, uint64_t size, const icicle_vec_ops_config_t* config, void* output); \
+  icicle_error_t F##_vector_sum(const void* vec_a, uint64_t size, const icicle_vec_ops_config_t* config, void* output); \
+  icicle_error_t F##_vector_product(const void* vec_a, uint64_t size, const icicle_vec_ops_config_t* config, void* output);
+ICICLE_HIP_DECLARE_VEC_INV(babybear)
+ICICLE_HIP_DECLARE_VEC_INV(koalabear)
+ICICLE_HIP_DECLARE_VEC_INV(bn254)
+ICICLE_HIP_DECLARE_VEC_INV(bls12_381)
+/* elements that share one inversion, for elements of 1, 2 or 8 words; 0 for any other width. Needs no device. */
+int icicle_hip_vector_inv_tile(int words_per_element);
+
 /* Matrix transpose of batch_size row-major nof_rows x nof_cols matrices (icicle/src/matrix_ops.cpp:75-102,
  * include/icicle/vec_ops.h:319; CPU: backend/cpu/src/field/cpu_matrix_ops.cpp:333-362): in place allowed, columns_batch
  * rejected. The Rust NTT suite calls it on the main device around every columns_batch transform
@@ -839,6 +862,9 @@ ICICLE_HIP_DECLARE_CONVERT(icicle_hip_stark252)
 ICICLE_HIP_DECLARE_VEC_ARITH(bls12_377)
 ICICLE_HIP_DECLARE_VEC_ARITH(grumpkin)
 ICICLE_HIP_DECLARE_VEC_ARITH(stark252)
+ICICLE_HIP_DECLARE_VEC_INV(bls12_377)
+ICICLE_HIP_DECLARE_VEC_INV(grumpkin)
+ICICLE_HIP_DECLARE_VEC_INV(stark252)
 /* goldilocks: elements are 2 u32 words (extension elements 4) */
 icicle_error_t goldilocks_ntt(const uint32_t* input, int size, int dir, const icicle_ntt_config_u64_t* config, uint32_t* output);           /* src/ntt.cpp:11 */
 icicle_error_t goldilocks_extension_ntt(const uint32_t* input, int size, int dir, const icicle_ntt_config_u64_t* config, uint32_t* output); /* src/ntt.cpp:90 */
@@ -856,6 +882,7 @@ ICICLE_HIP_DECLARE_CONVERT(icicle_hip_goldilocks)
 icicle_error_t goldilocks_extension_scalar_convert_montgomery(const void* input, uint64_t size, bool is_to_montgomery, const icicle_vec_ops_config_t* config, void* output);
 icicle_error_t icicle_hip_goldilocks_extension_scalar_convert_montgomery(const void* input, uint64_t size, bool is_to_montgomery, const icicle_vec_ops_config_t* config, void* output);
 ICICLE_HIP_DECLARE_VEC_ARITH(goldilocks)
+ICICLE_HIP_DECLARE_VEC_INV(goldilocks)
 
 #ifdef __cplusplus
 }
