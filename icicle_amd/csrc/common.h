@@ -7,6 +7,7 @@
 #include <cstdint>
 #include <cstdio>
 #include <map>
+#include <memory>
 #include <mutex>
 #include <string>
 #include <tuple>
@@ -350,6 +351,18 @@ namespace icicle_hip {
   // Montgomery), 4 = goldilocks (2 words, canonical); for the fold of fri_wide.hip
   bool ntt_big_domain_table(int field, const uint32_t** tw, int* log_max);
   uint64_t hasher_default_chunk(icicle_hasher_handle_t h); // the hasher's default input size, 0 = none
+
+  // ---- what hash.hip reads from poseidon2.hip ----
+  // A Poseidon2 hasher's parameters, derived on the host when it is made (no device needed), and their copy in device memory,
+  // uploaded when the hasher first hashes on a device and freed with the last owner: the hasher handle, and every tree that copied it.
+  struct Poseidon2Hasher;
+  // field 0 = babybear, 1 = koalabear; tag: canonical, or nullptr; nullptr for a width outside 2, 3, 4, 8, 12, 16, 20, 24
+  std::shared_ptr<Poseidon2Hasher> poseidon2_make(int field, unsigned t, const uint32_t* tag);
+  // n messages of `len` bytes at in + i * stride -> n digests of 4 bytes at out; in, stride, len and out multiples of 4
+  icicle_error_t poseidon2_launch_batch(Poseidon2Hasher& h, const uint8_t* in, uint64_t len, uint64_t stride, uint64_t n, uint8_t* out, hipStream_t st);
+  // layer-0 chunks [first, first + n) of a tree whose leaves end inside or in front of them (ReadPadded of hash_readers.hpp)
+  icicle_error_t poseidon2_launch_leaves(Poseidon2Hasher& h, const uint8_t* leaves, uint64_t chunk, uint64_t first, uint64_t n, uint64_t valid, const uint8_t* last,
+                                         uint64_t es, uint8_t* out, hipStream_t st);
 
   // ---- dominant-kernel timing with hipEvents on the launch stream (bench.py roofline figure) ----
   struct KernelTimer {

@@ -1,10 +1,11 @@
-"""Keccak / SHA3 / Blake2s / Blake3 batch hashing on the device: mirror of wrappers/rust/icicle-core/src/hash (Hasher, HashConfig)
-over icicle_create_keccak_256 .. icicle_create_blake3 / icicle_hasher_hash (include/icicle_hip.h)."""
+"""Keccak / SHA3 / Blake2s / Blake3 / Poseidon2 batch hashing on the device: mirror of wrappers/rust/icicle-core/src/hash (Hasher,
+HashConfig) over icicle_create_keccak_256 .. icicle_create_blake3, <field>_create_poseidon2_hasher / icicle_hasher_hash
+(include/icicle_hip.h)."""
 import ctypes
 
 import numpy as np
 
-from ._lib import lib, check, HashConfig
+from ._lib import lib, check, HashConfig, POSEIDON2_FIELDS
 from .runtime import DeviceVec
 
 
@@ -19,8 +20,8 @@ def _ptr(x):
 
 
 class Hasher:
-    """One of the four Keccak-f[1600] sponges, Blake2s-256 or Blake3; `chunk` is the default message size in bytes (a Merkle layer's
-    input size)."""
+    """One of the four Keccak-f[1600] sponges, Blake2s-256, Blake3 or Poseidon2 over a 31-bit field; `chunk` is the default message
+    size in bytes (a Merkle layer's input size)."""
 
     def __init__(self, handle, chunk):
         if not handle:
@@ -51,6 +52,18 @@ class Hasher:
     @classmethod
     def blake3(cls, chunk=0):
         return cls(lib.icicle_create_blake3(chunk), chunk)
+
+    @classmethod
+    def poseidon2(cls, field, t, domain_tag=None, input_size=0):
+        """Poseidon2 of width t (2, 3, 4, 8, 12, 16, 20, 24) over "babybear" or "koalabear": messages and digests are uint32 canonical
+        residues, the digest one element. `input_size` is in elements, 0 = t (t - 1 beside a `domain_tag`, which is one element)."""
+        if field not in POSEIDON2_FIELDS:
+            raise ValueError(f"Poseidon2 is built over {POSEIDON2_FIELDS}, not {field!r}")
+        tag = None if domain_tag is None else ctypes.byref(ctypes.c_uint32(int(domain_tag)))
+        handle = getattr(lib, f"{field}_create_poseidon2_hasher")(t, tag, input_size)
+        if not handle:
+            raise ValueError(f"Poseidon2 has no width {t}")
+        return cls(handle, 4 * (input_size or (t if domain_tag is None else t - 1)))
 
     @property
     def output_size(self) -> int:

@@ -80,7 +80,8 @@ def _leaves(leaves, size):
 
 class MerkleTree:
     """layer_hashers: one Hasher per layer, leaf layer first, each created with its layer's input chunk size; the layers may mix all
-    six hashers (Keccak / SHA3 256 and 512, Blake2s, Blake3)"""
+    six byte hashers (Keccak / SHA3 256 and 512, Blake2s, Blake3); Poseidon2 layers (leaf elements of 4 bytes, digests of one
+    element) build, open and verify the same way"""
 
     def __init__(self, layer_hashers, leaf_element_size, output_store_min_layer=0):
         arr = (ctypes.c_void_p * len(layer_hashers))(*[h.handle for h in layer_hashers])

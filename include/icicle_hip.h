@@ -327,8 +327,9 @@ ICICLE_HIP_DECLARE_TRANSPOSE(stark252, matrix_transpose)
  * hashers follow the Merkle functions below, and FRI over every field with an NTT, which composes all of them, follows the proof of work;
  * sumcheck, whose transcript hashes through the same entry points, follows FRI; execute_program, which runs the same programs over
  * vectors, follows sumcheck.
- * Poseidon, Poseidon2, proof serialisation (Merkle, FRI and sumcheck) and the extension_ / rns_ variants of execute_program are not
- * built.
+ * Poseidon2 over BabyBear and KoalaBear hashes and builds trees through the same entry points (its factories follow the Blake ones).
+ * Poseidon (the first), Poseidon2 over the other fields, proof serialisation (Merkle, FRI and sumcheck) and the extension_ / rns_
+ * variants of execute_program are not built.
  * ====================================================================================== */
 typedef struct {
   icicleStreamHandle stream;      /* 0  */
@@ -362,8 +363,20 @@ icicle_hasher_handle_t icicle_create_sha3_512(uint64_t input_chunk_size);   /* :
 /* Blake2s-256 (RFC 7693, no key) and Blake3 (default hash mode, 32-byte output; any message length) */
 icicle_hasher_handle_t icicle_create_blake2s(uint64_t input_chunk_size);    /* :123 */
 icicle_hasher_handle_t icicle_create_blake3(uint64_t input_chunk_size);     /* :136 */
+/* Poseidon2 (src/hash/poseidon2_c_api.cpp:13, semantics of backend/cpu/src/hash/cpu_poseidon2.cpp) of width t in {2, 3, 4, 8, 12, 16,
+ * 20, 24} over a 31-bit field; NULL for any other width. Elements are 4-byte canonical residues, the digest is one element (4 bytes:
+ * state[1]). domain_tag: NULL, or one element that becomes state[0]. input_size: the default message size in elements (a Merkle
+ * layer's input), 0 = one permutation's worth: t, or t - 1 beside a tag. A message of exactly that many elements is one
+ * permutation. Any other size is a sponge over a zero state: state[0] is the tag or else the first element, the rest is added into
+ * state[1 .. t-1], t - 1 elements per permutation; only an incomplete last block is padded, with 1, 0, 0, ..; fewer than t elements
+ * are one permutation. icicle_hasher_hash wants input_len % 4 == 0 and device operands 4-aligned (INVALID_ARGUMENT otherwise);
+ * proof_of_work and proof_of_work_verify refuse these hashers (INVALID_ARGUMENT). alpha, the round numbers, the round constants
+ * and the internal matrix are derived from the specification when the hasher is created (icicle_amd/csrc/poseidon2_params.h), on
+ * the host; they are uploaded when the hasher first hashes on a device and freed with the hasher and the trees that copied it. */
+icicle_hasher_handle_t babybear_create_poseidon2_hasher(unsigned t, const uint32_t* domain_tag, unsigned input_size);
+icicle_hasher_handle_t koalabear_create_poseidon2_hasher(unsigned t, const uint32_t* domain_tag, unsigned input_size);
 /* config->batch messages of input_len bytes each, back to back (input_len = 0: the hasher's default chunk size; both 0:
- * INVALID_ARGUMENT); digests of 32 / 64 bytes back to back. Any length, any pointer alignment. */
+ * INVALID_ARGUMENT); digests of 32 / 64 bytes back to back. Any length, any pointer alignment (Poseidon2: see its factories). */
 icicle_error_t icicle_hasher_hash(icicle_hasher_handle_t h, const uint8_t* input, uint64_t input_len, const icicle_hash_config_t* config, uint8_t* output); /* :22 */
 uint64_t icicle_hasher_output_size(icicle_hasher_handle_t h); /* :40 */
 icicle_error_t icicle_hasher_delete(icicle_hasher_handle_t h); /* :52 */

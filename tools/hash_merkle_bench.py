@@ -16,11 +16,17 @@ interleaved rounds of the same run.
 --openings times batched Merkle openings and verification against loops of single calls for the same indices (--open-counts, default
 200 and 4000 random indices with repeats) on a Blake2s tree over 2^--open-log-leaves 16-byte leaves kept on the device: MerkleTree.proofs
 beside a loop of MerkleTree.proof, MerkleTree.verify_batch beside a loop of MerkleTree.verify, in interleaved rounds.
+--poseidon2 times Poseidon2 over BabyBear and KoalaBear (profiles/poseidon2_notes.md, which it writes with --notes): batches of 2^--log-batch
+messages of one permutation at t = 16 and t = 24, device to device, beside a device-to-device copy of the same input bytes and Blake3
+over the same input, in interleaved rounds; and the build of a binary tree (leaf layer: a t = 16 sponge over 8 elements, upper layers:
+t = 2 compressions) beside a Blake3 tree over the same leaves. The registers and scratch of every kernel come from the library
+(tools/kernel_regs.py).
 usage: tools/hash_merkle_bench.py [--hash keccak256 [blake2s blake3]] [--log-batch 22] [--log-leaves 22 10] [--top-max 0 256 1024] [--reps 5]
        tools/hash_merkle_bench.py --pow [--hash keccak256 blake2s blake3] [--reps 9] [--pow-bits 20 25 30] [--pow-span-log2 24 28 32]
        tools/hash_merkle_bench.py --fri [--field babybear_extension|goldilocks|goldilocks_extension|stark252|bn254|bls12_381|bls12_377]
                                         [--fri-log-n 20 24] [--reps 5]
-       tools/hash_merkle_bench.py --openings [--open-log-leaves 20] [--open-counts 200 4000] [--reps 5]"""
+       tools/hash_merkle_bench.py --openings [--open-log-leaves 20] [--open-counts 200 4000] [--reps 5]
+       tools/hash_merkle_bench.py --poseidon2 [--log-batch 20] [--p2-log-leaves 18] [--reps 5] [--notes profiles/poseidon2_notes.md]"""
 import argparse
 import ctypes
 import os
@@ -253,8 +259,98 @@ def openings_bench(a):
     tree.close()
 
 
+def poseidon2_kernel_rows():
+    """name -> (VGPRs, SGPRs, scratch bytes per lane) of every Poseidon2 kernel in the library"""
+    import importlib.util
+    import re
+    import tempfile
+
+    import icicle_amd
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    spec = importlib.util.spec_from_file_location("kernel_regs", os.path.join(root, "tools", "kernel_regs.py"))
+    kr = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(kr)
+    out = {}
+    with tempfile.TemporaryDirectory() as tmp:
+        rows = [k for co in kr.code_objects(icicle_amd.LIB_PATH, tmp) for k in kr.kernels(co)]
+        dm = kr.demangle([r["name"] for r in rows])
+        for r in rows:
+            name = re.sub(r"\(.*", "", dm[r["name"]]).replace("icicle_hip::", "").replace("void ", "")
+            if name.startswith("k_poseidon2_"):
+                out[name] = (r.get("vgpr_count"), r.get("sgpr_count"), int(r.get("private_segment_fixed_size", 0)))
+    return out
+
+
+def poseidon2_bench(a):
+    from icicle_amd import MerkleTreeConfig, runtime
+    from icicle_amd._lib import lib, check
+    from icicle_amd.hash import Hasher
+    from icicle_amd.merkle import MerkleTree
+    from icicle_amd.runtime import DeviceVec
+
+    runtime.set_device(0)
+    rng = np.random.default_rng(1)
+    logb = min(a.log_batch, 20)
+    n = 1 << logb
+    med = lambda t: t[len(t) // 2]
+    lines = []
+
+    def say(line):
+        print(line, flush=True)
+        lines.append(line)
+
+    primes = {"babybear": 0x78000001, "koalabear": 0x7F000001}
+    for field, p in primes.items():
+        for t in (16, 24):
+            d_in = DeviceVec.from_host(rng.integers(0, p, t * n, dtype=np.uint64).astype(np.uint32))
+            d_out, d_out32, d_copy = DeviceVec(4 * n), DeviceVec(32 * n), DeviceVec(4 * t * n)
+            h, b3 = Hasher.poseidon2(field, t), Hasher.blake3(4 * t)
+
+            def copy():
+                check(lib.icicle_copy(d_copy.ptr, d_in.ptr, 4 * t * n))
+                runtime.device_synchronize()
+
+            ts = all_interleaved([lambda: h.hash(d_in, size=4 * t, batch=n, out=d_out), copy, lambda: b3.hash(d_in, size=4 * t, batch=n, out=d_out32)], a.reps)
+            say(f"poseidon2 {field} t={t} batch 2^{logb} x {4 * t} B device->device: median {med(ts[0]):.3f} ms ({ts[0][0]:.3f} .. {ts[0][-1]:.3f}), "
+                f"{n / med(ts[0]) * 1e3:.3e} hashes/s | copy of the same bytes {med(ts[1]):.3f} ms | blake3 {med(ts[2]):.3f} ms | "
+                f"poseidon2 / copy {med(ts[0]) / med(ts[1]):.1f}, poseidon2 / blake3 {med(ts[0]) / med(ts[2]):.2f}")
+            for v in (d_in, d_out, d_out32, d_copy):
+                v.free()
+            h.close(), b3.close()
+        logl = a.p2_log_leaves
+        d_leaves = DeviceVec.from_host(rng.integers(0, p, 8 << logl, dtype=np.uint64).astype(np.uint32))
+        cfg = MerkleTreeConfig.default()
+        cfg.is_tree_on_device = True
+        p2_layers = [Hasher.poseidon2(field, 16, input_size=8)] + [Hasher.poseidon2(field, 2)] * logl
+        b3_layers = [Hasher.blake3(32)] + [Hasher.blake3(64)] * logl
+
+        def build(layers, es):
+            tree = MerkleTree(layers, es)
+            tree.build(d_leaves, cfg=cfg)
+            tree.close()
+
+        ts = all_interleaved([lambda: build(p2_layers, 4), lambda: build(b3_layers, 32)], a.reps)
+        say(f"poseidon2 {field} merkle build 2^{logl} leaves x 32 B (t=16 sponge, then t=2), {logl + 1} layers: median {med(ts[0]):.3f} ms "
+            f"({ts[0][0]:.3f} .. {ts[0][-1]:.3f}) | blake3 tree over the same leaves {med(ts[1]):.3f} ms | poseidon2 / blake3 {med(ts[0]) / med(ts[1]):.2f}")
+        d_leaves.free()
+    regs = poseidon2_kernel_rows()
+    for name in sorted(regs, key=lambda k: (k.split("<")[0], "koala" in k, int(k.split(", ")[1].rstrip(">")))):
+        v, sg, scratch = regs[name]
+        say(f"{name}: {v} VGPRs, {sg} SGPRs, {scratch} B of scratch per lane")
+    if a.notes:
+        with open(a.notes, "w") as f:
+            f.write("# Poseidon2 on the device: first measurement\n\n"
+                    "Written by `tools/hash_merkle_bench.py --poseidon2 --notes <this file>` on one MI355X; wall-clock times of synchronous\n"
+                    "calls with device operands, medians of interleaved rounds (lowest .. highest in brackets). No target was set for this\n"
+                    "kernel: these figures are the starting point. One lane computes one hash, the state in registers, the round loop rolled\n"
+                    "(`DESIGN.md` 9e).\n\n```\n" + "\n".join(lines) + "\n```\n")
+
+
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--poseidon2", action="store_true")
+    ap.add_argument("--p2-log-leaves", type=int, default=18)
+    ap.add_argument("--notes", default=None)
     ap.add_argument("--openings", action="store_true")
     ap.add_argument("--open-log-leaves", type=int, default=20)
     ap.add_argument("--open-counts", type=int, nargs="*", default=[200, 4000])
@@ -277,6 +373,8 @@ def main():
         return fri_bench(a)
     if a.openings:
         return openings_bench(a)
+    if a.poseidon2:
+        return poseidon2_bench(a)
     import icicle_amd
     from icicle_amd import runtime
     from icicle_amd._lib import lib
