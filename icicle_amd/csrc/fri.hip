@@ -12,18 +12,8 @@
 
 namespace icicle_hip {
 
-  template <class PR>
-  struct FriField; // field index of ntt_domain_table, and W of the extension F[x] / (x^4 - W)
-  template <>
-  struct FriField<babybear_params> {
-    static constexpr int INDEX = 0;
-    static constexpr uint32_t W = 11;
-  };
-  template <>
-  struct FriField<koalabear_params> {
-    static constexpr int INDEX = 1;
-    static constexpr uint32_t W = 3;
-  };
+  // FriField<PR> (the field's index in ntt_domain_table, and W of the extension F[x] / (x^4 - W)) is in smallfield.hpp, which the
+  // extension vector operations share
 
   // alpha for the kernel, Montgomery form: a[k] = alpha_k, aw[k] = W * alpha_k (scalar: a[0] only)
   struct FoldConsts {

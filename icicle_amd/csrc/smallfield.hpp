@@ -60,4 +60,17 @@ namespace icicle_hip {
     static SF_HD uint32_t inv(uint32_t x) { return pow(x, (uint64_t)P - 2); }
   };
 
+  template <class PR>
+  struct FriField; // field index of ntt_domain_table, and W of the extension F[x] / (x^4 - W): FRI and the extension vector operations
+  template <>
+  struct FriField<babybear_params> {
+    static constexpr int INDEX = 0;
+    static constexpr uint32_t W = 11;
+  };
+  template <>
+  struct FriField<koalabear_params> {
+    static constexpr int INDEX = 1;
+    static constexpr uint32_t W = 3;
+  };
+
 } // namespace icicle_hip

@@ -202,6 +202,13 @@ DEFINE_VEC_ARITH(grumpkin, BigElem<bn254_fq_params>, 8)
 DEFINE_VEC_ARITH(stark252, BigElem<stark252_fr_params>, 8)
 DEFINE_VEC_ARITH(goldilocks, GoldElem, 2)
 
+// extension_bit_reverse (icicle/src/vec_ops.cpp:455-464): the kernel above over the 4-word extension elements of vecops_ext.hip
+#define DEFINE_EXT_BITREV(NAME)                                                                                        \
+  extern "C" icicle_error_t NAME##_extension_bit_reverse(const void* i, uint64_t n, const icicle_vec_ops_config_t* c, void* o) { GUARDED((bitrev_run<4>(i, n, c, o))); }
+DEFINE_EXT_BITREV(babybear)
+DEFINE_EXT_BITREV(koalabear)
+DEFINE_EXT_BITREV(goldilocks)
+
 // matrix_transpose / extension_matrix_transpose (icicle/src/matrix_ops.cpp:75-102): W = u32 words per element
 #define DEFINE_TRANSPOSE(NAME, SUFFIX, W)                                                                              \
   extern "C" icicle_error_t NAME##_##SUFFIX(const void* i, uint32_t r, uint32_t c, const icicle_vec_ops_config_t* cfg, void* o) { GUARDED((transpose_run<W>(i, r, c, cfg, o))); } \

@@ -8,6 +8,7 @@ from .runtime import DeviceVec
 # u32 words per scalar (a curve name stands for its scalar field) and per base-field coordinate of a point
 _WORDS = {"bn254": 8, "bls12_381": 8, "bls12_377": 8, "grumpkin": 8, "stark252": 8, "goldilocks": 2, "babybear": 1, "koalabear": 1}
 _EXT_DEGREE = {"babybear": 4, "koalabear": 4, "goldilocks": 2}
+_EXT_WORDS = 4  # u32 words per extension element, all three extension types
 _POINT_LIMBS = {"bn254": 8, "bls12_381": 12, "bls12_377": 12, "grumpkin": 8}
 
 def _ptr(x):
@@ -50,83 +51,105 @@ def projective_convert_montgomery(curve: str, inp, to_montgomery: bool, cfg=None
     return _run(f"{curve}_projective_convert_montgomery", inp, n if n is not None else inp.size // (3 * L), to_montgomery, cfg, out)
 
 
-def _vec2(op: str, field: str, a, b, size, cfg, out):
+def _sym(field: str, op: str, extension: bool) -> str:
+    """the library symbol of `op` over `field` or over its extension field (babybear, koalabear: quartic; goldilocks: quadratic)"""
+    if not extension:
+        return f"{field}_{op}"
+    if field not in _EXT_DEGREE:
+        raise ValueError(f"{field} has no extension field: extension=True is for {sorted(_EXT_DEGREE)}")
+    return f"{field}_extension_{op}"
+
+
+def _words(field: str, extension: bool) -> int:
+    return _EXT_WORDS if extension else _WORDS[field]
+
+
+def _vec2(op: str, field: str, a, b, size, cfg, out, extension=False, b_words=None):
     """mirror of wrappers/rust/icicle-core/src/vec_ops: add / sub / mul / scalar-mul of field vectors"""
+    sym = _sym(field, op, extension)
     cfg = cfg or VecOpsConfig.default()
     ap, cfg.is_a_on_device = _ptr(a)
     bp, cfg.is_b_on_device = _ptr(b)
+    words = _words(field, extension)
     if size is None:
-        size = b.size // _WORDS[field] // max(1, cfg.batch_size)
+        size = b.size // (b_words or words) // max(1, cfg.batch_size)
     if out is None:
-        out = np.zeros_like(b)
+        out = np.zeros((size * max(1, cfg.batch_size), words), np.uint32) if b_words else np.zeros_like(b)
     op_, cfg.is_result_on_device = _ptr(out)
-    check(getattr(lib, f"{field}_{op}")(ap, bp, size, ctypes.byref(cfg), op_), f"{field}_{op}")
+    check(getattr(lib, sym)(ap, bp, size, ctypes.byref(cfg), op_), sym)
     return out
 
 
-def vector_add(field, a, b, cfg=None, out=None, size=None):
-    return _vec2("vector_add", field, a, b, size, cfg, out)
+def vector_add(field, a, b, cfg=None, out=None, size=None, extension=False):
+    return _vec2("vector_add", field, a, b, size, cfg, out, extension)
 
 
-def vector_sub(field, a, b, cfg=None, out=None, size=None):
-    return _vec2("vector_sub", field, a, b, size, cfg, out)
+def vector_sub(field, a, b, cfg=None, out=None, size=None, extension=False):
+    return _vec2("vector_sub", field, a, b, size, cfg, out, extension)
 
 
-def vector_mul(field, a, b, cfg=None, out=None, size=None):
-    return _vec2("vector_mul", field, a, b, size, cfg, out)
+def vector_mul(field, a, b, cfg=None, out=None, size=None, extension=False):
+    return _vec2("vector_mul", field, a, b, size, cfg, out, extension)
 
 
-def scalar_mul_vec(field, scalars, b, cfg=None, out=None, size=None):
+def vector_mixed_mul(field, a_ext, b_base, cfg=None, out=None, size=None):
+    """a_ext[i] * b_base[i]: an extension vector ([n, 4] words) times a base-field vector of `field`; the result is an extension vector"""
+    return _vec2("vector_mixed_mul", field, a_ext, b_base, size, cfg, out, True, b_words=_WORDS[field])
+
+
+def scalar_mul_vec(field, scalars, b, cfg=None, out=None, size=None, extension=False):
     """scalars: one per batch entry"""
-    return _vec2("scalar_mul_vec", field, scalars, b, size, cfg, out)
+    return _vec2("scalar_mul_vec", field, scalars, b, size, cfg, out, extension)
 
 
-def scalar_add_vec(field, scalars, b, cfg=None, out=None, size=None):
+def scalar_add_vec(field, scalars, b, cfg=None, out=None, size=None, extension=False):
     """scalar[k] + b[i] for every element of batch entry k; scalars: one per batch entry"""
-    return _vec2("scalar_add_vec", field, scalars, b, size, cfg, out)
+    return _vec2("scalar_add_vec", field, scalars, b, size, cfg, out, extension)
 
 
-def scalar_sub_vec(field, scalars, b, cfg=None, out=None, size=None):
+def scalar_sub_vec(field, scalars, b, cfg=None, out=None, size=None, extension=False):
     """scalar[k] - b[i] (the scalar is the minuend); scalars: one per batch entry"""
-    return _vec2("scalar_sub_vec", field, scalars, b, size, cfg, out)
+    return _vec2("scalar_sub_vec", field, scalars, b, size, cfg, out, extension)
 
 
-def vector_div(field, a, b, cfg=None, out=None, size=None):
+def vector_div(field, a, b, cfg=None, out=None, size=None, extension=False):
     """a[i] / b[i], with x / 0 = 0; in place allowed (out is a or b)"""
-    return _vec2("vector_div", field, a, b, size, cfg, out)
+    return _vec2("vector_div", field, a, b, size, cfg, out, extension)
 
 
-def _vec1(op: str, field: str, a, size, cfg, out, reduces: bool):
+def _vec1(op: str, field: str, a, size, cfg, out, reduces: bool, extension=False):
     """vector_inv (one output element per input element) and vector_sum / vector_product (one per batch entry, [batch, words])"""
+    sym = _sym(field, op, extension)
+    words = _words(field, extension)
     cfg = cfg or VecOpsConfig.default()
     ap, cfg.is_a_on_device = _ptr(a)
     batch = max(1, cfg.batch_size)
     if size is None:
         assert not isinstance(a, int), "a raw device address has no size: pass size"
-        size = a.nbytes // (4 * _WORDS[field]) // batch
+        size = a.nbytes // (4 * words) // batch
     if out is None:
         if reduces:
-            out = np.zeros((batch, _WORDS[field]), np.uint32)
+            out = np.zeros((batch, words), np.uint32)
         else:
-            out = np.zeros_like(a) if isinstance(a, np.ndarray) else np.zeros((size * batch, _WORDS[field]), np.uint32)
+            out = np.zeros_like(a) if isinstance(a, np.ndarray) else np.zeros((size * batch, words), np.uint32)
     op_, cfg.is_result_on_device = _ptr(out)
-    check(getattr(lib, f"{field}_{op}")(ap, size, ctypes.byref(cfg), op_), f"{field}_{op}")
+    check(getattr(lib, sym)(ap, size, ctypes.byref(cfg), op_), sym)
     return out
 
 
-def vector_inv(field, a, cfg=None, out=None, size=None):
+def vector_inv(field, a, cfg=None, out=None, size=None, extension=False):
     """1 / a[i], with 1 / 0 = 0; in place allowed (out is a)"""
-    return _vec1("vector_inv", field, a, size, cfg, out, False)
+    return _vec1("vector_inv", field, a, size, cfg, out, False, extension)
 
 
-def vector_sum(field, a, cfg=None, out=None, size=None):
+def vector_sum(field, a, cfg=None, out=None, size=None, extension=False):
     """the sum of each batch entry (element j of entry k at k * size + j, or at j * batch_size + k with columns_batch): [batch, words]"""
-    return _vec1("vector_sum", field, a, size, cfg, out, True)
+    return _vec1("vector_sum", field, a, size, cfg, out, True, extension)
 
 
-def vector_product(field, a, cfg=None, out=None, size=None):
+def vector_product(field, a, cfg=None, out=None, size=None, extension=False):
     """the product of each batch entry, laid out like vector_sum's: [batch, words]"""
-    return _vec1("vector_product", field, a, size, cfg, out, True)
+    return _vec1("vector_product", field, a, size, cfg, out, True, extension)
 
 
 def vector_inv_tile(field) -> int:
@@ -134,15 +157,22 @@ def vector_inv_tile(field) -> int:
     return lib.icicle_hip_vector_inv_tile(_WORDS[field])
 
 
-def bit_reverse(field, inp, cfg=None, out=None, size=None):
+def extension_vector_inv_tile(field) -> int:
+    """how many neighbouring extension elements of `field` share one base-field inversion of their norms in vector_inv / vector_div"""
+    _sym(field, "vector_inv", True)
+    return lib.icicle_hip_extension_vector_inv_tile(_WORDS[field])
+
+
+def bit_reverse(field, inp, cfg=None, out=None, size=None, extension=False):
+    sym = _sym(field, "bit_reverse", extension)
     cfg = cfg or VecOpsConfig.default()
     ip, cfg.is_a_on_device = _ptr(inp)
     if size is None:
-        size = inp.size // _WORDS[field] // max(1, cfg.batch_size)
+        size = inp.size // _words(field, extension) // max(1, cfg.batch_size)
     if out is None:
         out = np.zeros_like(inp)
     op_, cfg.is_result_on_device = _ptr(out)
-    check(getattr(lib, f"{field}_bit_reverse")(ip, size, ctypes.byref(cfg), op_), f"{field}_bit_reverse")
+    check(getattr(lib, sym)(ip, size, ctypes.byref(cfg), op_), sym)
     return out
 
 

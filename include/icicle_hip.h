@@ -297,6 +297,38 @@ ICICLE_HIP_DECLARE_VEC_INV(bls12_381)
 /* elements that share one inversion, for elements of 1, 2 or 8 words; 0 for any other width. Needs no device. */
 int icicle_hip_vector_inv_tile(int words_per_element);
 
+/* The same operations over the extension field, for the three fields that have an extension type: babybear, koalabear, goldilocks
+ * (src/vec_ops.cpp:24-64 extension_vector_product / _sum, :87-97 _vector_add, :152-162 _vector_sub, :185-210 _vector_mul and
+ * _vector_mixed_mul, :233-243 _vector_div, :265-274 _vector_inv, :297-315 _scalar_add_vec, :338-356 _scalar_sub_vec, :378-396
+ * _scalar_mul_vec, :455-464 _bit_reverse; cmake/features.cmake EXT_FIELD).
+ *  - An element is 16 bytes. babybear, koalabear: four canonical 4-byte coefficients, constant term first, of F[x] / (x^4 - W),
+ *    W = 11 and 3. goldilocks: two canonical 8-byte coefficients c0 + c1 u, u^2 = 7.
+ *  - Semantics, config and argument checks are those of the base-field functions above, over extension elements: `size` is per
+ *    batch entry, scalar_*_vec take one extension scalar per batch entry (scalar_sub_vec is scalar minus vector), columns_batch
+ *    matters to them and to sum / product only, in place is allowed, inv(0) = 0 and a / 0 = 0, sum and product give the same bytes
+ *    on every run. vector_mixed_mul multiplies an extension vector by a BASE-field vector (4 or 8 bytes per element of vec_b).
+ *    extension_bit_reverse checks its arguments as bit_reverse does.
+ *  - vector_inv / vector_div take the norm of each element down to the base field; the norms of a tile of
+ *    icicle_hip_extension_vector_inv_tile(base words) neighbours share one base-field a^(p-2) chain. */
+#define ICICLE_HIP_DECLARE_VEC_EXT(F)                                                                                  \
+  icicle_error_t F##_extension_vector_add(const void* vec_a, const void* vec_b, uint64_t size, const icicle_vec_ops_config_t* config, void* result); \
+  icicle_error_t F##_extension_vector_sub(const void* vec_a, const void* vec_b, uint64_t size, const icicle_vec_ops_config_t* config, void* result); \
+  icicle_error_t F##_extension_vector_mul(const void* vec_a, const void* vec_b, uint64_t size, const icicle_vec_ops_config_t* config, void* result); \
+  icicle_error_t F##_extension_vector_div(const void* vec_a, const void* vec_b, uint64_t size, const icicle_vec_ops_config_t* config, void* result); \
+  icicle_error_t F##_extension_vector_mixed_mul(const void* vec_a, const void* vec_b, uint64_t size, const icicle_vec_ops_config_t* config, void* result); \
+  icicle_error_t F##_extension_vector_inv(const void* vec_a, uint64_t size, const icicle_vec_ops_config_t* config, void* result); \
+  icicle_error_t F##_extension_vector_sum(const void* vec_a, uint64_t size, const icicle_vec_ops_config_t* config, void* result); \
+  icicle_error_t F##_extension_vector_product(const void* vec_a, uint64_t size, const icicle_vec_ops_config_t* config, void* result); \
+  icicle_error_t F##_extension_scalar_add_vec(const void* scalar_a, const void* vec_b, uint64_t size, const icicle_vec_ops_config_t* config, void* result); \
+  icicle_error_t F##_extension_scalar_sub_vec(const void* scalar_a, const void* vec_b, uint64_t size, const icicle_vec_ops_config_t* config, void* result); \
+  icicle_error_t F##_extension_scalar_mul_vec(const void* scalar_a, const void* vec_b, uint64_t size, const icicle_vec_ops_config_t* config, void* result); \
+  icicle_error_t F##_extension_bit_reverse(const void* input, uint64_t size, const icicle_vec_ops_config_t* config, void* output);
+ICICLE_HIP_DECLARE_VEC_EXT(babybear)
+ICICLE_HIP_DECLARE_VEC_EXT(koalabear)
+ICICLE_HIP_DECLARE_VEC_EXT(goldilocks)
+/* elements whose norms share one inversion, by the words of a BASE-field element (1 or 2); 0 for anything else. Needs no device. */
+int icicle_hip_extension_vector_inv_tile(int base_words_per_element);
+
 /* Matrix transpose of batch_size row-major nof_rows x nof_cols matrices (icicle/src/matrix_ops.cpp:75-102,
  * include/icicle/vec_ops.h:319; CPU: backend/cpu/src/field/cpu_matrix_ops.cpp:333-362): in place allowed, columns_batch
  * rejected. The Rust NTT suite calls it on the main device around every columns_batch transform
