@@ -10,7 +10,7 @@
 //   3. two-level counting sort of point indices by bucket, every scatter staged through an LDS
 //      tile-sort so that HBM sees runs, not 4-byte random writes:
 //        pass A  k_a_count / k_scan_a / k_a_scatter     partition by the high hb bits of the key
-//        pass B  k_b_plan / k_b_count / k_scan_buckets / k_b_scatter   sort by the low lb bits
+//        pass B  k_b_owned (a partition per block) | k_b_plan / k_b_count / k_b_scan_part / k_b_scatter (sub-chunks): by the low lb bits
 //      (c <= 11: pass A alone sorts by the whole key, k_a_scatter<true> + k_tables_from_a)
 //   4. k_accumulate      ONE THREAD PER BUCKET walks its sorted index list, gathers the 64 B affine
 //      point and does an XYZZ mixed add entirely in registers -- ~77 % of the time at 2^26,
@@ -71,10 +71,16 @@ namespace icicle_hip {
   //   pass A:   block (b, window) owns digits [b*chunk, (b+1)*chunk) of that window and partitions
   //             them by the HIGH hb bits of the bucket key. Element = sign | low key bits | j |
   //             index within chunk.
-  //   pass B:   blocks own sub-chunks (<= 2^17 elements) of one (window, partition) and sort them
-  //             by the LOW lb key bits; each (tile, bin) run reserves its slot in the bucket with
-  //             one global atomic. The source block of an element (needed to rebuild its global
-  //             scalar index) is found by a binary search in the partition's per-block offset row.
+  //   pass B:   sorts every (window, partition) by the LOW lb key bits, on one of two routes.
+  //             Owned (a partition of at most own_max = 2^18 elements, i.e. every partition of a large
+  //             MSM with spread scalars): ONE block histograms the partition in LDS, scans the
+  //             histogram, writes count[] / offs[] of its 2^lb buckets and keeps the write cursors
+  //             in LDS -- no global atomic, no counter memset, no window-wide scan (k_b_owned).
+  //             Sub-chunks (a larger partition: skewed scalars, a sparse top window): blocks own
+  //             <= 2^17 elements each; counts are added up in count[], scanned per partition, and
+  //             each (tile, bin) run reserves its slot in the bucket with one global atomic.
+  //             The source block of an element (needed to rebuild its global scalar index) is
+  //             found by a binary search in the partition's per-block offset row.
   // Output is what bucket accumulation consumes: count[], offs[], sorted[] (point index | sign<<31).
   struct SortPlan {
     int hb, lb;       // high / low bucket-key bits, hb + lb = c - 1
@@ -469,31 +475,37 @@ namespace icicle_hip {
     count[t] = pe - ps;
   }
 
-  // pass B. A partition (window wp, high key bits h) is cut into sub-chunks of CHUNKB elements, one
-  // block each, so neither a sparse top window nor skewed scalars can serialise it on one block.
-  // k_b_plan turns partition sizes into a block -> (partition, sub-chunk) table; k_b_count adds LDS
-  // histograms of the low lb key bits into count[]; k_scan_buckets makes offs[]/cursor[];
-  // k_b_scatter reserves a range per (block, bin) with ONE global atomic and ranks inside it in LDS.
+  // pass B, sub-chunk route. A partition (window wp, high key bits h) that k_b_owned does not take is cut into
+  // sub-chunks of CHUNKB elements, one block each, so neither a sparse top window nor skewed scalars can serialise
+  // it on one block. k_b_plan turns partition sizes into a block -> (partition, sub-chunk) table; k_b_count adds LDS
+  // histograms of the low lb key bits into count[]; k_b_scan_part (window-wide k_scan_* when nothing is owned) makes
+  // offs[]/cursor[]; k_b_scatter reserves a range per (block, bin) with ONE global atomic and ranks inside it in LDS.
   constexpr uint32_t CHUNKB_LOG = 17;
+  // A partition of at most this many elements is sorted whole by ONE block (k_b_owned below) instead of in sub-chunks. At
+  // 2^26 terms a partition holds 2^16 (wide windows) or 2^17 elements, so 2^18 is more than 300 sigma above the mean: only
+  // skewed scalars exceed it, and those keep the sub-chunks. MSMConfig.ext "hip_msm_passb_own_max" overrides (0: none owned).
+  constexpr uint32_t PASSB_OWN_MAX_DEFAULT = 1u << 18;
 
-  static __global__ __launch_bounds__(1024) void k_b_plan(const uint32_t* __restrict__ offA, uint32_t* __restrict__ bstart, uint32_t nparts, int wpf, int hb, int nblk, uint32_t p0)
+  static __global__ __launch_bounds__(1024) void k_b_plan(const uint32_t* __restrict__ offA, uint32_t* __restrict__ bstart, uint32_t nparts, int wpf, int hb, int nblk, uint32_t p0, uint32_t own_max)
   {
     // plans partitions [p0, p0 + nparts) (one window group); bstart[] is local to the group, wpf = windows of the whole launch
+    // own_max > 0: a partition of at most own_max elements belongs to k_b_owned and gets no sub-chunk here
     __shared__ uint32_t part[1024];
     const uint32_t per = (nparts + 1023) / 1024;
     const uint32_t lo = min(nparts, threadIdx.x * per), hi = min(nparts, lo + per);
     const uint32_t nparts_w = 1u << hb;
-    auto psize = [&](uint32_t pl) -> uint32_t {
+    auto nchunks = [&](uint32_t pl) -> uint32_t {
       const uint32_t p = p0 + pl;
       const uint32_t wp = p >> hb, h = p & (nparts_w - 1);
       const size_t row = (size_t)p * nblk;
       const uint32_t ps = offA[row];
       const uint32_t pe = (h + 1 < nparts_w) ? offA[row + nblk] : offA[(size_t)wpf * nparts_w * nblk + wp];
-      return pe - ps;
+      if (own_max && pe - ps <= own_max) return 0;
+      return (pe - ps + (1u << CHUNKB_LOG) - 1) >> CHUNKB_LOG;
     };
     uint32_t s = 0;
     for (uint32_t p = lo; p < hi; p++)
-      s += (psize(p) + (1u << CHUNKB_LOG) - 1) >> CHUNKB_LOG;
+      s += nchunks(p);
     part[threadIdx.x] = s;
     __syncthreads();
     for (int d = 1; d < 1024; d <<= 1) {
@@ -505,7 +517,7 @@ namespace icicle_hip {
     uint32_t run = part[threadIdx.x] - s;
     for (uint32_t p = lo; p < hi; p++) {
       bstart[p] = run;
-      run += (psize(p) + (1u << CHUNKB_LOG) - 1) >> CHUNKB_LOG;
+      run += nchunks(p);
     }
     if (threadIdx.x == 1023) bstart[nparts] = part[1023];
   }
@@ -566,13 +578,15 @@ namespace icicle_hip {
       if (lds[k]) atomicAdd(&cw[k], lds[k]);
   }
 
-  template <int TPB>
-  __global__ __launch_bounds__(TPB) void k_b_scatter(const uint32_t* __restrict__ inA, const uint32_t* __restrict__ offA, const uint32_t* __restrict__ bstart, uint32_t* __restrict__ cursor, uint32_t* __restrict__ sorted, uint32_t nparts, int wpf, int pf, SortPlan sp, size_t cap, uint32_t nb, uint32_t p0)
+  // The tile loop of pass B over elements [r0, r1) of partition p, shared by both routes. OWNED = false: `cw` is the
+  // partition's row of the global cursor array and a (tile, bin) run is reserved with one returning atomic; OWNED = true:
+  // the block is the only writer of the partition's buckets, `cw` is its cursor[D] in LDS and the reservation is a plain
+  // read-modify-write by the thread that owns the bin.
+  template <int TPB, bool OWNED>
+  __device__ __forceinline__ void b_sort_range(uint32_t* lds, const uint32_t* __restrict__ inA, const uint32_t* __restrict__ offA, uint32_t* cw, uint32_t* __restrict__ sorted, int wpf, int pf, const SortPlan& sp, size_t cap, uint32_t p, uint32_t r0, uint32_t r1)
   {
-    extern __shared__ uint32_t lds[]; // tile-sort arrays | [nblk+1] piece offsets of this partition
+    // lds: tile-sort arrays | [nblk+1] piece offsets of this partition | [TS / 64] group -> source block
     constexpr uint32_t TS = (uint32_t)TPB * SORT_EPT;
-    uint32_t p, r0, r1;
-    if (!b_locate(bstart, offA, nparts, wpf, sp.hb, sp.nblk, p0, p, r0, r1)) return;
     const uint32_t D = 1u << sp.lb;
     const uint32_t R = (D + TPB - 1) / TPB, k0 = threadIdx.x * R; // bins [k0, k0 + R) belong to this thread
     TileLds t = tile_lds(lds, D, TS);
@@ -586,7 +600,6 @@ namespace icicle_hip {
     __syncthreads();
     const uint32_t* src = inA + (size_t)wp * cap;
     uint32_t* dst = sorted + (size_t)wp * cap;
-    uint32_t* cw = cursor + (size_t)wp * nb + ((size_t)h << sp.lb);
     const int lshift = 31 - sp.lb;
     const uint32_t lmask = D - 1;
     const uint32_t imask = (1u << (31 - sp.lb - sp.jb)) - 1;
@@ -652,7 +665,12 @@ namespace icicle_hip {
           if (k0 + r < D) {
             const uint32_t c1 = t.cnt[k0 + r];
             t.cnt[k0 + r] = toff;
-            t.gbase[k0 + r] = c1 ? atomicAdd(&cw[k0 + r], c1) : 0u; // reserve the run in the bucket list
+            if constexpr (OWNED) {
+              t.gbase[k0 + r] = cw[k0 + r];
+              cw[k0 + r] += c1;
+            } else {
+              t.gbase[k0 + r] = c1 ? atomicAdd(&cw[k0 + r], c1) : 0u; // reserve the run in the bucket list
+            }
             toff += c1;
           }
       }
@@ -677,6 +695,106 @@ namespace icicle_hip {
       }
       __syncthreads();
     }
+  }
+
+  template <int TPB>
+  __global__ __launch_bounds__(TPB) void k_b_scatter(const uint32_t* __restrict__ inA, const uint32_t* __restrict__ offA, const uint32_t* __restrict__ bstart, uint32_t* __restrict__ cursor, uint32_t* __restrict__ sorted, uint32_t nparts, int wpf, int pf, SortPlan sp, size_t cap, uint32_t nb, uint32_t p0)
+  {
+    extern __shared__ uint32_t lds[];
+    uint32_t p, r0, r1;
+    if (!b_locate(bstart, offA, nparts, wpf, sp.hb, sp.nblk, p0, p, r0, r1)) return;
+    const uint32_t wp = p >> sp.hb, h = p & ((1u << sp.hb) - 1);
+    b_sort_range<TPB, false>(lds, inA, offA, cursor + (size_t)wp * nb + ((size_t)h << sp.lb), sorted, wpf, pf, sp, cap, p, r0, r1);
+  }
+
+  // pass B, owned route: block blockIdx.x sorts the WHOLE partition p0 + blockIdx.x when it holds at most own_max
+  // elements (k_b_plan gives such a partition no sub-chunk, so the kernels above never see it). Its 2^lb bucket lists lie
+  // contiguously in `sorted` from the partition's start ps in the pass-A array (both arrays are [window][cap] and the
+  // partitions are ordered by h), and nobody else writes them: the block histograms the partition in LDS, scans the
+  // histogram in LDS, writes count[] / offs[] of EVERY one of its buckets -- of an empty partition too: k_accumulate
+  // forms sorted + offs[bucket] before it looks at the count -- and keeps the write cursors in LDS, as k_a_scatter does.
+  // A block whose partition is larger only zeroes its buckets' count[] for k_b_count.
+  template <int TPB>
+  __global__ __launch_bounds__(TPB) void k_b_owned(const uint32_t* __restrict__ inA, const uint32_t* __restrict__ offA, uint32_t* __restrict__ count, uint32_t* __restrict__ offs, uint32_t* __restrict__ sorted, int wpf, int pf, SortPlan sp, size_t cap, uint32_t nb, uint32_t p0, uint32_t own_max)
+  {
+    extern __shared__ uint32_t lds[]; // b_sort_range's arrays | [D] write cursor per bin (the histogram of sweep 1 first)
+    constexpr uint32_t TS = (uint32_t)TPB * SORT_EPT;
+    const uint32_t p = p0 + blockIdx.x;
+    const uint32_t D = 1u << sp.lb, nparts_w = 1u << sp.hb;
+    const uint32_t wp = p >> sp.hb, h = p & (nparts_w - 1);
+    const size_t row = (size_t)p * sp.nblk;
+    const uint32_t ps = offA[row];
+    const uint32_t pe = (h + 1 < nparts_w) ? offA[row + sp.nblk] : offA[(size_t)wpf * nparts_w * sp.nblk + wp];
+    uint32_t* cnt_p = count + (size_t)wp * nb + ((size_t)h << sp.lb);
+    uint32_t* offs_p = offs + (size_t)wp * nb + ((size_t)h << sp.lb);
+    if (pe - ps > own_max) {
+      for (uint32_t k = threadIdx.x; k < D; k += TPB)
+        cnt_p[k] = 0;
+      return;
+    }
+    uint32_t* cursor = lds + tile_lds_bytes(D, TS) / 4 + sp.nblk + 1 + TS / 64;
+    for (uint32_t k = threadIdx.x; k < D; k += TPB)
+      cursor[k] = 0;
+    __syncthreads();
+    { // sweep 1 in a scope of its own: its load registers are dead before the tile arrays of sweep 2 exist
+      const uint32_t* src = inA + (size_t)wp * cap;
+      const int lshift = 31 - sp.lb;
+      const uint32_t lmask = D - 1;
+      for (uint32_t q0 = ps + threadIdx.x; q0 < pe; q0 += 8 * TPB) {
+        uint32_t v[8];
+#pragma unroll
+        for (int u = 0; u < 8; u++) { // all loads first, see k_a_count
+          const uint32_t pos = q0 + u * TPB;
+          v[u] = pos < pe ? src[pos] : 0u;
+        }
+#pragma unroll
+        for (int u = 0; u < 8; u++)
+          if (q0 + u * TPB < pe) atomicAdd(&cursor[(v[u] >> lshift) & lmask], 1u);
+      }
+    }
+    __syncthreads();
+    {
+      const uint32_t R = (D + TPB - 1) / TPB, k0 = threadIdx.x * R; // the bins b_sort_range gives this thread
+      uint32_t mysum = 0;
+      for (uint32_t r = 0; r < R; r++)
+        if (k0 + r < D) mysum += cursor[k0 + r];
+      uint32_t run = ps + block_exscan(mysum, tile_lds(lds, D, TS).wsum);
+      for (uint32_t r = 0; r < R; r++)
+        if (k0 + r < D) {
+          const uint32_t c1 = cursor[k0 + r];
+          cnt_p[k0 + r] = c1;
+          offs_p[k0 + r] = run;
+          cursor[k0 + r] = run;
+          run += c1;
+        }
+    }
+    b_sort_range<TPB, true>(lds, inA, offA, cursor, sorted, wpf, pf, sp, cap, p, ps, pe); // (starts with a barrier)
+  }
+
+  // offs[] / cursor[] of the partitions k_b_owned left to the sub-chunk route, one block per partition: the same
+  // offs = ps + prefix, from the counts k_b_count added up. Owned partitions return at once.
+  static __global__ __launch_bounds__(1024) void k_b_scan_part(const uint32_t* __restrict__ offA, const uint32_t* __restrict__ count, uint32_t* __restrict__ offs, uint32_t* __restrict__ cursor, int wpf, SortPlan sp, uint32_t nb, uint32_t p0, uint32_t own_max)
+  {
+    __shared__ uint32_t wsum[32];
+    const uint32_t p = p0 + blockIdx.x;
+    const uint32_t D = 1u << sp.lb, nparts_w = 1u << sp.hb;
+    const uint32_t wp = p >> sp.hb, h = p & (nparts_w - 1);
+    const size_t row = (size_t)p * sp.nblk;
+    const uint32_t ps = offA[row];
+    const uint32_t pe = (h + 1 < nparts_w) ? offA[row + sp.nblk] : offA[(size_t)wpf * nparts_w * sp.nblk + wp];
+    if (pe - ps <= own_max) return;
+    const size_t b0 = (size_t)wp * nb + ((size_t)h << sp.lb);
+    const uint32_t R = (D + 1023) / 1024, k0 = threadIdx.x * R;
+    uint32_t mysum = 0;
+    for (uint32_t r = 0; r < R; r++)
+      if (k0 + r < D) mysum += count[b0 + k0 + r];
+    uint32_t run = ps + block_exscan(mysum, wsum);
+    for (uint32_t r = 0; r < R; r++)
+      if (k0 + r < D) {
+        offs[b0 + k0 + r] = run;
+        cursor[b0 + k0 + r] = run;
+        run += count[b0 + k0 + r];
+      }
   }
 
   // ------------------------------------------------------------------------------------------
@@ -1735,6 +1853,17 @@ namespace icicle_hip {
     HIP_TRY(hipFuncSetAttribute((const void*)k_a_scatter<true, 1024>, hipFuncAttributeMaxDynamicSharedMemorySize, 156 * 1024), ICICLE_INVALID_ARGUMENT);
     HIP_TRY(hipFuncSetAttribute((const void*)k_b_count, hipFuncAttributeMaxDynamicSharedMemorySize, 156 * 1024), ICICLE_INVALID_ARGUMENT);
     HIP_TRY(hipFuncSetAttribute((const void*)k_b_scatter<1024>, hipFuncAttributeMaxDynamicSharedMemorySize, 156 * 1024), ICICLE_INVALID_ARGUMENT);
+    // pass B, owned route (k_b_owned): partitions of at most own_max elements; 0 = none, every partition takes the sub-chunk route
+    uint32_t own_max = PASSB_OWN_MAX_DEFAULT;
+    if (cfg->ext) own_max = (uint32_t)std::max(0, reinterpret_cast<const ConfigExt*>(cfg->ext)->get_int("hip_msm_passb_own_max", (int)own_max));
+    const size_t ldsOwn = ldsB + ((size_t)4 << sp.lb); // + the write cursors
+    if (own_max && !single_level) {
+      int dev = 0, lds_dev = 0;
+      HIP_TRY(hipGetDevice(&dev), ICICLE_INVALID_DEVICE);
+      HIP_TRY(hipDeviceGetAttribute(&lds_dev, hipDeviceAttributeMaxSharedMemoryPerBlock, dev), ICICLE_INVALID_DEVICE);
+      if (ldsOwn > (size_t)lds_dev) return ICICLE_INVALID_ARGUMENT;
+      HIP_TRY(hipFuncSetAttribute((const void*)k_b_owned<1024>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)ldsOwn), ICICLE_INVALID_ARGUMENT);
+    }
 
     uint32_t* dig = d_dig.as<uint32_t>();
     uint32_t* cntA = d_cntA.as<uint32_t>();
@@ -1862,12 +1991,22 @@ namespace icicle_hip {
           if (coresident) k_a_scatter<false, CO_TPB><<<dim3(sp.nblk, (unsigned)nw), CO_TPB, ldsA_co, sq>>>(dig, offA, partA, n, pl.nwin, wpf, pf, sp, cap, w0);
           else k_a_scatter<false, 1024><<<dim3(sp.nblk, (unsigned)nw), 1024, ldsA, sq>>>(dig, offA, partA, n, pl.nwin, wpf, pf, sp, cap, w0);
           LAUNCH_CHECK("k_a_scatter", sq);
-          k_b_plan<<<1, 1024, 0, sq>>>(offA, bstart, np_g, (int)tw, sp.hb, sp.nblk, p0);
+          // partitions of at most own_g elements: k_b_owned, one block each; the others (and all of them when own_g == 0):
+          // sub-chunks. The host cannot know which kind it has, so both routes are launched; an idle one returns at once.
+          const uint32_t own_g = coresident ? 0u : own_max;
+          k_b_plan<<<1, 1024, 0, sq>>>(offA, bstart, np_g, (int)tw, sp.hb, sp.nblk, p0, own_g);
           LAUNCH_CHECK("k_b_plan", sq);
-          HIP_TRY(hipMemsetAsync(count + bk0, 0, nbk_g * 4, sq), ICICLE_COPY_FAILED);
+          if (own_g) {
+            k_b_owned<1024><<<np_g, 1024, ldsOwn, sq>>>(partA, offA, count, offs, sorted, (int)tw, pf, sp, cap, nb, p0, own_g);
+            LAUNCH_CHECK("k_b_owned", sq);
+          } else {
+            HIP_TRY(hipMemsetAsync(count + bk0, 0, nbk_g * 4, sq), ICICLE_COPY_FAILED);
+          }
           k_b_count<<<nblkB, 1024, ((size_t)1 << sp.lb) * 4, sq>>>(partA, offA, bstart, count, np_g, (int)tw, sp, cap, nb, p0);
           LAUNCH_CHECK("k_b_count", sq);
-          {
+          if (own_g) {
+            k_b_scan_part<<<np_g, 1024, 0, sq>>>(offA, count, offs, d_cursor.as<uint32_t>(), (int)tw, sp, nb, p0, own_g);
+          } else {
             const uint32_t nch = (nb + SCAN_CHUNK - 1) / SCAN_CHUNK;
             k_scan_sums<<<dim3(nch, (unsigned)nw), 1024, 0, sq>>>(count + bk0, scan_g, nb);
             k_scan_apply<<<dim3(nch, (unsigned)nw), 1024, 0, sq>>>(count + bk0, scan_g, offs + bk0, d_cursor.as<uint32_t>() + bk0, nullptr, nb);

@@ -768,6 +768,9 @@ icicle_error_t icicle_hip_workspace_bytes(size_t* bytes);
  *                                    to the scalar bits, the top ones one bit wider, with the reference's negate-if-top-bit-set trick
  *                                    (cpu_msm.hpp:276-277). The cost model picks such a plan by itself from 2^23 terms up (BN254 2^26:
  *                                    10 x 21 + 2 x 22 bits); the key forces one at any size (parity tests, A/B runs)
+ *   "hip_msm_passb_own_max"    int   msm (test hook): pass B of the two-level sort lets ONE block sort a whole (window, high key bits)
+ *                                    partition of at most this many elements, with its histogram, scan and write cursors in LDS;
+ *                                    larger partitions are cut into sub-chunks. 0: no partition is sorted that way; absent: 2^18
  *   "hip_force_rccl"           bool  msm, ntt: take the RCCL exchanges even with one device slot -- all-gather, and the grouped
  *                                    ncclSend / ncclRecv of the bucket exchange and of the split transform as sends to
  *                                    the own rank of a size-1 communicator (test hook: the real librccl on one GPU)

@@ -161,8 +161,10 @@ struct HipExt {
     if (!e) return;
     const bool nd = e->has("hip_num_devices"), xb = e->has("hip_msm_exchange_buckets"), rb = e->has("hip_bases_resident"), fr = e->has("hip_force_rccl");
     const bool bg = e->has("hip_bases_generation"), mw = e->has("hip_msm_windows");
-    if (!nd && !xb && !rb && !fr && !bg && !mw) return;
+    const bool om = e->has("hip_msm_passb_own_max");
+    if (!nd && !xb && !rb && !fr && !bg && !mw && !om) return;
     h = icicle_hip_create_config_extension();
+    if (om) icicle_hip_config_extension_set_int(h, "hip_msm_passb_own_max", e->get<int>("hip_msm_passb_own_max"));
     if (bg) icicle_hip_config_extension_set_int(h, "hip_bases_generation", e->get<int>("hip_bases_generation"));
     if (mw) icicle_hip_config_extension_set_int(h, "hip_msm_windows", e->get<int>("hip_msm_windows"));
     if (nd) icicle_hip_config_extension_set_int(h, "hip_num_devices", e->get<int>("hip_num_devices"));
