@@ -31,8 +31,14 @@
 #ifdef BIGFIELD_BOUNDS
   #include <cassert>
   #include <cstdio>
-  #define BF_BOUND_DECL double bnd = 0;
-  #define BF_SET_BOUND(x, v) (x).bnd = (v)
+  // bnd: the unsigned operations' value bound. The signed layer's record (sg set; see "signed layer" below): value in
+  // [slo, shi] units of p, limbs 0..N-2 in [llo, lhi], top limb in [tlo, thi]. An element of the signed layer has bnd = 1e300,
+  // so every unsigned operation that is handed one trips its own precondition.
+  #define BF_BOUND_DECL                                                                                                \
+    double bnd = 0;                                                                                                    \
+    bool sg = false;                                                                                                   \
+    double slo = 0, shi = 0, llo = 0, lhi = 0, tlo = 0, thi = 0;
+  #define BF_SET_BOUND(x, v) ((x).bnd = (v), (x).sg = false)
   #define BF_ASSERT(cond, msg)                                                                                         \
     do {                                                                                                               \
       if (!(cond)) {                                                                                                   \
@@ -356,6 +362,365 @@ namespace icicle_hip {
       r.bnd = a.bnd > b.bnd ? a.bnd : b.bnd;
 #endif
       return r;
+    }
+
+    // ---- signed layer: the same radix, SIGNED limbs, no carry chains ------------------------------------------------------
+    // The operations above keep every limb in [0, 2^29): a subtraction adds K*p to stay non-negative and every add / sub walks a
+    // serial carry chain (3-4 instructions per limb). Nothing downstream needs that: v_mad_i64_i32 issues at the rate of
+    // v_mad_u64_u32 (profiles/r02_alu_ubench.txt), so a product can take signed limbs into a signed column accumulator, and
+    // then every linear step is ONE instruction per limb with no carry and no K*p. An element of this layer is the integer
+    // sum_i (int32)l[i] * 2^(29 i), which may be negative; the limbs stay in uint32_t storage and are reinterpreted (two's
+    // complement), so nothing here is undefined behaviour.
+    //   sadd / ssub / sneg / sadd2 (2a + b) / scneg   limb-wise, no carry: limb ranges add up
+    //   snormalise                                    one signed carry pass: limbs 0..N-2 back in [0, 2^29), signed top limb
+    //   smul / ssqr / smul_add / *_inplace            Montgomery products of signed operands: (a b + m p) / R with 0 <= m < R, so a
+    //                                                 result lies in (a b / R, a b / R + p) and comes out normalised (signed top)
+    //   to_unsigned<K>                                a + K p, carry-normalised: back to the operations above (cold paths)
+    // What bounds the limbs is the column accumulator: |sum of products| + m p + carry must stay below 2^63, and a limb-wise
+    // result must fit an int32. Under -DBIGFIELD_BOUNDS every element of this layer carries a two-sided value bound (units of
+    // p), the range of its limbs 0..N-2 and the range of its top limb; every product asserts its columns one by one, every
+    // linear operation asserts the int32 range. (Ranges, not magnitudes: the difference of two normalised elements has limbs
+    // in (-2^29, 2^29), not below 2^30 -- ec.hpp's madd needs exactly that.) An element of the unsigned operations is a valid
+    // operand here (limbs in [0, 2^29), value in [0, bnd p]); the reverse needs to_unsigned.
+#ifdef BIGFIELD_BOUNDS
+    struct SB {
+      double lo, hi;   // value, units of p
+      double llo, lhi; // limbs 0..N-2
+      double tlo, thi; // limb N-1
+    };
+    static constexpr double I32_LIM = 2147483647.0;
+    // top limb of a NORMALISED element (limbs 0..N-2 in [0, 2^29)) of value v in [lo, hi] p: floor(v / 2^(29 (N-1))), and
+    // p < (P[N-1] + 1) 2^(29 (N-1)); one unit of slack for the rounding of the doubles
+    static void top_range(double lo, double hi, double& tlo, double& thi)
+    {
+      const double pt = (double)PR::P[N - 1] + 1.0;
+      tlo = lo < 0 ? __builtin_floor(lo * pt) - 1.0 : 0.0;
+      thi = hi > 0 ? __builtin_ceil(hi * pt) + 1.0 : 0.0;
+    }
+    static SB normalised(double lo, double hi)
+    {
+      SB s;
+      s.lo = lo, s.hi = hi, s.llo = 0, s.lhi = (double)MASK;
+      top_range(lo, hi, s.tlo, s.thi);
+      return s;
+    }
+    static SB sview(const fe& a)
+    {
+      if (!a.sg) return normalised(0, a.bnd);
+      SB s;
+      s.lo = a.slo, s.hi = a.shi, s.llo = a.llo, s.lhi = a.lhi, s.tlo = a.tlo, s.thi = a.thi;
+      return s;
+    }
+    static void sset(fe& r, const SB& s)
+    {
+      BF_ASSERT(s.llo >= -I32_LIM && s.lhi <= I32_LIM && s.tlo >= -I32_LIM && s.thi <= I32_LIM, "signed layer: a limb can leave int32");
+      r.sg = true, r.bnd = 1e300;
+      r.slo = s.lo, r.shi = s.hi, r.llo = s.llo, r.lhi = s.lhi, r.tlo = s.tlo, r.thi = s.thi;
+    }
+    static double smag(const SB& s, int i)
+    {
+      const double lo = i == N - 1 ? s.tlo : s.llo, hi = i == N - 1 ? s.thi : s.lhi;
+      return -lo > hi ? -lo : hi;
+    }
+    // worst case of every column of the product scanning: sum |x_i| |y_j| over the operand pairs + sum m_i p_j + carry < 2^63
+    static void scolumns(const SB* x, const SB* y, int npairs)
+    {
+      unsigned __int128 carry = 0;
+      for (int k = 0; k < 2 * N - 1; k++) {
+        unsigned __int128 col = carry;
+        const int lo = k < N ? 0 : k - N + 1, hi = k < N ? k : N - 1;
+        for (int i = lo; i <= hi; i++) {
+          for (int q = 0; q < npairs; q++)
+            col += (unsigned __int128)(uint64_t)smag(x[q], i) * (uint64_t)smag(y[q], k - i);
+          col += (unsigned __int128)MASK * PR::P[k - i];
+        }
+        BF_ASSERT(col < ((unsigned __int128)1 << 63), "signed product: a column accumulator can leave int64");
+        carry = (col >> RB) + 1;
+      }
+    }
+    static void prod_range(const SB& a, const SB& b, double& lo, double& hi)
+    {
+      const double v[4] = {a.lo * b.lo, a.lo * b.hi, a.hi * b.lo, a.hi * b.hi};
+      lo = hi = v[0];
+      for (int i = 1; i < 4; i++) {
+        lo = v[i] < lo ? v[i] : lo;
+        hi = v[i] > hi ? v[i] : hi;
+      }
+    }
+    static void sset_mul(fe& r, const fe& a, const fe& b)
+    {
+      const SB x = sview(a), y = sview(b);
+      scolumns(&x, &y, 1);
+      double lo, hi;
+      prod_range(x, y, lo, hi);
+      sset(r, normalised(lo / r_over_p(), hi / r_over_p() + 1.0));
+    }
+    static void sset_mul_add(fe& r, const fe& a, const fe& b, const fe& c, const fe& d)
+    {
+      const SB x[2] = {sview(a), sview(c)}, y[2] = {sview(b), sview(d)};
+      scolumns(x, y, 2);
+      double lo0, hi0, lo1, hi1;
+      prod_range(x[0], y[0], lo0, hi0);
+      prod_range(x[1], y[1], lo1, hi1);
+      sset(r, normalised((lo0 + lo1) / r_over_p(), (hi0 + hi1) / r_over_p() + 1.0));
+    }
+    // test hooks: claim a record for an element built by hand (as BF_SET_BOUND does for the unsigned operations)
+    static void sclaim(fe& a, double lo, double hi, double llo, double lhi, double tlo, double thi)
+    {
+      SB s;
+      s.lo = lo, s.hi = hi, s.llo = llo, s.lhi = lhi, s.tlo = tlo, s.thi = thi;
+      sset(a, s);
+    }
+#endif
+    // Tracker only: assert that a's value lies in [lo, hi] p and that it is normalised, then WIDEN its record to exactly that. A loop
+    // that does this to its carried state at the top of every step proves "invariant in => invariant out" in one step,
+    // whatever the history (ec.hpp madd).
+    static HD void sassume_normalised(fe& a, double lo, double hi)
+    {
+#ifdef BIGFIELD_BOUNDS
+      const SB s = sview(a);
+      BF_ASSERT(s.lo >= lo && s.hi <= hi, "signed layer: value outside the stated invariant");
+      BF_ASSERT(s.llo >= 0 && s.lhi <= (double)MASK, "signed layer: operand must be normalised");
+      sset(a, normalised(lo, hi));
+#else
+      (void)a, (void)lo, (void)hi;
+#endif
+    }
+    // Tracker only: a's limbs 0..N-2 lie in (-2^29, 2^29) and its value in [lo, hi] p (a gathered operand, negated limb-wise or not)
+    static HD void sassert_operand(const fe& a, double lo, double hi)
+    {
+#ifdef BIGFIELD_BOUNDS
+      const SB s = sview(a);
+      BF_ASSERT(s.lo >= lo && s.hi <= hi, "signed layer: operand value outside the stated range");
+      BF_ASSERT(s.llo >= -(double)MASK && s.lhi <= (double)MASK, "signed layer: operand limb outside (-2^29, 2^29)");
+#else
+      (void)a, (void)lo, (void)hi;
+#endif
+    }
+
+    static HD fe sadd(const fe& a, const fe& b)
+    {
+      fe r;
+#pragma unroll
+      for (int i = 0; i < N; i++)
+        r.l[i] = a.l[i] + b.l[i];
+#ifdef BIGFIELD_BOUNDS
+      const SB x = sview(a), y = sview(b);
+      sset(r, SB{x.lo + y.lo, x.hi + y.hi, x.llo + y.llo, x.lhi + y.lhi, x.tlo + y.tlo, x.thi + y.thi});
+#endif
+      return r;
+    }
+    static HD fe ssub(const fe& a, const fe& b)
+    {
+      fe r;
+#pragma unroll
+      for (int i = 0; i < N; i++)
+        r.l[i] = a.l[i] - b.l[i];
+#ifdef BIGFIELD_BOUNDS
+      const SB x = sview(a), y = sview(b);
+      sset(r, SB{x.lo - y.hi, x.hi - y.lo, x.llo - y.lhi, x.lhi - y.llo, x.tlo - y.thi, x.thi - y.tlo});
+#endif
+      return r;
+    }
+    static HD fe sneg(const fe& a)
+    {
+      fe r;
+#pragma unroll
+      for (int i = 0; i < N; i++)
+        r.l[i] = 0u - a.l[i];
+#ifdef BIGFIELD_BOUNDS
+      const SB x = sview(a);
+      sset(r, SB{-x.hi, -x.lo, -x.lhi, -x.llo, -x.thi, -x.tlo});
+#endif
+      return r;
+    }
+    // 2a + b (one v_lshl_add_u32 per limb)
+    static HD fe sadd2(const fe& a, const fe& b)
+    {
+      fe r;
+#pragma unroll
+      for (int i = 0; i < N; i++)
+        r.l[i] = (a.l[i] << 1) + b.l[i];
+#ifdef BIGFIELD_BOUNDS
+      const SB x = sview(a), y = sview(b);
+      sset(r, SB{2 * x.lo + y.lo, 2 * x.hi + y.hi, 2 * x.llo + y.llo, 2 * x.lhi + y.lhi, 2 * x.tlo + y.tlo, 2 * x.thi + y.thi});
+#endif
+      return r;
+    }
+    // negate ? -a : a, limb-wise: (l ^ s) + (s & 1) with s = 0 or ~0 (one v_xad_u32 per limb)
+    static HD fe scneg(const fe& a, bool negate)
+    {
+      fe r;
+      const uint32_t s = negate ? 0xffffffffu : 0u, o = negate ? 1u : 0u;
+#pragma unroll
+      for (int i = 0; i < N; i++)
+        r.l[i] = (a.l[i] ^ s) + o;
+#ifdef BIGFIELD_BOUNDS
+      const SB x = sview(a);
+      auto mn = [](double u, double v) { return u < v ? u : v; };
+      auto mx = [](double u, double v) { return u > v ? u : v; };
+      sset(r, SB{mn(x.lo, -x.hi), mx(x.hi, -x.lo), mn(x.llo, -x.lhi), mx(x.lhi, -x.llo), mn(x.tlo, -x.thi), mx(x.thi, -x.tlo)});
+#endif
+      return r;
+    }
+    // one signed carry pass: same value, limbs 0..N-2 in [0, 2^29), signed top limb
+    static HD fe snormalise(const fe& a)
+    {
+      fe r;
+      int32_t c = 0;
+#pragma unroll
+      for (int i = 0; i < N - 1; i++) {
+        const int32_t t = (int32_t)a.l[i] + c;
+        r.l[i] = (uint32_t)t & MASK;
+        c = t >> RB; // arithmetic
+      }
+      r.l[N - 1] = a.l[N - 1] + (uint32_t)c;
+#ifdef BIGFIELD_BOUNDS
+      const SB x = sview(a);
+      double clo = 0, chi = 0;
+      for (int i = 0; i < N - 1; i++) {
+        BF_ASSERT(x.llo + clo >= -I32_LIM && x.lhi + chi <= I32_LIM, "snormalise: limb + carry can leave int32");
+        clo = __builtin_floor((x.llo + clo) / (double)(1u << RB));
+        chi = __builtin_floor((x.lhi + chi) / (double)(1u << RB));
+      }
+      BF_ASSERT(x.tlo + clo >= -I32_LIM && x.thi + chi <= I32_LIM, "snormalise: top limb + carry can leave int32");
+      sset(r, normalised(x.lo, x.hi));
+#endif
+      return r;
+    }
+    // a + K*p with the carry chain of sub<K>: requires a >= -K*p; the result is an element of the unsigned operations
+    template <int K>
+    static HD fe to_unsigned(const fe& a)
+    {
+      fe r;
+      int32_t c = 0;
+#pragma unroll
+      for (int i = 0; i < N - 1; i++) {
+        const int32_t t = (int32_t)(a.l[i] + kp<K>(i)) + c;
+        r.l[i] = (uint32_t)t & MASK;
+        c = t >> RB; // arithmetic
+      }
+      r.l[N - 1] = a.l[N - 1] + kp<K>(N - 1) + (uint32_t)c;
+#ifdef BIGFIELD_BOUNDS
+      const SB x = sview(a);
+      BF_ASSERT(x.lo >= -(double)K, "to_unsigned: value can be below -K*p");
+      BF_ASSERT(smag(x, 0) + (double)(1u << RB) + 8.0 <= I32_LIM && smag(x, N - 1) + (double)kp<K>(N - 1) + 8.0 <= I32_LIM, "to_unsigned: limb + K*p + carry can leave int32");
+      BF_SET_BOUND(r, x.hi + (double)K);
+      BF_ASSERT(r.bnd <= max_bound(), "to_unsigned result bound");
+#endif
+      return r;
+    }
+
+    // (a*b [+ c*d] + m*p) / R over signed limbs, int64_t column accumulators: the host's and -DBIGFIELD_NO_ASM's form of the products
+    template <bool TWO>
+    static HD void sprod_generic(fe& r, const fe& a, const fe& b, const fe& c, const fe& d)
+    {
+      uint32_t m[N], o[N];
+      int64_t acc = 0;
+      auto term = [](uint32_t x, uint32_t y) { return (int64_t)(int32_t)x * (int64_t)(int32_t)y; };
+#pragma unroll
+      for (int k = 0; k < N; k++) {
+#pragma unroll
+        for (int i = 0; i <= k; i++) {
+          acc += term(a.l[i], b.l[k - i]);
+          if constexpr (TWO) acc += term(c.l[i], d.l[k - i]);
+          if (i < k) acc += (int64_t)m[i] * (int64_t)PR::P[k - i];
+        }
+        m[k] = ((uint32_t)acc * PR::PINV) & MASK;
+        acc += (int64_t)m[k] * (int64_t)PR::P[0];
+        acc >>= RB; // arithmetic, exact: the low 29 bits are zero
+      }
+#pragma unroll
+      for (int k = N; k < 2 * N - 1; k++) {
+#pragma unroll
+        for (int i = k - N + 1; i < N; i++) {
+          acc += term(a.l[i], b.l[k - i]);
+          if constexpr (TWO) acc += term(c.l[i], d.l[k - i]);
+          acc += (int64_t)m[i] * (int64_t)PR::P[k - i];
+        }
+        o[k - N] = (uint32_t)acc & MASK;
+        acc >>= RB;
+      }
+      o[N - 1] = (uint32_t)acc; // the arithmetic remainder: signed top limb
+#pragma unroll
+      for (int i = 0; i < N; i++)
+        r.l[i] = o[i]; // (r may be one of the operands)
+    }
+    static HD fe smul(const fe& a, const fe& b)
+    {
+      fe r;
+#ifdef BIGFIELD_BOUNDS
+      sset_mul(r, a, b);
+#endif
+#if defined(__HIP_DEVICE_COMPILE__) && !defined(BIGFIELD_NO_ASM)
+      if constexpr (N == 9) {
+        mont_smul_asm9<PR>(r.l, a.l, b.l);
+        return r;
+      }
+#endif
+      sprod_generic<false>(r, a, b, a, b);
+      return r;
+    }
+    static HD void smul_inplace(fe& a, const fe& b)
+    {
+#if defined(__HIP_DEVICE_COMPILE__) && !defined(BIGFIELD_NO_ASM)
+      if constexpr (N == 9) {
+        mont_smul_inplace_asm9<PR>(a.l, b.l);
+        return;
+      }
+#endif
+      a = smul(a, b);
+    }
+    static HD fe ssqr(const fe& a)
+    {
+      fe r;
+#ifdef BIGFIELD_BOUNDS
+      { // the asm form multiplies by a2 = 2a: those limbs must fit an int32 too; a square is never negative
+        const SB x = sview(a);
+        BF_ASSERT(2 * smag(x, 0) <= I32_LIM && 2 * smag(x, N - 1) <= I32_LIM, "ssqr: a doubled limb can leave int32");
+        scolumns(&x, &x, 1);
+        const double l2 = x.lo * x.lo, h2 = x.hi * x.hi;
+        sset(r, normalised((x.lo <= 0 && x.hi >= 0) ? 0.0 : (l2 < h2 ? l2 : h2) / r_over_p(), (l2 > h2 ? l2 : h2) / r_over_p() + 1.0));
+      }
+#endif
+#if defined(__HIP_DEVICE_COMPILE__) && !defined(BIGFIELD_NO_ASM)
+      if constexpr (N == 9) {
+        uint32_t a2[N];
+#pragma unroll
+        for (int i = 0; i < N; i++)
+          a2[i] = a.l[i] << 1;
+        mont_ssqr_asm9<PR>(r.l, a.l, a2);
+        return r;
+      }
+#endif
+      sprod_generic<false>(r, a, a, a, a);
+      return r;
+    }
+    static HD fe smul_add(const fe& a, const fe& b, const fe& c, const fe& d)
+    {
+      fe r;
+#ifdef BIGFIELD_BOUNDS
+      sset_mul_add(r, a, b, c, d);
+#endif
+#if defined(__HIP_DEVICE_COMPILE__) && !defined(BIGFIELD_NO_ASM)
+      if constexpr (N == 9) {
+        mont_smul_add_asm9<PR>(r.l, a.l, b.l, c.l, d.l);
+        return r;
+      }
+#endif
+      sprod_generic<true>(r, a, b, c, d);
+      return r;
+    }
+    // c <- (a*b + c*d)/R in c's own registers (see mul_add_inplace_c)
+    static HD void smul_add_inplace_c(fe& c, const fe& a, const fe& b, const fe& d)
+    {
+#if defined(__HIP_DEVICE_COMPILE__) && !defined(BIGFIELD_NO_ASM)
+      if constexpr (N == 9) {
+        mont_smul_add_inplace_c_asm9<PR>(c.l, a.l, b.l, d.l);
+        return;
+      }
+#endif
+      c = smul_add(a, b, c, d);
     }
 
     // ---- full reduction to [0,p) (output path only) ----

@@ -33,7 +33,7 @@ namespace icicle_hip {
     using F = typename E::F;
     const uint32_t t = blockIdx.x * blockDim.x + threadIdx.x;
     // The loop is k_accumulate's own (msm_impl.hpp): an empty accumulator, a fresh operand every step -- built from two live
-    // words where the real kernel gathers it from HBM --, load_plain + cneg + madd, to_proj at the end. (Rounds 1-5 kept a
+    // words where the real kernel gathers it from HBM --, load_plain + cneg_madd + madd, to_proj at the end. (Rounds 1-5 kept a
     // seeded accumulator and the operand live across the addition: 18 registers more than the real kernel, 144 B of scratch at
     // the same launch bounds -- a roof measured on a spilling kernel reads low.)
     constexpr int PW = 2 * E::N32;
@@ -50,7 +50,7 @@ namespace icicle_hip {
         w[E::N32 + k] = sy ^ ((uint32_t)k * 0x51ed27fu);
       }
       w[E::N32 - 1] &= 0x00ffffffu, w[PW - 1] &= 0x00ffffffu; // below p
-      E::madd(acc, empty, E::cneg(E::load_plain(w), (it & 1) != 0));
+      E::madd(acc, empty, E::cneg_madd(E::load_plain(w), (it & 1) != 0));
     }
     const typename E::Proj pr = E::to_proj(acc, empty);
     uint32_t r = 0;

@@ -19,6 +19,8 @@
 // Bounds (units of p, see bigfield.hpp; machine-checked under -DBIGFIELD_BOUNDS):
 //   affine (plain words) x <= 1.2, y <= 2.2         XYZZ  X <= 8, Y <= 4, ZZ,ZZZ <= 2
 //   projective           X,Y,Z <= 4
+// G1 over a 9-limb field (bn254, grumpkin) runs the hot loop on bigfield.hpp's SIGNED layer instead (madd_signed): limb-wise
+// subtraction and negation, no K*p; its accumulator is two-sided, X in [-4, 6], Y in [-1, 4], ZZ, ZZZ in [-0.25, 2].
 //
 // The same code serves G1 (coordinates in Fq, FieldOps) and G2 (coordinates in Fq2, fq2.hpp):
 // C::EXT_DEGREE selects the field-ops class, everything below only uses their common interface.
@@ -92,6 +94,23 @@ namespace icicle_hip {
       r.y = F::select(negate, F::template neg<2>(a.y), a.y);
       return r;
     }
+    // madd() on bigfield.hpp's signed layer: G1 over a 9-limb field (bn254, grumpkin). A signed mul_add column of a 14-limb field
+    // holds 42 products of up to 2^58, more than an int64 takes, and the carry-normalised operands that would fit cost what
+    // the layer saves: bls12_381 and bls12_377 keep the unsigned form, and so does G2 (Fq2Ops, TIGHT mode).
+    static constexpr bool SIGNED_MADD = C::EXT_DEGREE == 1 && F::N == 9;
+    // cneg for an operand that goes to madd() and nowhere else: where madd() runs on the signed layer the sign is applied
+    // limb-wise (one instruction per limb instead of the carry chain of neg<2> plus a select)
+    static HD Aff cneg_madd(const Aff& a, bool negate)
+    {
+      if constexpr (SIGNED_MADD) {
+        Aff r;
+        r.x = a.x;
+        r.y = F::scneg(a.y, negate);
+        return r;
+      } else {
+        return cneg(a, negate);
+      }
+    }
 
     // ---- XYZZ --------------------------------------------------------------------------------
     // 2*(x,y) for a PLAIN affine point, result in the accumulator's scaling (dbl-2008-s-1 with ZZ1 = ZZZ1 = 1, a = 0).
@@ -121,6 +140,14 @@ namespace icicle_hip {
     // acc += b (b = PLAIN affine limbs, not the identity). `empty` is the accumulator's "is identity" flag.
     // madd-2008-s: 8M + 2S. Scaling: see the file header.
     static HD void madd(XYZZ& acc, bool& empty, const Aff& b)
+    {
+      if constexpr (SIGNED_MADD)
+        madd_signed(acc, empty, b);
+      else
+        madd_carry(acc, empty, b);
+    }
+    // the carry-normalised form: every limb in [0, 2^29), subtraction by adding K*p (14-limb fields and G2)
+    static HD void madd_carry(XYZZ& acc, bool& empty, const Aff& b)
     {
       if (__builtin_expect(empty, 0)) {
         acc.x = F::mul_base(b.x, F::base_r2());
@@ -161,6 +188,63 @@ namespace icicle_hip {
       acc.x = X3;
     }
 
+    // The same addition on the signed layer (bigfield.hpp): no K*p, no carry chain but ONE (X3). The operand b is plain affine
+    // limbs, y as load_plain() left it, negated limb-wise (cneg_madd) or by neg<2> (cneg): limbs in (-2^29, 2^29).
+    // Invariant of the accumulator (units of p), asserted and re-imposed on the tracker at the top of every addition, so that one
+    // step proves the fixed point:   X in [-4, 6]   Y in [-1, 4]   ZZ, ZZZ in [-0.25, 2],   all four normalised with a signed top limb.
+    // Then (R/p >= 128, a signed product of |a| <= A p, |b| <= B p lies in (-A B / 128, A B / 128 + 1) p and is normalised):
+    //   U2 in (-0.02, 1.02)   S2 in (-0.04, 1.04)   P = U2 - X in (-6.1, 5.1)   R = S2 - Y in (-4.1, 2.1): limbs in (-2^29, 2^29)
+    //   PP in [0, 1.3)   PPP, Q in (-0.07, 1.07)   t = 2Q + PPP: limbs below 3 * 2^29   X3 = R^2 - t in (-3.2, 1.4), normalised
+    //   d = Q - X3 in (-1.5, 4.3): limbs in (-2^29, 2^29)   Y3 in (-0.2, 1.2)   ZZ3, ZZZ3 in (-0.03, 1.03)
+    // The widest column is that of R*d + (-Y)*PPP: 27 products below 2^58 and the carry, below 2^63. The doubled limbs of the two
+    // squarings stay below 2^30. The first-point path and dbl_affine() leave X <= 5.1, Y <= 3.3, ZZ, ZZZ <= 1.3.
+    static HD void madd_signed(XYZZ& acc, bool& empty, const Aff& b)
+    {
+      F::sassert_operand(b.x, 0.0, 1.2);
+      F::sassert_operand(b.y, -1.2, 2.2);
+      if (__builtin_expect(empty, 0)) {
+        acc.x = F::smul(b.x, F::r2());
+        acc.y = F::smul(b.y, F::r2());
+        acc.zz = F::r2();
+        acc.zzz = F::r2();
+        empty = false;
+        return;
+      }
+      F::sassume_normalised(acc.x, -4.0, 6.0);
+      F::sassume_normalised(acc.y, -1.0, 4.0);
+      F::sassume_normalised(acc.zz, -0.25, 2.0);
+      F::sassume_normalised(acc.zzz, -0.25, 2.0);
+      fe U2 = F::smul(b.x, acc.zz);
+      fe S2 = F::smul(b.y, acc.zzz);
+      fe P = F::ssub(U2, acc.x);
+      fe R = F::ssub(S2, acc.y);
+      fe PP = F::ssqr(P); // in [0, 2p): the filter's four constants cover {0, p}
+      if (__builtin_expect(F::maybe_zero_mulout(PP), 0)) {
+        if (F::is_zero(F::template to_unsigned<8>(P))) { // same x: either b == acc (double) or b == -acc (cancel)
+          if (F::is_zero(F::template to_unsigned<8>(R))) {
+            Aff u;
+            u.x = b.x;
+            u.y = F::template to_unsigned<2>(b.y);
+            acc = dbl_affine(u);
+          } else {
+            empty = true;
+          }
+          return;
+        }
+      }
+      fe PPP = F::smul(P, PP);
+      fe Q = F::smul(acc.x, PP);
+      fe t = F::sadd2(Q, PPP); // 2Q + PPP
+      fe X3 = F::snormalise(F::ssub(F::ssqr(R), t));
+      fe d = F::ssub(Q, X3);
+      // Y3 = R*d + (-Y1)*PPP with one shared reduction, produced in Y's own registers; ZZ, ZZZ likewise
+      acc.y = F::sneg(acc.y);
+      F::smul_add_inplace_c(acc.y, R, d, PPP);
+      F::smul_inplace(acc.zz, PP);
+      F::smul_inplace(acc.zzz, PPP);
+      acc.x = X3;
+    }
+
     // ---- complete projective arithmetic (identity = (0:1:0)) -----------------------------------
     static HD Proj proj_identity()
     {
@@ -176,10 +260,24 @@ namespace icicle_hip {
     {
       if (empty) return proj_identity();
       Proj r;
-      const fe zz1 = F::mul_base(a.zz, F::base_plain_one()); // ZZ*R
-      r.x = F::mul(a.x, a.zzz);
-      r.y = F::mul(a.y, a.zz);
-      r.z = F::mul(zz1, a.zzz);
+      if constexpr (SIGNED_MADD) {
+        // the accumulator as madd_signed() leaves it (its invariant: see there): signed products, each in (-0.2, 1.2) p, then
+        // + p with a carry pass -- the complete formulas downstream work on non-negative limbs
+        XYZZ s = a;
+        F::sassume_normalised(s.x, -4.0, 6.0);
+        F::sassume_normalised(s.y, -1.0, 4.0);
+        F::sassume_normalised(s.zz, -0.25, 2.0);
+        F::sassume_normalised(s.zzz, -0.25, 2.0);
+        const fe zz1 = F::smul(s.zz, F::plain_one()); // ZZ*R
+        r.x = F::template to_unsigned<1>(F::smul(s.x, s.zzz));
+        r.y = F::template to_unsigned<1>(F::smul(s.y, s.zz));
+        r.z = F::template to_unsigned<1>(F::smul(zz1, s.zzz));
+      } else {
+        const fe zz1 = F::mul_base(a.zz, F::base_plain_one()); // ZZ*R
+        r.x = F::mul(a.x, a.zzz);
+        r.y = F::mul(a.y, a.zz);
+        r.z = F::mul(zz1, a.zzz);
+      }
       return r;
     }
     static HD Proj to_proj(const Aff& a)

@@ -952,7 +952,7 @@ namespace icicle_hip {
         w[4 * q + 3] = v.w;
       }
       if (__builtin_expect(E::words_are_zero(w), 0)) continue; // identity base: contributes nothing (cpu_msm.hpp:282)
-      typename E::Aff a = E::cneg(E::load_plain(w), (e >> 31) != 0);
+      typename E::Aff a = E::cneg_madd(E::load_plain(w), (e >> 31) != 0);
       E::madd(acc, empty, a);
     }
     *dst = E::to_proj(acc, empty);

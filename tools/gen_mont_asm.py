@@ -20,8 +20,15 @@ RB = 29
 MASK = "0x1fffffff"
 
 
-def gen(n: int, kind: str) -> str:
-    """kind: mul (a*b), mul_add (a*b + c*d), sqr (a*a; inputs a and a2 = 2a)"""
+def gen(n: int, kind: str, signed: bool = False) -> str:
+    """kind: mul (a*b), mul_add (a*b + c*d), sqr (a*a; inputs a and a2 = 2a).
+    signed: the operands are SIGNED limbs (bigfield.hpp's signed layer): v_mad_i64_i32 into a signed column accumulator,
+    arithmetic shifts between columns. m_k = (lo32(acc) * pinv) & MASK is the same instruction pair (the low 29 bits of a
+    two's-complement number do not depend on its sign) and stays in [0, 2^29); the output limbs 0..N-2 are masked, hence
+    non-negative, and the top limb is the arithmetic remainder of the last column (v_alignbit_b32 yields the low 32 bits
+    of the shifted pair, which is that remainder as an int32)."""
+    MAD = "v_mad_i64_i32" if signed else "v_mad_u64_u32"
+    SHR = "v_ashrrev_i64" if signed else "v_lshrrev_b64"
     ops = []  # textual operand list in order
     r = [f"%{i}" for i in range(n)]
     m = [f"%{n + i}" for i in range(n)]
@@ -34,7 +41,7 @@ def gen(n: int, kind: str) -> str:
     first = [True]
 
     def mad(x, y):
-        lines.append(f"v_mad_u64_u32 {ACC}, vcc, {x}, {y}, {'0' if first[0] else ACC}")
+        lines.append(f"{MAD} {ACC}, vcc, {x}, {y}, {'0' if first[0] else ACC}")
         first[0] = False
 
     def products(k):
@@ -62,23 +69,24 @@ def gen(n: int, kind: str) -> str:
             lines.append(f"v_mul_lo_u32 {m[k]}, {LO}, {pinv}")
             lines.append(f"v_and_b32 {m[k]}, {MASK}, {m[k]}")
             mad(m[k], p[0])
-            lines.append(f"v_lshrrev_b64 {ACC}, {RB}, {ACC}")
+            lines.append(f"{SHR} {ACC}, {RB}, {ACC}")
         else:
             for i in range(k - n + 1, n):
                 mad(m[i], p[k - i])
             lines.append(f"v_and_b32 {r[k - n]}, {MASK}, {LO}")
             if k < 2 * n - 2:
-                lines.append(f"v_lshrrev_b64 {ACC}, {RB}, {ACC}")
+                lines.append(f"{SHR} {ACC}, {RB}, {ACC}")
             else:
                 lines.append(f"v_alignbit_b32 {r[n - 1]}, {HI}, {LO}, {RB}")
     return lines
 
 
-def emit_inplace(n: int) -> str:
+def emit_inplace(n: int, signed: bool = False) -> str:
     """a <- a*b with the result in a's own registers: a[k-N] is dead before r[k-N] is written (column k only reads
     a[i], i > k-N), so r and a can be the same read-write operands -- an accumulator coordinate updated in a loop then
     needs no register-to-register copies at the back edge (early-clobber outputs can never be coalesced with inputs)."""
-    lines = gen(n, "mul")
+    lines = gen(n, "mul", signed)
+    sg = "s" if signed else ""
     # operand renumbering: gen() numbers r = %0..%(n-1), m = %n.., acc, a = %(2n+1).., b, p, pinv; here a IS r
     base = 2 * n + 1
     ren = {}
@@ -94,9 +102,9 @@ def emit_inplace(n: int) -> str:
     body = "\n".join(f'      "{ln}\\n"' for ln in out)
     outs = ", ".join([f'"+&v"(a[{i}])' for i in range(n)] + [f'"=&v"(m[{i}])' for i in range(n)] + ['"=&{v[2:3]}"(acc)'])
     ins = ", ".join([f'"v"(b[{i}])' for i in range(n)] + [f'"s"(PR::P[{i}])' for i in range(n)] + ['"s"(PR::PINV)'])
-    return f"""  // mul in place (a <- a*b), N = {n}
+    return f"""  // {'signed ' if signed else ''}mul in place (a <- a*b), N = {n}
   template <class PR>
-  __device__ __forceinline__ void mont_mul_inplace_asm{n}(uint32_t* a, const uint32_t* b)
+  __device__ __forceinline__ void mont_{sg}mul_inplace_asm{n}(uint32_t* a, const uint32_t* b)
   {{
     uint32_t m[{n}];
     uint64_t acc;
@@ -110,11 +118,12 @@ def emit_inplace(n: int) -> str:
 """
 
 
-def emit_mul_add_inplace_c(n: int) -> str:
+def emit_mul_add_inplace_c(n: int, signed: bool = False) -> str:
     """c <- a*b + c*d with the result in c's own registers (same argument as emit_inplace: c[k-N] is dead before
     r[k-N] is written)."""
     import re
-    lines = gen(n, "mul_add")
+    lines = gen(n, "mul_add", signed)
+    sg = "s" if signed else ""
     base = 2 * n + 1  # gen(): r %0.., m %n.., acc, a, b, c, d, p, pinv
     ren = {}
     for i in range(n):
@@ -125,9 +134,9 @@ def emit_mul_add_inplace_c(n: int) -> str:
     body = "\n".join(f'      "{ln}\\n"' for ln in out)
     outs = ", ".join([f'"+&v"(c[{i}])' for i in range(n)] + [f'"=&v"(m[{i}])' for i in range(n)] + ['"=&{v[2:3]}"(acc)'])
     ins = ", ".join([f'"v"({nm}[{i}])' for nm in ("a", "b", "d") for i in range(n)] + [f'"s"(PR::P[{i}])' for i in range(n)] + ['"s"(PR::PINV)'])
-    return f"""  // mul_add in place (c <- a*b + c*d), N = {n}
+    return f"""  // {'signed ' if signed else ''}mul_add in place (c <- a*b + c*d), N = {n}
   template <class PR>
-  __device__ __forceinline__ void mont_mul_add_inplace_c_asm{n}(uint32_t* c, const uint32_t* a, const uint32_t* b, const uint32_t* d)
+  __device__ __forceinline__ void mont_{sg}mul_add_inplace_c_asm{n}(uint32_t* c, const uint32_t* a, const uint32_t* b, const uint32_t* d)
   {{
     uint32_t m[{n}];
     uint64_t acc;
@@ -141,8 +150,10 @@ def emit_mul_add_inplace_c(n: int) -> str:
 """
 
 
-def emit(n: int, kind: str) -> str:
-    lines = gen(n, kind)
+def emit(n: int, kind: str, signed: bool = False) -> str:
+    lines = gen(n, kind, signed)
+    sg = "s" if signed else ""
+    mad = "v_mad_i64_i32" if signed else "v_mad_u64_u32"
     body = "\n".join(f'      "{ln}\\n"' for ln in lines)
     nin = {"mul": 2, "mul_add": 4, "sqr": 2}[kind]
     names = {"mul": ["a", "b"], "mul_add": ["a", "b", "c", "d"], "sqr": ["a", "a2"]}[kind]
@@ -150,9 +161,9 @@ def emit(n: int, kind: str) -> str:
     ins = ", ".join([f'"v"({nm}[{i}])' for nm in names for i in range(n)] + [f'"s"(PR::P[{i}])' for i in range(n)] + ['"s"(PR::PINV)'])
     args = ", ".join(f"const uint32_t* {nm}" for nm in names)
     nmads = sum(1 for ln in lines if ln.startswith("v_mad"))
-    return f"""  // {kind}, N = {n}: {len(lines)} instructions ({nmads} v_mad_u64_u32)
+    return f"""  // {'signed ' if signed else ''}{kind}, N = {n}: {len(lines)} instructions ({nmads} {mad})
   template <class PR>
-  __device__ __forceinline__ void mont_{kind}_asm{n}(uint32_t* r, {args})
+  __device__ __forceinline__ void mont_{sg}{kind}_asm{n}(uint32_t* r, {args})
   {{
     uint32_t m[{n}];
     uint64_t acc;
@@ -174,6 +185,12 @@ def main():
             out.append(emit(n, kind))
         out.append(emit_inplace(n))
         out.append(emit_mul_add_inplace_c(n))
+    # the signed layer (bigfield.hpp): 9-limb fields only -- a signed mul_add column of a 14-limb field does not fit 63 bits
+    for n in (9,):
+        for kind in ("mul", "sqr", "mul_add"):
+            out.append(emit(n, kind, signed=True))
+        out.append(emit_inplace(n, signed=True))
+        out.append(emit_mul_add_inplace_c(n, signed=True))
     out += ["} // namespace icicle_hip", "#endif", ""]
     sys.stdout.write("\n".join(out))
 
