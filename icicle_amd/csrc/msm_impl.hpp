@@ -82,12 +82,7 @@ namespace icicle_hip {
   //             The source block of an element (needed to rebuild its global scalar index) is
   //             found by a binary search in the partition's per-block offset row.
   // Output is what bucket accumulation consumes: count[], offs[], sorted[] (point index | sign<<31).
-  struct SortPlan {
-    int hb, lb;       // high / low bucket-key bits, hb + lb = c - 1
-    int jb;           // bits for the precompute index j
-    int chunk_log;    // scalars per pass-A block = 2^chunk_log
-    int nblk;         // pass-A blocks
-  };
+  // (SortPlan -- hb, lb, jb, chunk_log, nblk -- and msm_sort_plan(), which fills it: msm_plan.h)
 
   // digit word: |d| | (d<0)<<31, |d| in [0, 2^(c-1)], 0 = skip. Signed recoding as cpu_msm.hpp:289-295.
   // Windows are consumed in order, lowest first: the scalar is shifted right by c after each digit, so every
@@ -251,10 +246,9 @@ namespace icicle_hip {
   // Tile sort in LDS: a block ranks TS = 16 * blockDim elements by destination, stages them sorted,
   // and writes each destination's run contiguously -- HBM sees >= 64-byte runs instead of 4-byte
   // scatters (the unstaged scatter wrote 30 GB to place 3.5 GB, profiles/r01_notes.md).
-  constexpr int SORT_EPT = 16;                 // elements per thread per tile
-  constexpr uint32_t SORT_TS = 1024 * SORT_EPT; // tile size with 1024 threads
+  // (SORT_EPT = 16 elements per thread per tile, SORT_TS = the tile of 1024 threads, tile_lds_bytes(): msm_plan.h)
   // Two block shapes. 1024 threads (a whole CU: 16 waves, ~100 KiB of LDS) is the stand-alone sort. 256 threads (one wave per
-  // SIMD, a 4096-element tile, ~36 KiB) is the CO-RESIDENT sort of the pipelined schedule (msm_run_single, window groups):
+  // SIMD, a 4096-element tile, ~36 KiB) is the CO-RESIDENT sort of the pipelined schedule (msm_run_pipelined, window groups):
   // its waves fit beside two k_accumulate waves per SIMD, so the sort of window group g + 1 -- waves parked on memory most
   // of the time -- runs in the issue slots the accumulation of group g leaves, instead of before it.
   struct TileLds {
@@ -274,7 +268,6 @@ namespace icicle_hip {
     t.wsum = lds + 2 * D + TS + TS / 2;
     return t;
   }
-  __host__ __device__ static inline size_t tile_lds_bytes(uint32_t D, uint32_t TS = SORT_TS) { return ((size_t)2 * D + TS + TS / 2 + 32) * 4; }
 
   // pass A count: block (b, wl) histograms the high key bits of scalar chunk b for target window w0+wl
   static __global__ __launch_bounds__(1024) void k_a_count(const uint32_t* __restrict__ dig, uint32_t* __restrict__ cntA, int n, int nwin, int wpf, int pf, SortPlan sp)
@@ -413,8 +406,7 @@ namespace icicle_hip {
 
   // Row-wise exclusive scans (pass-A counter tables [2^hb][nblk] per window, bucket counts per window).
   // Two launches over (chunk, row): chunk sums, then each chunk scans itself on top of the sums before it --
-  // a single block per row left 243 of 256 CUs idle and took ~1 ms per table at 2^26.
-  constexpr uint32_t SCAN_CHUNK = 8192; // 1024 threads x 8 consecutive elements
+  // a single block per row left 243 of 256 CUs idle and took ~1 ms per table at 2^26. (SCAN_CHUNK = 8192: msm_plan.h)
   static __global__ __launch_bounds__(1024) void k_scan_sums(const uint32_t* __restrict__ in, uint32_t* __restrict__ sums, uint32_t m)
   {
     __shared__ uint32_t wsum[32];
@@ -480,11 +472,10 @@ namespace icicle_hip {
   // it on one block. k_b_plan turns partition sizes into a block -> (partition, sub-chunk) table; k_b_count adds LDS
   // histograms of the low lb key bits into count[]; k_b_scan_part (window-wide k_scan_* when nothing is owned) makes
   // offs[]/cursor[]; k_b_scatter reserves a range per (block, bin) with ONE global atomic and ranks inside it in LDS.
-  constexpr uint32_t CHUNKB_LOG = 17;
-  // A partition of at most this many elements is sorted whole by ONE block (k_b_owned below) instead of in sub-chunks. At
+  // (CHUNKB = 2^CHUNKB_LOG = 2^17 elements: msm_plan.h)
+  // A partition of at most PASSB_OWN_MAX_DEFAULT = 2^18 (msm_plan.h) elements is sorted whole by ONE block (k_b_owned below) instead of in sub-chunks. At
   // 2^26 terms a partition holds 2^16 (wide windows) or 2^17 elements, so 2^18 is more than 300 sigma above the mean: only
   // skewed scalars exceed it, and those keep the sub-chunks. MSMConfig.ext "hip_msm_passb_own_max" overrides (0: none owned).
-  constexpr uint32_t PASSB_OWN_MAX_DEFAULT = 1u << 18;
 
   static __global__ __launch_bounds__(1024) void k_b_plan(const uint32_t* __restrict__ offA, uint32_t* __restrict__ bstart, uint32_t nparts, int wpf, int hb, int nblk, uint32_t p0, uint32_t own_max)
   {
@@ -839,9 +830,8 @@ namespace icicle_hip {
   // per bucket (Poisson, sigma 11) the longest of 64 is ~155, i.e. ~15 % of the lane-cycles of the dominant
   // kernel were idle (SQ_INSTS_VALU per mixed add 2912 vs ~2540 in the instruction stream). perm[] lists the
   // buckets by descending size class, so the 64 lanes of a wave get buckets of (almost) the same length and the
-  // empty buckets end up in waves that exit at once. Counting sort over 257 classes of min(count, seg).
-  constexpr uint32_t SZ_BINS = 257;
-  constexpr uint32_t SZ_CHUNK = 16384; // buckets per block (1024 threads x 16)
+  // empty buckets end up in waves that exit at once. Counting sort over SZ_BINS = 257 classes of min(count, seg), SZ_CHUNK = 16384
+  // buckets per block (msm_plan.h).
   __device__ __forceinline__ uint32_t size_class(uint32_t cnt, uint32_t seg)
   {
     const uint32_t q = (uint32_t)(((uint64_t)min(cnt, seg) * 256u) / seg); // 0..256
@@ -1306,7 +1296,7 @@ namespace icicle_hip {
   // 0.61-0.73 ms for 13-16 windows of the same chain length; the windows dealt round-robin to four waves -> 1.1-1.6 ms
   // (profiles/r03_notes.md section 8): the waves of one small block share issue bandwidth instead of taking a SIMD each.
   // Separate single-wave blocks land on different CUs; their partial sums are added by k_final_combine.
-  constexpr int FINAL_WINDOWS_PER_BLOCK = 16;
+  // (FINAL_WINDOWS_PER_BLOCK = 16: msm_plan.h)
   // Block (bw, b) combines windows [w0 + 16 bw, ...) of MSM b, at most 16 of the nw windows [w0, w0 + nw) -- still scaled
   // by their full 2^(c*w). With `partial` the block's sum goes to partial[(slot0 + bw) * nmsm + b] in the kernels' own
   // representation (several blocks per MSM, or a window group of the pipelined schedule); without, to result[b].
@@ -1663,229 +1653,222 @@ namespace icicle_hip {
   };
 
   // ------------------------------------------------------------------------------------------
+  // The steps of msm_run_single_planned. The decisions -- sort geometry, reduction geometry and route, batch fold, window
+  // combine, the k_accumulate form -- are the host-only functions of msm_plan.h; here are the leases, the launches and their order.
+
+  // empty sum = identity for every batch element
   template <class C>
-  static icicle_error_t msm_run_single_planned(const void* scalars_v, const void* bases_v, int n, const icicle_msm_config_t* cfg, void* results_v, MsmBucketHook<C>* hook, int plan_override);
-  // The auto-selected mixed-width plan (2^23 terms and up) holds ~2.15 x the buckets, counters and lists of the uniform plan -- several
-  // GB more for G2 at 2^26. A call that does not get that memory is run again on the uniform plan, which fit before round 5 (ADVICE r05).
-  template <class C>
-  static icicle_error_t msm_run_single(const void* scalars_v, const void* bases_v, int n, const icicle_msm_config_t* cfg, void* results_v, MsmBucketHook<C>* hook = nullptr)
-  {
-    // (icicle_hip_test_inject_failure(0, 9): the first attempt "runs out of memory" once -- the rehearsal of this path)
-    icicle_error_t rc = (!hook && test_failure_armed(0, 9)) ? ICICLE_ALLOCATION_FAILED : msm_run_single_planned<C>(scalars_v, bases_v, n, cfg, results_v, hook, 0);
-    if (rc == ICICLE_ALLOCATION_FAILED && !hook && cfg && make_plan(std::max(n, 1), C::fr::NBITS, *cfg, 0).n_lo > 0) {
-      multi_stats().plan_fallbacks++;
-      (void)hipGetLastError();
-      if (cfg->stream) (void)hipStreamSynchronize((hipStream_t)cfg->stream);
-      (void)icicle_hip_release_workspace();
-      rc = msm_run_single_planned<C>(scalars_v, bases_v, n, cfg, results_v, hook, -1);
-    }
-    return rc;
-  }
-  template <class C>
-  static icicle_error_t msm_run_single_planned(const void* scalars_v, const void* bases_v, int n, const icicle_msm_config_t* cfg, void* results_v, MsmBucketHook<C>* hook, int plan_override)
+  static icicle_error_t msm_store_identity(const icicle_msm_config_t* cfg, int batch, uint32_t* d_res, void* results_v, hipStream_t st)
   {
     using E = EC<C>;
-    using FR = FieldOps<typename C::fr>;
-    constexpr int PW = 2 * E::N32, RW = 3 * E::N32;
-    if (!cfg || !results_v || n < 0) return ICICLE_INVALID_ARGUMENT;
-    const int batch = std::max(1, cfg->batch_size);
-    if (n > 0 && (!scalars_v || !bases_v)) return ICICLE_INVALID_POINTER;
-    ICICLE_TRY(bind_current_device());
-    hipStream_t st = (hipStream_t)cfg->stream;
-    int force_windows = hook ? -1 : plan_override; // (a bucket exchange adds bucket arrays of several calls element-wise: uniform widths)
-    if (!hook && plan_override == 0 && cfg->ext) force_windows = std::max(0, reinterpret_cast<const ConfigExt*>(cfg->ext)->get_int("hip_msm_windows", 0));
-    {
-      static const int env_w = getenv("ICICLE_HIP_MSM_WINDOWS") ? atoi(getenv("ICICLE_HIP_MSM_WINDOWS")) : 0; // A/B: -1 = uniform only
-      if (force_windows == 0 && env_w != 0) force_windows = env_w;
-    }
-    const MsmPlan pl = make_plan(std::max(n, 1), C::fr::NBITS, *cfg, force_windows);
-    const WinWidths ww{pl.c, pl.n_lo, pl.negate};
-    const int pf = pl.pf;
-    if ((long long)n * pf >= (1ll << 31)) return ICICLE_INVALID_ARGUMENT;
-    const bool shared = cfg->are_points_shared_in_batch || batch == 1;
-    const size_t npts_one = (size_t)n * pf;
-    const size_t npts_all = shared ? npts_one : npts_one * batch;
+    constexpr int RW = 3 * E::N32;
+    std::vector<uint32_t> id((size_t)batch * RW, 0);
+    for (int b = 0; b < batch; b++)
+      id[(size_t)b * RW + E::N32] = 1; // (0:1:0)
+    HIP_TRY(hipMemcpyAsync(d_res, id.data(), id.size() * 4, hipMemcpyHostToDevice, st), ICICLE_COPY_FAILED);
+    HIP_TRY(hipStreamSynchronize(st), ICICLE_SYNCHRONIZATION_FAILED);
+    if (!cfg->are_results_on_device) HIP_TRY(hipMemcpy(results_v, d_res, id.size() * 4, hipMemcpyDeviceToHost), ICICLE_COPY_FAILED);
+    return ICICLE_SUCCESS;
+  }
 
-    // ---- result buffer
-    TempBuf d_res_tmp;
-    uint32_t* d_res = (uint32_t*)results_v;
+  // an input that lies in host memory is copied into a lease of this call; *dev is where the kernels read it
+  static icicle_error_t msm_stage_input(const void* src, bool on_device, size_t bytes, TempBuf& tmp, const uint32_t** dev, hipStream_t st)
+  {
+    *dev = (const uint32_t*)src;
+    if (on_device) return ICICLE_SUCCESS;
+    HIP_TRY(tmp.alloc(bytes, st), ICICLE_ALLOCATION_FAILED);
+    HIP_TRY(hipMemcpyAsync(tmp.ptr(), src, bytes, hipMemcpyHostToDevice, st), ICICLE_COPY_FAILED);
+    *dev = tmp.as<uint32_t>();
+    return ICICLE_SUCCESS;
+  }
+
+  // the end of a call: results that go to the host are downloaded; a synchronous call waits for its stream
+  static icicle_error_t msm_deliver_results(const icicle_msm_config_t* cfg, const uint32_t* d_res, void* results_v, size_t bytes, hipStream_t st)
+  {
     if (!cfg->are_results_on_device) {
-      HIP_TRY(d_res_tmp.alloc((size_t)batch * RW * 4, st), ICICLE_ALLOCATION_FAILED);
-      d_res = d_res_tmp.as<uint32_t>();
-    }
-
-    if (n == 0) { // empty sum = identity for every batch element
-      std::vector<uint32_t> id((size_t)batch * RW, 0);
-      for (int b = 0; b < batch; b++)
-        id[(size_t)b * RW + E::N32] = 1; // (0:1:0)
-      HIP_TRY(hipMemcpyAsync(d_res, id.data(), id.size() * 4, hipMemcpyHostToDevice, st), ICICLE_COPY_FAILED);
+      HIP_TRY(hipMemcpyAsync(results_v, d_res, bytes, hipMemcpyDeviceToHost, st), ICICLE_COPY_FAILED);
       HIP_TRY(hipStreamSynchronize(st), ICICLE_SYNCHRONIZATION_FAILED);
-      if (!cfg->are_results_on_device) HIP_TRY(hipMemcpy(results_v, d_res, id.size() * 4, hipMemcpyDeviceToHost), ICICLE_COPY_FAILED);
+    } else if (!cfg->is_async) {
+      HIP_TRY(hipStreamSynchronize(st), ICICLE_SYNCHRONIZATION_FAILED);
+    }
+    return ICICLE_SUCCESS;
+  }
+
+  // The temporaries of one call, sized for its largest launch sequence: BB MSMs = TW windows. alloc() holds every size formula.
+  template <class C>
+  struct MsmWorkspace {
+    using Proj = typename EC<C>::Proj;
+    // slack terms of the formulas below
+    static constexpr size_t LIST_TAIL_BYTES = 64;       // k_accumulate reads the bucket lists in groups of 4: the last read may run past the lists
+    static constexpr uint32_t OVF_ROUNDING = 16;        // overflow segments on top of (list entries) / seg, for the call and again for every window group
+    static constexpr size_t OVFCNT_GROUP_BYTES = 16;    // [overflow segments, overflowing buckets, largest bucket, -] per window group
+    static constexpr size_t QUAD_CHUNKS = 64;           // chunks per window the quad reduction may write, however few the one-lane geometry has
+    static constexpr size_t SCAN_TAIL_WORDS = 16;       // a group's scan scratch (MsmLaunch::scan_words): the round-up of its size-table scan
+    TempBuf mont, dig, partA, sorted, cntA, offA, bstart, count, offs, cursor, buckets, seg, win, ovf, ovfpart, ovfcnt, scansum, perm, sztab, szoff, firsts;
+    size_t TW = 0;             // windows per launch sequence
+    size_t chunk_stride = 0;   // chunk sums: V at seg, T chunk_stride points behind
+    size_t szblk_max = 0;      // blocks of the size-class tables
+    size_t scan_row_words = 0; // chunk sums of one window's scan (pass-A table row or bucket counts)
+    uint32_t maxblkB = 0;      // pass-B sub-chunk blocks
+    uint32_t ovf_cap = 0;      // overflow segments
+
+    // mont_bytes: the staged copy of the bases, 0 when they are gathered where they lie
+    icicle_error_t alloc(const MsmPlan& pl, const SortPlan& sp, const MsmReduceGeom& geo, int n, int BB, size_t mont_bytes, hipStream_t st)
+    {
+      const size_t cap = (size_t)n * pl.pf; // bucket-list capacity per target window
+      TW = (size_t)BB * pl.wpf;
+      const size_t nbk = TW * pl.nb;
+      const size_t nparts = TW << sp.hb;
+      const size_t tabA = nparts * sp.nblk + TW; // [wl][h][b] counters + per-window totals
+      const size_t elems_max = (size_t)BB * n * pl.nwin + 1;
+      maxblkB = (uint32_t)std::min<size_t>(nparts + (elems_max >> CHUNKB_LOG) + 2, 0x7fffffffu);
+      ovf_cap = (uint32_t)std::min<size_t>(elems_max / pl.seg + OVF_ROUNDING, 0x7fffffffu);
+      chunk_stride = TW * std::max<size_t>(geo.nseg, QUAD_CHUNKS);
+      szblk_max = (nbk + SZ_CHUNK - 1) / SZ_CHUNK + MSM_MAX_GROUPS; // (+ one partial block per window group)
+      scan_row_words = std::max<size_t>((size_t)sp.nblk << sp.hb, pl.nb) / SCAN_CHUNK + 1;
+      // the pipelined schedule gives every window group its own slice of the overflow tables: the groups' caps add up to
+      // ovf_cap + OVF_ROUNDING per group, and firsts[] keeps one more word per group
+      const size_t ovf_slots = (size_t)ovf_cap + MSM_MAX_GROUPS * OVF_ROUNDING;
+      if (mont_bytes) HIP_TRY(mont.alloc(mont_bytes, st), ICICLE_ALLOCATION_FAILED);
+      HIP_TRY(dig.alloc((size_t)BB * pl.nwin * n * 4, st), ICICLE_ALLOCATION_FAILED);
+      if (sp.lb != 0) HIP_TRY(partA.alloc(TW * cap * 4, st), ICICLE_ALLOCATION_FAILED);
+      HIP_TRY(sorted.alloc(TW * cap * 4 + LIST_TAIL_BYTES, st), ICICLE_ALLOCATION_FAILED);
+      HIP_TRY(cntA.alloc(tabA * 4, st), ICICLE_ALLOCATION_FAILED);
+      HIP_TRY(offA.alloc(tabA * 4, st), ICICLE_ALLOCATION_FAILED);
+      HIP_TRY(bstart.alloc((nparts + 1 + MSM_MAX_GROUPS) * 4, st), ICICLE_ALLOCATION_FAILED); // + one end marker per window group
+      HIP_TRY(count.alloc(nbk * 4, st), ICICLE_ALLOCATION_FAILED);
+      HIP_TRY(offs.alloc(nbk * 4, st), ICICLE_ALLOCATION_FAILED);
+      HIP_TRY(cursor.alloc(nbk * 4, st), ICICLE_ALLOCATION_FAILED);
+      HIP_TRY(buckets.alloc(nbk * sizeof(Proj), st), ICICLE_ALLOCATION_FAILED);
+      HIP_TRY(seg.alloc(2 * chunk_stride * sizeof(Proj), st), ICICLE_ALLOCATION_FAILED); // chunk V | chunk T
+      HIP_TRY(win.alloc(TW * sizeof(Proj), st), ICICLE_ALLOCATION_FAILED);
+      HIP_TRY(ovf.alloc(ovf_slots * sizeof(OvfSeg), st), ICICLE_ALLOCATION_FAILED);
+      HIP_TRY(ovfpart.alloc(ovf_slots * sizeof(Proj), st), ICICLE_ALLOCATION_FAILED);
+      HIP_TRY(firsts.alloc((ovf_slots + MSM_MAX_GROUPS) * 4 + 4, st), ICICLE_ALLOCATION_FAILED);
+      HIP_TRY(ovfcnt.alloc(MSM_MAX_GROUPS * OVFCNT_GROUP_BYTES, st), ICICLE_ALLOCATION_FAILED);
+      HIP_TRY(perm.alloc(nbk * 4, st), ICICLE_ALLOCATION_FAILED);
+      HIP_TRY(sztab.alloc(szblk_max * SZ_BINS * 4, st), ICICLE_ALLOCATION_FAILED);
+      HIP_TRY(szoff.alloc(szblk_max * SZ_BINS * 4, st), ICICLE_ALLOCATION_FAILED);
+      HIP_TRY(scansum.alloc(TW * scan_row_words * 4, st), ICICLE_ALLOCATION_FAILED);
+      return ICICLE_SUCCESS;
+    }
+  };
+
+  // k_accumulate in the form msm_acc_waves() chose. Instantiated: G1 1 / 2 / 3 / 4 waves, plus the padded two-wave form on
+  // the 9-limb curves; G2 1 wave, and 2 where the point fits 288 bytes.
+  template <class C, class... Args>
+  static void launch_accumulate(MsmAccWaves aw, unsigned gridn, hipStream_t sq, Args... args)
+  {
+    using E = EC<C>;
+    if constexpr (sizeof(typename E::XYZZ) > 288) { // G2
+      k_accumulate<C, 1><<<gridn, 128, 0, sq>>>(args...);
+    } else if constexpr (sizeof(typename E::XYZZ) > 256) {
+      if (aw.minw == 2) k_accumulate<C, 2><<<gridn, 128, 0, sq>>>(args...);
+      else k_accumulate<C, 1><<<gridn, 128, 0, sq>>>(args...);
+    } else if (aw.pad) {
+      if constexpr (E::F::N <= 9) k_accumulate<C, 2, true><<<gridn, 128, 0, sq>>>(args...);
+    } else {
+      switch (aw.minw) {
+      case 2: k_accumulate<C, 2><<<gridn, 128, 0, sq>>>(args...); break;
+      case 4: k_accumulate<C, 4><<<gridn, 128, 0, sq>>>(args...); break;
+      case 1: k_accumulate<C, 1><<<gridn, 128, 0, sq>>>(args...); break;
+      default: k_accumulate<C, 3><<<gridn, 128, 0, sq>>>(args...); break;
+      }
+    }
+  }
+
+  // One call's launch state: what sort_group, accumulate_group and reduce_group read. The upper part is fixed for the call,
+  // the lower part is set by begin_sequence() for each launch sequence of bb MSMs.
+  template <class C>
+  struct MsmLaunch {
+    using E = EC<C>;
+    using Proj = typename E::Proj;
+    using FR = FieldOps<typename C::fr>;
+    static constexpr int PW = 2 * E::N32, RW = 3 * E::N32;
+    static constexpr uint32_t RWL = ReduceWindowLanes<C>::value;
+    static constexpr int CO_TPB = 256; // block size of the co-resident sort (window groups)
+    static constexpr uint32_t CO_TS = CO_TPB * SORT_EPT;
+    // groups behind the first are sorted WHILE the group before them is accumulated: small blocks that fit beside the
+    // padded k_accumulate (two waves per SIMD). Only the 9-limb G1 curves leave the registers for that.
+    static constexpr bool CAN_CORESIDE = !(sizeof(typename E::XYZZ) > 256) && E::F::N <= 9;
+    // the four-lane bucket reduction: G1, and the G2 whose point fits the registers four lanes deep (BN254's)
+    static constexpr bool QUAD_OK = C::EXT_DEGREE == 1 || sizeof(typename E::XYZZ) <= 288;
+
+    // ---- the call
+    const icicle_msm_config_t* cfg;
+    MsmBucketHook<C>* hook;
+    const MsmKnobs* kn;
+    MsmWorkspace<C>* ws;
+    hipStream_t st;
+    MsmPlan pl;
+    WinWidths ww;
+    SortPlan sp;
+    MsmReduceGeom geo;
+    int n, batch, pf, wpf;
+    uint32_t nb;
+    bool shared, stage_bases;
+    size_t npts_one, cap; // points of one MSM = bucket-list capacity per target window
+    const uint32_t *d_scalars, *d_bases;
+    uint32_t* d_res; // results of the whole batch: the caller's buffer or a lease
+    void* results_v;
+    size_t ldsA, ldsB, ldsA_co, ldsB_co, ldsOwn;
+    uint32_t own_max; // pass B, owned route (k_b_owned): partitions of at most own_max elements; 0 = none, every partition takes the sub-chunk route
+    uint32_t *dig, *cntA, *offA, *sorted, *count, *offs;
+    Proj *buckets, *chunkV, *chunkT;
+
+    // ---- the launch sequence: MSMs [b0, b0 + bb) of the batch, tw windows in NG groups
+    int b0, bb;
+    size_t tw, gparts;
+    const uint32_t* acc_bases;
+    int NG, glo[MSM_MAX_GROUPS], ghi[MSM_MAX_GROUPS];
+    int part_slot[MSM_MAX_GROUPS], part_slots; // partial-sum slots of the window combine: one per 16 windows of a group
+    uint32_t g_ovf_off[MSM_MAX_GROUPS], g_ovf_cap[MSM_MAX_GROUPS];
+    bool co_ok;
+    hipStream_t s_sort, s_red;
+    size_t scan_words;
+    TempBuf d_gscan, d_part; // scratch that concurrent groups must not share; partial sums of the window combine
+
+    // typed views of the workspace; LDS sizes of the sort kernels and their opt-in above the default limit
+    icicle_error_t prepare()
+    {
+      dig = ws->dig.template as<uint32_t>(), cntA = ws->cntA.template as<uint32_t>(), offA = ws->offA.template as<uint32_t>();
+      sorted = ws->sorted.template as<uint32_t>(), count = ws->count.template as<uint32_t>(), offs = ws->offs.template as<uint32_t>();
+      buckets = ws->buckets.template as<Proj>(), chunkV = ws->seg.template as<Proj>(), chunkT = chunkV + ws->chunk_stride;
+      ldsA =tile_lds_bytes(1u << sp.hb) + ((size_t)4 << sp.hb);
+      ldsB = tile_lds_bytes(1u << sp.lb) + ((size_t)sp.nblk + 1) * 4 + (SORT_TS / 64) * 4;
+      ldsA_co = tile_lds_bytes(1u << sp.hb, CO_TS) + ((size_t)4 << sp.hb);
+      ldsB_co = tile_lds_bytes(1u << sp.lb, CO_TS) + ((size_t)sp.nblk + 1) * 4 + (CO_TS / 64) * 4;
+      if (ldsA > 156 * 1024 || ldsB > 156 * 1024) return ICICLE_INVALID_ARGUMENT;
+      for (const void* k : {(const void*)k_a_scatter<false, 1024>, (const void*)k_a_scatter<true, 1024>, (const void*)k_b_count, (const void*)k_b_scatter<1024>})
+        HIP_TRY(hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, 156 * 1024), ICICLE_INVALID_ARGUMENT);
+      own_max = PASSB_OWN_MAX_DEFAULT;
+      if (cfg->ext) own_max = (uint32_t)std::max(0, reinterpret_cast<const ConfigExt*>(cfg->ext)->get_int("hip_msm_passb_own_max", (int)own_max));
+      ldsOwn = ldsB + ((size_t)4 << sp.lb); // + the write cursors
+      if (own_max && sp.lb != 0) {
+        int dev = 0, lds_dev = 0;
+        HIP_TRY(hipGetDevice(&dev), ICICLE_INVALID_DEVICE);
+        HIP_TRY(hipDeviceGetAttribute(&lds_dev, hipDeviceAttributeMaxSharedMemoryPerBlock, dev), ICICLE_INVALID_DEVICE);
+        if (ldsOwn > (size_t)lds_dev) return ICICLE_INVALID_ARGUMENT;
+        HIP_TRY(hipFuncSetAttribute((const void*)k_b_owned<1024>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)ldsOwn), ICICLE_INVALID_ARGUMENT);
+      }
       return ICICLE_SUCCESS;
     }
 
-    // ---- stage inputs
-    TempBuf d_sc_tmp, d_b_tmp;
-    const uint32_t* d_scalars = (const uint32_t*)scalars_v;
-    if (!cfg->are_scalars_on_device) {
-      const size_t bytes = (size_t)batch * n * FR::N32 * 4;
-      HIP_TRY(d_sc_tmp.alloc(bytes, st), ICICLE_ALLOCATION_FAILED);
-      HIP_TRY(hipMemcpyAsync(d_sc_tmp.ptr(), scalars_v, bytes, hipMemcpyHostToDevice, st), ICICLE_COPY_FAILED);
-      d_scalars = d_sc_tmp.as<uint32_t>();
-    }
-    const uint32_t* d_bases = (const uint32_t*)bases_v;
-    if (!cfg->are_points_on_device) {
-      const size_t bytes = npts_all * PW * 4;
-      HIP_TRY(d_b_tmp.alloc(bytes, st), ICICLE_ALLOCATION_FAILED);
-      HIP_TRY(hipMemcpyAsync(d_b_tmp.ptr(), bases_v, bytes, hipMemcpyHostToDevice, st), ICICLE_COPY_FAILED);
-      d_bases = d_b_tmp.as<uint32_t>();
-    }
-
-    // ---- geometry
-    const uint32_t nb = pl.nb;
-    const int wpf = pl.wpf;
-    const size_t cap = npts_one; // bucket-list capacity per target window
-    SortPlan sp;
+    // digits and pass-A tables of MSMs [b0, ...), then the window groups, their streams, leases and overflow slices
+    icicle_error_t begin_sequence(int first_msm, int BB)
     {
-      const int kb = pl.c - 1;
-      // each tile-sorted pass ranks into <= 1024 destinations (one per thread of the block); small
-      // windows (kb <= 10) need a single level: pass A already produces the bucket lists
-      int hb = kb <= 10 ? kb : (kb + 1) / 2;
-      if (const char* e = getenv("ICICLE_HIP_MSM_HB")) hb = atoi(e);
-      hb = std::max(kb - 11, std::min(std::min(kb, 10), hb)); // pass A: at most 2^10 partitions; pass B: up to 2^11 bins (c = 22)
-      if (hb < 0 || hb > 10 || kb - hb > 11) return ICICLE_INVALID_ARGUMENT;
-      sp.hb = hb;
-      sp.lb = kb - hb;
-      sp.jb = 0;
-      while ((1 << sp.jb) < pf)
-        sp.jb++;
-      int logn = 0;
-      while (((size_t)1 << logn) < (size_t)n)
-        logn++;
-      const int max_chunk = 31 - sp.lb - sp.jb;
-      if (max_chunk < 10) return ICICLE_INVALID_ARGUMENT;
-      sp.chunk_log = std::max(10, std::min(max_chunk, std::max(17, logn - 9)));
-      if (sp.chunk_log < logn - 9) return ICICLE_INVALID_ARGUMENT; // would need more than 512 pass-A blocks per window
-      sp.nblk = (int)(((size_t)n + ((size_t)1 << sp.chunk_log) - 1) >> sp.chunk_log);
-    }
-    const bool single_level = (sp.lb == 0);
-    const size_t nparts_w = (size_t)1 << sp.hb;
-    // bucket reduction geometry: a wave owns a chunk of 64*mrow buckets; at most RWL chunks per window (one thread of
-    // the per-window kernel each), at least 16 rows per lane when the window is big enough to amortise the wave scans
-    constexpr uint32_t RWL = ReduceWindowLanes<C>::value;
-    // Rows per lane: 16 amortise the wave scans; a single mid-size MSM has fewer reduction waves than the chip has SIMDs
-    // and is bound by the length of one wave's chain, so there the rows shrink until the waves fill the SIMDs once
-    // (2^16, c = 15: 272 waves of 16 rows -> 544 of 8, 1.78 -> 1.59 ms; at 2^20 16 rows already make 960 waves). The rule
-    // depends on the window plan only (every shard of a multi-device call derives the same geometry).
-    uint32_t mrow_cap = 16;
-    if (batch == 1 && nb >= 8192) {
-      uint32_t need = (uint32_t)(((uint64_t)pl.wpf * nb + 65535) / 65536), p2 = 2;
-      while (p2 < need)
-        p2 <<= 1;
-      mrow_cap = std::min<uint32_t>(16, p2);
-    }
-    if (const char* e = getenv("ICICLE_HIP_MSM_MROW")) mrow_cap = (uint32_t)std::max(1, atoi(e)); // (A/B knob)
-    const uint32_t mrow = std::max<uint32_t>(1, std::max<uint32_t>(nb / (64 * RWL), std::min<uint32_t>(mrow_cap, nb / 64)));
-    const uint32_t m = 64 * mrow;                       // buckets per chunk ("segment" of the exchange hook)
-    const uint32_t nseg = std::max<uint32_t>(1, nb / m); // chunks per window
-    uint32_t log_chunk = 0;
-    while ((1u << log_chunk) < m)
-      log_chunk++;
-
-    // ---- batch folding: BB MSMs of the batch run as ONE launch sequence with BB*wpf windows
-    // (wrappers/rust/icicle-core/src/msm/tests.rs:92-254 batches; small MSMs would otherwise leave the
-    // GPU idle). BB is bounded by a memory budget and by the grid.y limit.
-    const size_t per_msm_bytes = (size_t)pl.nwin * n * 4 + (single_level ? 1 : 2) * (size_t)wpf * cap * 4 + (size_t)wpf * nb * (sizeof(typename E::Proj) + 12) +
-                                 (size_t)wpf * nparts_w * sp.nblk * 8 + (shared || !(cfg->are_points_montgomery_form) ? 0 : npts_one * PW * 4);
-    size_t budget = (size_t)48 << 30;
-    {
-      size_t free_b = 0, total_b = 0;
-      if (hipMemGetInfo(&free_b, &total_b) == hipSuccess) budget = std::min(budget, free_b / 2);
-    }
-    int BB = (int)std::max<size_t>(1, std::min<size_t>((size_t)batch, budget / std::max<size_t>(per_msm_bytes, 1)));
-    BB = std::min(BB, std::max(1, 60000 / wpf));
-    if (hook && BB < batch) { // a bucket exchange needs the whole batch in one launch group (msm_multi_run checked the grid limit)
-      BB = batch;
-      if ((size_t)BB * wpf > 60000) return ICICLE_INVALID_ARGUMENT;
-    }
-    const size_t TW = (size_t)BB * wpf; // windows per launch
-    const size_t nbk = TW * nb;
-    const size_t nparts = TW << sp.hb;
-    const size_t tabA = nparts * sp.nblk + TW; // [wl][h][b] counters + per-window totals
-    const size_t elems_max = (size_t)BB * n * pl.nwin + 1;
-    const uint32_t maxblkB = (uint32_t)std::min<size_t>(nparts + (elems_max >> CHUNKB_LOG) + 2, 0x7fffffffu);
-    const uint32_t ovf_cap = (uint32_t)std::min<size_t>(elems_max / pl.seg + 16, 0x7fffffffu);
-
-    TempBuf d_mont, d_dig, d_partA, d_sorted, d_cntA, d_offA, d_bstart, d_count, d_offs, d_cursor, d_buckets, d_seg, d_win, d_ovf, d_ovfpart, d_ovfcnt, d_scansum, d_perm, d_sztab, d_szoff, d_firsts;
-    // bases are gathered where they lie unless they need converting (reference-Montgomery input) or realigning
-    const bool stage_bases = cfg->are_points_montgomery_form || (((uintptr_t)d_bases) & 15) != 0;
-    if (stage_bases) HIP_TRY(d_mont.alloc((shared ? 1 : (size_t)BB) * npts_one * PW * 4, st), ICICLE_ALLOCATION_FAILED);
-    HIP_TRY(d_dig.alloc((size_t)BB * pl.nwin * n * 4, st), ICICLE_ALLOCATION_FAILED);
-    if (!single_level) HIP_TRY(d_partA.alloc(TW * cap * 4, st), ICICLE_ALLOCATION_FAILED);
-    HIP_TRY(d_sorted.alloc(TW * cap * 4 + 64, st), ICICLE_ALLOCATION_FAILED); // + slack: k_accumulate reads lists in groups of 4
-    HIP_TRY(d_cntA.alloc(tabA * 4, st), ICICLE_ALLOCATION_FAILED);
-    HIP_TRY(d_offA.alloc(tabA * 4, st), ICICLE_ALLOCATION_FAILED);
-    HIP_TRY(d_bstart.alloc((nparts + 1 + 16) * 4, st), ICICLE_ALLOCATION_FAILED); // + one end marker per window group
-    HIP_TRY(d_count.alloc(nbk * 4, st), ICICLE_ALLOCATION_FAILED);
-    HIP_TRY(d_offs.alloc(nbk * 4, st), ICICLE_ALLOCATION_FAILED);
-    HIP_TRY(d_cursor.alloc(nbk * 4, st), ICICLE_ALLOCATION_FAILED);
-    HIP_TRY(d_buckets.alloc(nbk * sizeof(typename E::Proj), st), ICICLE_ALLOCATION_FAILED);
-    HIP_TRY(d_seg.alloc(2 * TW * std::max<size_t>(nseg, 64) * sizeof(typename E::Proj), st), ICICLE_ALLOCATION_FAILED); // chunk V | chunk T (64: the quad reduction's chunks per window)
-    HIP_TRY(d_win.alloc(TW * sizeof(typename E::Proj), st), ICICLE_ALLOCATION_FAILED);
-    HIP_TRY(d_ovf.alloc(((size_t)ovf_cap + 16 * 16) * sizeof(OvfSeg), st), ICICLE_ALLOCATION_FAILED); // (+ the per-group slack of the pipelined schedule)
-    HIP_TRY(d_ovfpart.alloc(((size_t)ovf_cap + 16 * 16) * sizeof(typename E::Proj), st), ICICLE_ALLOCATION_FAILED);
-    HIP_TRY(d_firsts.alloc(((size_t)ovf_cap + 16 * 17) * 4 + 4, st), ICICLE_ALLOCATION_FAILED);
-    HIP_TRY(d_ovfcnt.alloc(16 * 16, st), ICICLE_ALLOCATION_FAILED); // [overflow segments, overflowing buckets, largest bucket, -] per window group
-    const size_t szblk_max = (nbk + SZ_CHUNK - 1) / SZ_CHUNK + 16; // (+ one partial block per window group)
-    HIP_TRY(d_perm.alloc(nbk * 4, st), ICICLE_ALLOCATION_FAILED);
-    HIP_TRY(d_sztab.alloc(szblk_max * SZ_BINS * 4, st), ICICLE_ALLOCATION_FAILED);
-    HIP_TRY(d_szoff.alloc(szblk_max * SZ_BINS * 4, st), ICICLE_ALLOCATION_FAILED);
-    HIP_TRY(d_scansum.alloc(TW * (std::max<size_t>((size_t)sp.nblk << sp.hb, nb) / SCAN_CHUNK + 1) * 4, st), ICICLE_ALLOCATION_FAILED);
-
-    const size_t ldsA = tile_lds_bytes(1u << sp.hb) + ((size_t)4 << sp.hb);
-    const size_t ldsB = tile_lds_bytes(1u << sp.lb) + ((size_t)sp.nblk + 1) * 4 + (SORT_TS / 64) * 4;
-    constexpr int CO_TPB = 256; // block size of the co-resident sort (window groups, below)
-    constexpr uint32_t CO_TS = CO_TPB * SORT_EPT;
-    const size_t ldsA_co = tile_lds_bytes(1u << sp.hb, CO_TS) + ((size_t)4 << sp.hb);
-    const size_t ldsB_co = tile_lds_bytes(1u << sp.lb, CO_TS) + ((size_t)sp.nblk + 1) * 4 + (CO_TS / 64) * 4;
-    if (ldsA > 156 * 1024 || ldsB > 156 * 1024) return ICICLE_INVALID_ARGUMENT;
-    HIP_TRY(hipFuncSetAttribute((const void*)k_a_scatter<false, 1024>, hipFuncAttributeMaxDynamicSharedMemorySize, 156 * 1024), ICICLE_INVALID_ARGUMENT);
-    HIP_TRY(hipFuncSetAttribute((const void*)k_a_scatter<true, 1024>, hipFuncAttributeMaxDynamicSharedMemorySize, 156 * 1024), ICICLE_INVALID_ARGUMENT);
-    HIP_TRY(hipFuncSetAttribute((const void*)k_b_count, hipFuncAttributeMaxDynamicSharedMemorySize, 156 * 1024), ICICLE_INVALID_ARGUMENT);
-    HIP_TRY(hipFuncSetAttribute((const void*)k_b_scatter<1024>, hipFuncAttributeMaxDynamicSharedMemorySize, 156 * 1024), ICICLE_INVALID_ARGUMENT);
-    // pass B, owned route (k_b_owned): partitions of at most own_max elements; 0 = none, every partition takes the sub-chunk route
-    uint32_t own_max = PASSB_OWN_MAX_DEFAULT;
-    if (cfg->ext) own_max = (uint32_t)std::max(0, reinterpret_cast<const ConfigExt*>(cfg->ext)->get_int("hip_msm_passb_own_max", (int)own_max));
-    const size_t ldsOwn = ldsB + ((size_t)4 << sp.lb); // + the write cursors
-    if (own_max && !single_level) {
-      int dev = 0, lds_dev = 0;
-      HIP_TRY(hipGetDevice(&dev), ICICLE_INVALID_DEVICE);
-      HIP_TRY(hipDeviceGetAttribute(&lds_dev, hipDeviceAttributeMaxSharedMemoryPerBlock, dev), ICICLE_INVALID_DEVICE);
-      if (ldsOwn > (size_t)lds_dev) return ICICLE_INVALID_ARGUMENT;
-      HIP_TRY(hipFuncSetAttribute((const void*)k_b_owned<1024>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)ldsOwn), ICICLE_INVALID_ARGUMENT);
-    }
-
-    uint32_t* dig = d_dig.as<uint32_t>();
-    uint32_t* cntA = d_cntA.as<uint32_t>();
-    uint32_t* offA = d_offA.as<uint32_t>();
-    uint32_t* sorted = d_sorted.as<uint32_t>();
-    uint32_t* count = d_count.as<uint32_t>();
-    uint32_t* offs = d_offs.as<uint32_t>();
-    typename E::Proj* buckets = d_buckets.as<typename E::Proj>();
-
-    for (int b0 = 0; b0 < batch; b0 += BB) {
-      const int bb = std::min(BB, batch - b0); // MSMs in this launch sequence
-      const size_t tw = (size_t)bb * wpf;
-      const size_t gbk = tw * nb;
-      const size_t gparts = tw << sp.hb;
-      const uint32_t* acc_bases = d_bases + (shared ? 0 : (size_t)b0 * npts_one * PW);
+      b0 = first_msm;
+      bb = std::min(BB, batch - b0);
+      tw = (size_t)bb * wpf;
+      gparts = tw << sp.hb;
+      acc_bases = d_bases + (shared ? 0 : (size_t)b0 * npts_one * PW);
       if (stage_bases) {
         if (b0 == 0 || !shared) {
           const size_t ncoord = (shared ? 1 : (size_t)bb) * npts_one * 2 * (E::N32 / FieldOps<typename C::fq>::N32);
-          k_bases_stage<C><<<dim3((unsigned)((ncoord + 255) / 256)), 256, 0, st>>>(acc_bases, d_mont.as<uint32_t>(), ncoord, cfg->are_points_montgomery_form);
+          k_bases_stage<C><<<dim3((unsigned)((ncoord + 255) / 256)), 256, 0, st>>>(acc_bases, ws->mont.template as<uint32_t>(), ncoord, cfg->are_points_montgomery_form);
           LAUNCH_CHECK("k_bases_stage", st);
         }
-        acc_bases = d_mont.as<uint32_t>();
+        acc_bases = ws->mont.template as<uint32_t>();
       }
       KernelTimer::begin(2, st);
       const uint32_t* sc = d_scalars + (size_t)b0 * n * FR::N32;
@@ -1904,383 +1887,396 @@ namespace icicle_hip {
       }
       // the per-window totals live right after the [tw][2^hb][nblk] table of THIS launch
       {
-        const uint32_t m = (uint32_t)(nparts_w * sp.nblk), nch = (m + SCAN_CHUNK - 1) / SCAN_CHUNK;
-        k_scan_sums<<<dim3(nch, (unsigned)tw), 1024, 0, st>>>(cntA, d_scansum.as<uint32_t>(), m);
-        k_scan_apply<<<dim3(nch, (unsigned)tw), 1024, 0, st>>>(cntA, d_scansum.as<uint32_t>(), offA, nullptr, offA + (size_t)tw * m, m);
+        const uint32_t m = (uint32_t)(((size_t)1 << sp.hb) * sp.nblk), nch = (m + SCAN_CHUNK - 1) / SCAN_CHUNK;
+        k_scan_sums<<<dim3(nch, (unsigned)tw), 1024, 0, st>>>(cntA, ws->scansum.template as<uint32_t>(), m);
+        k_scan_apply<<<dim3(nch, (unsigned)tw), 1024, 0, st>>>(cntA, ws->scansum.template as<uint32_t>(), offA, nullptr, offA + (size_t)tw * m, m);
       }
       LAUNCH_CHECK("k_scan_a", st);
 
-      // ---- window groups ("pipelined schedule"). Everything behind the digit pass is independent
-      // per window, and the phases are bound by different things: the sort by memory latency, bucket accumulation by
-      // VALU issue, the window combine by the latency of one doubling chain. A single large MSM is therefore cut into
-      // NG groups of windows, HIGHEST windows first: while group g is accumulated on the main stream, group g + 1 is
-      // sorted on a second stream and group g - 1 is reduced and scaled by its 2^(c*w) on a third, so the long doubling
-      // chains of the high windows and most of the sort leave the critical path. NG = 1 is the plain sequence.
-      // Batches (bb > 1) already fill the chip with independent work, and a bucket-exchange hook wants all windows at once.
-      int glo[MSM_MAX_GROUPS], ghi[MSM_MAX_GROUPS];
-      int want_groups = 1;
-      if (bb == 1 && !hook && tw >= 4) {
-        static const int env_ng = getenv("ICICLE_HIP_MSM_GROUPS") ? atoi(getenv("ICICLE_HIP_MSM_GROUPS")) : MSM_DEFAULT_GROUPS;
-        want_groups = env_ng;
-      }
-      const int NG = msm_window_groups((int)tw, want_groups, glo, ghi); // msm_plan.h
-      hipStream_t s_sort = st, s_red = st, s_acc = st;
+      // ---- window groups (run_pipelined): NG = 1 is the plain sequence. Batches (bb > 1) already fill the chip with
+      // independent work, and a bucket-exchange hook wants all windows at once.
+      const int want_groups = (bb == 1 && !hook && tw >= 4) ? kn->groups : 1;
+      NG = msm_window_groups((int)tw, want_groups, glo, ghi); // msm_plan.h
+      s_sort = s_red = st;
       if (NG > 1) {
         s_sort = side_stream(10);
         s_red = side_stream(11);
         if (!s_sort || !s_red) return ICICLE_STREAM_CREATION_FAILED;
       }
-      // scratch that concurrent groups must not share
-      TempBuf d_gscan, d_part;
-      const size_t scan_words = tw * (std::max<size_t>((size_t)sp.nblk << sp.hb, nb) / SCAN_CHUNK + 1) + (szblk_max * SZ_BINS) / SCAN_CHUNK + 16;
-      int part_slot[MSM_MAX_GROUPS], part_slots = 0; // partial-sum slots of the window combine: one per 16 windows of a group
+      scan_words = tw * ws->scan_row_words + (ws->szblk_max * SZ_BINS) / SCAN_CHUNK + MsmWorkspace<C>::SCAN_TAIL_WORDS;
+      part_slots = 0;
       for (int g = 0; g < NG; g++) {
         part_slot[g] = part_slots;
         part_slots += (ghi[g] - glo[g] + FINAL_WINDOWS_PER_BLOCK - 1) / FINAL_WINDOWS_PER_BLOCK;
       }
       // (one group: blocks of 16 windows per MSM of the launch; several groups: bb == 1 and the slots counted above)
-      HIP_TRY(d_part.alloc((size_t)(NG > 1 ? part_slots : (wpf + FINAL_WINDOWS_PER_BLOCK - 1) / FINAL_WINDOWS_PER_BLOCK) * bb * sizeof(typename E::Proj), st), ICICLE_ALLOCATION_FAILED);
+      HIP_TRY(d_part.alloc((size_t)(NG > 1 ? part_slots : (wpf + FINAL_WINDOWS_PER_BLOCK - 1) / FINAL_WINDOWS_PER_BLOCK) * bb * sizeof(Proj), st), ICICLE_ALLOCATION_FAILED);
       if (NG > 1) {
         HIP_TRY(d_gscan.alloc((size_t)NG * scan_words * 4, st), ICICLE_ALLOCATION_FAILED);
-        HIP_TRY(hipMemsetAsync(d_ovfcnt.ptr(), 0, 16 * 16, st), ICICLE_COPY_FAILED);
-      }
-      hipEvent_t ev_ready = nullptr, ev_sorted[16] = {nullptr}, ev_acc[16] = {nullptr}, ev_red[16] = {nullptr};
-      if (NG > 1) {
-        ev_ready = ring_event();
+        HIP_TRY(hipMemsetAsync(ws->ovfcnt.ptr(), 0, MSM_MAX_GROUPS * MsmWorkspace<C>::OVFCNT_GROUP_BYTES, st), ICICLE_COPY_FAILED);
+        hipEvent_t ev_ready = ring_event();
         if (!ev_ready) return ICICLE_ALLOCATION_FAILED;
         HIP_TRY(hipEventRecord(ev_ready, st), ICICLE_SYNCHRONIZATION_FAILED); // digits, pass-A tables and every buffer lease are in place
         HIP_TRY(hipStreamWaitEvent(s_sort, ev_ready, 0), ICICLE_SYNCHRONIZATION_FAILED);
       }
-      typename E::Proj* chunkV = d_seg.as<typename E::Proj>();
-      typename E::Proj* chunkT = chunkV + TW * std::max<size_t>(nseg, 64);
       uint32_t ovf_off = 0;
-      uint32_t g_ovf_off[16], g_ovf_cap[16];
-      for (int g = 0; g < NG; g++) { // overflow segments of a group <= (list entries of its windows) / seg; the caps add up to ovf_cap + 16 NG
+      for (int g = 0; g < NG; g++) { // overflow segments of a group <= (list entries of its windows) / seg; the caps add up to ovf_cap + OVF_ROUNDING * NG
         size_t src = 0; // source windows folded into the group's target windows (precompute: j * wpf + wp < nwin)
         for (int wp = glo[g]; wp < ghi[g]; wp++)
           for (int j = 0; j < pf; j++)
             src += (j * wpf + wp % wpf < pl.nwin) ? 1 : 0;
         g_ovf_off[g] = ovf_off;
-        g_ovf_cap[g] = NG == 1 ? ovf_cap : (uint32_t)std::min<size_t>(((size_t)n * src) / pl.seg + 16, ovf_cap);
+        g_ovf_cap[g] = NG == 1 ? ws->ovf_cap : (uint32_t)std::min<size_t>(((size_t)n * src) / pl.seg + MsmWorkspace<C>::OVF_ROUNDING, ws->ovf_cap);
         ovf_off += g_ovf_cap[g];
       }
+      co_ok = CAN_CORESIDE && kn->coresident && NG > 1 && ldsA_co <= 60 * 1024 && ldsB_co <= 60 * 1024;
+      return ICICLE_SUCCESS;
+    }
 
-      // ---- phase 1 of a group: bucket lists (pass-A scatter, pass B, overflow plan, size-balanced order)
-      // groups behind the first are sorted WHILE the group before them is accumulated: small blocks that fit beside the
-      // padded k_accumulate (two waves per SIMD). Only the 9-limb G1 curves leave the registers for that.
-      constexpr bool CAN_CORESIDE = !(sizeof(typename E::XYZZ) > 256) && E::F::N <= 9;
-      static const bool co_env = !(getenv("ICICLE_HIP_MSM_CORESIDENT") && atoi(getenv("ICICLE_HIP_MSM_CORESIDENT")) == 0);
-      const bool co_ok = CAN_CORESIDE && co_env && NG > 1 && ldsA_co <= 60 * 1024 && ldsB_co <= 60 * 1024;
-      auto sort_group = [&](int g, hipStream_t sq) -> icicle_error_t {
-        const bool coresident = co_ok && g > 0;
-        const int w0 = glo[g], nw = ghi[g] - glo[g];
-        const size_t bk0 = (size_t)w0 * nb, nbk_g = (size_t)nw * nb;
-        const uint32_t p0 = (uint32_t)((size_t)w0 << sp.hb), np_g = (uint32_t)((size_t)nw << sp.hb);
-        uint32_t* scan_g = NG > 1 ? d_gscan.as<uint32_t>() + (size_t)g * scan_words : d_scansum.as<uint32_t>();
-        if (single_level) {
-          if (coresident) k_a_scatter<true, CO_TPB><<<dim3(sp.nblk, (unsigned)nw), CO_TPB, ldsA_co, sq>>>(dig, offA, sorted, n, pl.nwin, wpf, pf, sp, cap, w0);
-          else k_a_scatter<true, 1024><<<dim3(sp.nblk, (unsigned)nw), 1024, ldsA, sq>>>(dig, offA, sorted, n, pl.nwin, wpf, pf, sp, cap, w0);
-          LAUNCH_CHECK("k_a_scatter<final>", sq);
-          k_tables_from_a<<<(unsigned)((nbk_g + 255) / 256), 256, 0, sq>>>(offA, count, offs, nbk_g, nb, sp.nblk, gparts * sp.nblk, bk0);
-          LAUNCH_CHECK("k_tables_from_a", sq);
-        } else {
-          uint32_t* partA = d_partA.as<uint32_t>();
-          uint32_t* bstart = d_bstart.as<uint32_t>() + p0 + (NG - 1 - g); // nparts_g + 1 entries per group, groups in window order
-          const size_t elems = (size_t)bb * n * pf * (size_t)nw + 1;
-          const uint32_t nblkB = (uint32_t)std::min<size_t>(np_g + (elems >> CHUNKB_LOG) + 2, maxblkB);
-          if (coresident) k_a_scatter<false, CO_TPB><<<dim3(sp.nblk, (unsigned)nw), CO_TPB, ldsA_co, sq>>>(dig, offA, partA, n, pl.nwin, wpf, pf, sp, cap, w0);
-          else k_a_scatter<false, 1024><<<dim3(sp.nblk, (unsigned)nw), 1024, ldsA, sq>>>(dig, offA, partA, n, pl.nwin, wpf, pf, sp, cap, w0);
-          LAUNCH_CHECK("k_a_scatter", sq);
-          // partitions of at most own_g elements: k_b_owned, one block each; the others (and all of them when own_g == 0):
-          // sub-chunks. The host cannot know which kind it has, so both routes are launched; an idle one returns at once.
-          const uint32_t own_g = coresident ? 0u : own_max;
-          k_b_plan<<<1, 1024, 0, sq>>>(offA, bstart, np_g, (int)tw, sp.hb, sp.nblk, p0, own_g);
-          LAUNCH_CHECK("k_b_plan", sq);
-          if (own_g) {
-            k_b_owned<1024><<<np_g, 1024, ldsOwn, sq>>>(partA, offA, count, offs, sorted, (int)tw, pf, sp, cap, nb, p0, own_g);
-            LAUNCH_CHECK("k_b_owned", sq);
-          } else {
-            HIP_TRY(hipMemsetAsync(count + bk0, 0, nbk_g * 4, sq), ICICLE_COPY_FAILED);
-          }
-          k_b_count<<<nblkB, 1024, ((size_t)1 << sp.lb) * 4, sq>>>(partA, offA, bstart, count, np_g, (int)tw, sp, cap, nb, p0);
-          LAUNCH_CHECK("k_b_count", sq);
-          if (own_g) {
-            k_b_scan_part<<<np_g, 1024, 0, sq>>>(offA, count, offs, d_cursor.as<uint32_t>(), (int)tw, sp, nb, p0, own_g);
-          } else {
-            const uint32_t nch = (nb + SCAN_CHUNK - 1) / SCAN_CHUNK;
-            k_scan_sums<<<dim3(nch, (unsigned)nw), 1024, 0, sq>>>(count + bk0, scan_g, nb);
-            k_scan_apply<<<dim3(nch, (unsigned)nw), 1024, 0, sq>>>(count + bk0, scan_g, offs + bk0, d_cursor.as<uint32_t>() + bk0, nullptr, nb);
-          }
-          LAUNCH_CHECK("k_scan_buckets", sq);
-          if (coresident) k_b_scatter<CO_TPB><<<nblkB, CO_TPB, ldsB_co, sq>>>(partA, offA, bstart, d_cursor.as<uint32_t>(), sorted, np_g, (int)tw, pf, sp, cap, nb, p0);
-          else k_b_scatter<1024><<<nblkB, 1024, ldsB, sq>>>(partA, offA, bstart, d_cursor.as<uint32_t>(), sorted, np_g, (int)tw, pf, sp, cap, nb, p0);
-          LAUNCH_CHECK("k_b_scatter", sq);
-        }
-        uint32_t* ovfcnt = d_ovfcnt.as<uint32_t>() + 4 * g;
-        if (NG == 1) HIP_TRY(hipMemsetAsync(ovfcnt, 0, 16, sq), ICICLE_COPY_FAILED);
-        k_plan_overflow<<<(unsigned)((nbk_g + 255) / 256), 256, 0, sq>>>(count, nbk_g, pl.seg, ovfcnt, d_ovf.as<OvfSeg>() + g_ovf_off[g], d_firsts.as<uint32_t>() + g_ovf_off[g] + g, g_ovf_cap[g], bk0);
-        LAUNCH_CHECK("k_plan_overflow", sq);
-        {
-          const unsigned szblk = (unsigned)((nbk_g + SZ_CHUNK - 1) / SZ_CHUNK);
-          const size_t sz0 = (bk0 / SZ_CHUNK + (size_t)(NG - 1 - g)) * SZ_BINS; // this group's slice of the size tables (groups in window order)
-          const uint32_t m = szblk * SZ_BINS, nch = (m + SCAN_CHUNK - 1) / SCAN_CHUNK;
-          uint32_t* sztab = d_sztab.as<uint32_t>() + sz0;
-          uint32_t* szoff = d_szoff.as<uint32_t>() + sz0;
-          k_bsize_count<<<szblk, 1024, 0, sq>>>(count, sztab, nbk_g, pl.seg, bk0, nb, (uint32_t)pl.n_lo);
-          k_scan_sums<<<dim3(nch, 1), 1024, 0, sq>>>(sztab, scan_g, m);
-          k_scan_apply<<<dim3(nch, 1), 1024, 0, sq>>>(sztab, scan_g, szoff, nullptr, nullptr, m);
-          k_bsize_scatter<<<szblk, 1024, 0, sq>>>(count, szoff, d_perm.as<uint32_t>() + bk0, nbk_g, pl.seg, bk0, nb, (uint32_t)pl.n_lo);
-          LAUNCH_CHECK("k_bsize_scatter", sq);
-        }
-        return ICICLE_SUCCESS;
-      };
-
-      // ---- phase 2 of a group: bucket accumulation (+ the fold of the overflow partials)
-      auto accumulate_group = [&](int g, hipStream_t sq) -> icicle_error_t {
-        const int w0 = glo[g], nw = ghi[g] - glo[g];
-        const size_t bk0 = (size_t)w0 * nb, nbk_g = (size_t)nw * nb;
-        uint32_t* ovfcnt = d_ovfcnt.as<uint32_t>() + 4 * g;
-        OvfSeg* ovf = d_ovf.as<OvfSeg>() + g_ovf_off[g];
-        typename E::Proj* ovfpart = d_ovfpart.as<typename E::Proj>() + g_ovf_off[g];
-        const uint32_t ocap = g_ovf_cap[g];
-        KernelTimer::begin(0, sq);
-        {
-          // waves per SIMD the register allocator must leave room for: 3 fits BN254 G1 (157 VGPRs) without
-          // spilling, 2 fits BLS12-381 G1 (14-limb elements) and BN254 G2, 1 for BLS12-381 G2
-          constexpr bool BIGPT = sizeof(typename E::XYZZ) > 256; // G2
-          static const int minw = getenv("ICICLE_HIP_MSM_ACC_WAVES") ? atoi(getenv("ICICLE_HIP_MSM_ACC_WAVES"))
-                                                                     : (BIGPT ? (sizeof(typename E::XYZZ) <= 288 ? 2 : 1) : (E::F::N <= 9 ? 3 : 2));
-          // threads = the group's buckets in use (perm[] lists exactly those) + its overflow slots
-          const int nlo_g = std::max(0, std::min(pl.n_lo, w0 + nw) - w0); // (bb == 1 whenever n_lo > 0)
-          const size_t nbk_used = nbk_g - (size_t)nlo_g * (nb / 2);
-          const size_t nthreads_acc = nbk_used + ocap;
-          const unsigned gridn = (unsigned)((nthreads_acc + 127) / 128);
-          const size_t bstride = shared ? 0 : npts_one * PW;
-#define ACC_ARGS acc_bases, sorted, count, offs, buckets, ovfpart, ovf, ovfcnt, d_perm.as<uint32_t>() + bk0, ocap, nb, nbk_used, cap, pl.seg, wpf, bstride
-          if constexpr (BIGPT) {
-            if constexpr (sizeof(typename E::XYZZ) <= 288) {
-              if (minw >= 2) k_accumulate<C, 2><<<gridn, 128, 0, sq>>>(ACC_ARGS);
-              else k_accumulate<C, 1><<<gridn, 128, 0, sq>>>(ACC_ARGS);
-            } else {
-              k_accumulate<C, 1><<<gridn, 128, 0, sq>>>(ACC_ARGS);
-            }
-          } else {
-            if (co_ok) {
-              if constexpr (CAN_CORESIDE) k_accumulate<C, 2, true><<<gridn, 128, 0, sq>>>(ACC_ARGS);
-            } else if (minw == 2) k_accumulate<C, 2><<<gridn, 128, 0, sq>>>(ACC_ARGS);
-            else if (minw == 4) k_accumulate<C, 4><<<gridn, 128, 0, sq>>>(ACC_ARGS);
-            else if (minw == 1) k_accumulate<C, 1><<<gridn, 128, 0, sq>>>(ACC_ARGS);
-            else k_accumulate<C, 3><<<gridn, 128, 0, sq>>>(ACC_ARGS);
-          }
-#undef ACC_ARGS
-        }
-        LAUNCH_CHECK("k_accumulate", sq);
-        KernelTimer::end(0, sq);
-        k_fold_overflow<C><<<std::min<uint32_t>(ocap, 4096), 64, 0, sq>>>(buckets, ovfpart, ovf, d_firsts.as<uint32_t>() + g_ovf_off[g] + g, ovfcnt, ocap);
-        LAUNCH_CHECK("k_fold_overflow", sq);
-        return ICICLE_SUCCESS;
-      };
-
-      // ---- phase 3 of a group: bucket reduction of its windows, then their share of the window combine
-      auto reduce_group = [&](int g, hipStream_t sq, uint32_t seg_lo, uint32_t nsegr) -> icicle_error_t {
-        const int w0 = glo[g], nw = ghi[g] - glo[g];
-        // windows [w0, split) of the group are the narrow windows of a mixed-width plan (half the buckets, nseg_lo chunks), the
-        // rest wide; one launch of each kernel serves both (a uniform plan has n_lo = 0: no narrow windows). (bb == 1 whenever n_lo > 0)
-        const int split = std::min(std::max(pl.n_lo, w0), w0 + nw);
-        const uint32_t nlo_w = (uint32_t)(split - w0);
-        // narrow windows: half the rows per lane, so that they have as many chunks as the wide ones (see k_reduce_wave)
-        // Measured and left OFF (profiles/r06_msm_reduce_balance_ab.txt, same box, BN254 2^26): tail 4.72 / 4.75 ms without, 4.90 / 4.86 ms
-        // with -- the extra 1280 waves bring 19 scan additions each, more than the evened-out SIMD load gives back. ICICLE_HIP_MSM_REDUCE_BALANCE=1: on.
-        static const bool balance = getenv("ICICLE_HIP_MSM_REDUCE_BALANCE") && atoi(getenv("ICICLE_HIP_MSM_REDUCE_BALANCE")) != 0;
-        const uint32_t mrow_lo = (balance && nlo_w > 0 && mrow >= 2 && !hook) ? mrow / 2 : mrow;
-        const uint32_t nseg_lo = std::max<uint32_t>(1, (nb / 2) / (64 * mrow_lo));
-        const uint32_t log_chunk_lo = mrow_lo == mrow ? log_chunk : log_chunk - 1;
-        const bool direct = (nseg == 1 && nsegr == 1 && seg_lo == 0);
-        typename E::Proj* win = d_win.as<typename E::Proj>() + w0;
-        typename E::Proj* cV = chunkV + (size_t)w0 * nseg;
-        typename E::Proj* cT = chunkT + (size_t)w0 * nseg;
-        const size_t nblocks = (size_t)nlo_w * nseg_lo + (size_t)(nw - nlo_w) * nsegr;
-        // whole small windows: several per wave (k_reduce_small); rows per lane: 8, or 4 for the tiniest windows
-        static const bool small_on = !(getenv("ICICLE_HIP_MSM_REDUCE_SMALL") && atoi(getenv("ICICLE_HIP_MSM_REDUCE_SMALL")) == 0);
-        // Four lanes per bucket column while the reduction is a latency chain (single MSM, uniform plan, one device): the window kernel
-        // whenever a window has at most 64 chunks, the wave kernel when its shorter additions beat the one-lane kernel's 3.5 x fewer
-        // lanes -- up to ~2^18 terms; beyond, the reduction is work and the one-lane kernel wins (2^20: 0.56 against 0.43 ms).
-        // ICICLE_HIP_MSM_REDUCE_QUAD=0: off (A/B).
-        static const bool quad_on = !(getenv("ICICLE_HIP_MSM_REDUCE_QUAD") && atoi(getenv("ICICLE_HIP_MSM_REDUCE_QUAD")) == 0);
-        bool quad_done = false, quad_window = false;
-        // (G1, and the G2 whose point fits the registers four lanes deep: BN254's -- BLS12-381's 28-limb Fq2 elements do not)
-        constexpr bool QUAD_OK = C::EXT_DEGREE == 1 || sizeof(typename E::XYZZ) <= 288;
-        if constexpr (QUAD_OK) {
-          const bool small_path = small_on && direct && nlo_w == 0 && nb >= 16 && nb <= 512 && nw >= 64;
-          if (quad_on && !hook && NG == 1 && bb == 1 && pl.n_lo == 0 && seg_lo == 0 && nsegr == nseg && nb >= 16 && !small_path) {
-            quad_window = nseg <= 64 && !direct;
-            if (nb <= 65536) {
-              // chunks per window so that the waves fill the SIMDs once (a wave past 1024 doubles the time of its SIMD), rows to match
-              uint32_t nsq = std::min<uint32_t>(std::min<uint32_t>(64, std::max<uint32_t>(1, 1024 / (uint32_t)nw)), nb / 16);
-              const uint32_t mq = (nb + 16 * nsq - 1) / (16 * nsq);
-              nsq = (nb + 16 * mq - 1) / (16 * mq);
-              // additions on the chain x instructions per addition (in hundreds) x rounds of waves on the 1024 SIMDs
-              const uint64_t cost_q = (uint64_t)(2 * mq + 13) * 13 * (((uint64_t)nw * nsq + 1023) / 1024);
-              const uint64_t cost_s = (uint64_t)(2 * mrow + 19) * 29 * (((uint64_t)nw * nseg + 1023) / 1024);
-              if (cost_q < cost_s) {
-                const bool direct_q = nsq == 1;
-                k_reduce_wave_quad<C><<<(unsigned)((size_t)nw * nsq), 64, 0, sq>>>(buckets + (size_t)w0 * nb, chunkV, chunkT, direct_q ? win : nullptr, nb, mq, nsq);
-                LAUNCH_CHECK("k_reduce_wave_quad", sq);
-                if (!direct_q) {
-                  unsigned qthreads = 64;
-                  while (qthreads < 4 * nsq)
-                    qthreads <<= 1;
-                  k_reduce_window_quad<C><<<(unsigned)nw, qthreads, 0, sq>>>(chunkV, chunkT, win, nsq, 16 * mq);
-                  LAUNCH_CHECK("k_reduce_window_quad", sq);
-                }
-                quad_done = true;
-              }
-            }
-          }
-        }
-        if (quad_done) {
-        } else if (small_on && direct && nlo_w == 0 && nb >= 16 && nb <= 512 && nw >= 64) {
-          uint32_t lw_log = 2;
-          while ((nb >> lw_log) > 8 && lw_log < 5)
-            lw_log++;
-          const uint32_t per_wave = 64u >> lw_log;
-          k_reduce_small<C><<<(unsigned)(((size_t)nw + per_wave - 1) / per_wave), 64, 0, sq>>>(buckets + (size_t)w0 * nb, win, nb, lw_log, (uint32_t)nw);
-          LAUNCH_CHECK("k_reduce_small", sq);
-        } else if (nblocks) {
-          k_reduce_wave<C><<<(unsigned)nblocks, 64, 0, sq>>>(buckets + (size_t)w0 * nb, cV, cT, direct ? win : nullptr, nb, nb, mrow, seg_lo, nsegr, nlo_w, nseg_lo, mrow_lo);
-          LAUNCH_CHECK("k_reduce_wave", sq);
-        }
-        if (!direct && !quad_done && quad_window) {
-          if constexpr (QUAD_OK) {
-            unsigned qthreads = 64;
-            while (qthreads < 4 * nseg)
-              qthreads <<= 1;
-            k_reduce_window_quad<C><<<(unsigned)nw, qthreads, 0, sq>>>(cV, cT, win, nseg, 64 * mrow);
-            LAUNCH_CHECK("k_reduce_window_quad", sq);
-          }
-        } else if (!direct && !quad_done) {
-          unsigned rthreads = 64; // power of two (LDS tree), >= the chunks of a window
-          while (rthreads < std::max(nsegr, nlo_w ? nseg_lo : 0u) && rthreads < RWL)
-            rthreads <<= 1;
-          k_reduce_window<C><<<(unsigned)nw, rthreads, 0, sq>>>(cV, cT, win, nsegr, seg_lo, log_chunk, nlo_w, nseg_lo, log_chunk_lo);
-          LAUNCH_CHECK("k_reduce_window", sq);
-        }
-        if (NG > 1) { // (bb == 1) this group's windows, scaled, into its partial slots
-          const int nbw = (nw + FINAL_WINDOWS_PER_BLOCK - 1) / FINAL_WINDOWS_PER_BLOCK;
-          k_final<C><<<dim3((unsigned)nbw, 1), 64, 0, sq>>>(d_win.as<typename E::Proj>(), nullptr, wpf, ww, w0, nw, d_part.as<typename E::Proj>(), part_slot[g], 1);
-          LAUNCH_CHECK("k_final(group)", sq);
-        }
-        return ICICLE_SUCCESS;
-      };
-
-      if (NG == 1) {
-        ICICLE_TRY(sort_group(0, st));
-        KernelTimer::end(2, st);
-        ICICLE_TRY(accumulate_group(0, st));
-        KernelTimer::begin(3, st);
-        uint32_t seg_lo = 0, nsegr = nseg;
-        if (hook) {
-          bool skip = false;
-          ICICLE_TRY(hook->after_accumulate(buckets, tw, nb, nseg, m, st, &skip, &seg_lo, &nsegr));
-          if (skip) continue; // another shard of this device (or the exchange step) produces the result
-        }
-        ICICLE_TRY(reduce_group(0, st, seg_lo, nsegr));
-        // Window combine on the HOST when the result goes there anyway (every wrapper's default; the reference's phase 3 is
-        // host code too, cpu_msm.hpp:365-417): result = sum_w 2^offset(w) S_w is a chain of ~250 DEPENDENT doublings whatever
-        // the window size. On the GPU that is the latency floor of a small MSM (k_final: 0.65 ms with four lanes per window);
-        // one host core runs the same Jacobian chain (ec.hpp dbl_jac, 2M + 5S per step) in ~0.15 ms, and the 13 window sums
-        // are a 1.4 KB download that replaces the download of the result. Single MSMs only (a batch of 1024 combines runs in
-        // parallel on the GPU); device-resident results keep k_final. ICICLE_HIP_MSM_HOST_COMBINE=0: always k_final.
-        static const bool host_combine_env = !(getenv("ICICLE_HIP_MSM_HOST_COMBINE") && atoi(getenv("ICICLE_HIP_MSM_HOST_COMBINE")) == 0);
-        // (a device-resident result of a SYNCHRONOUS call takes the same route -- the call waits for the stream anyway -- and the 96 / 144
-        //  bytes go back up: 2^20 2.99 -> see profiles/r06_notes.md; an asynchronous call must not block, so it keeps k_final)
-        if (host_combine_env && (!cfg->are_results_on_device || !cfg->is_async) && batch == 1 && bb == 1 && !hook && wpf <= 64) {
-          typename E::Proj hw[64];
-          HIP_TRY(hipMemcpyAsync(hw, d_win.ptr(), (size_t)wpf * sizeof(typename E::Proj), hipMemcpyDeviceToHost, st), ICICLE_COPY_FAILED);
-          KernelTimer::end(3, st);
-          HIP_TRY(hipStreamSynchronize(st), ICICLE_SYNCHRONIZATION_FAILED);
-          typename E::Proj acc = hw[wpf - 1];
-          for (int w = wpf - 2; w >= 0; w--) { // Horner from the top window: acc = 2^width(w) * acc + S_w
-            typename E::Jac j = E::to_jac(acc);
-            for (int i = 0; i < pl.width(w); i++)
-              j = E::dbl_jac(j);
-            acc = E::add(E::from_jac(j), hw[w]);
-          }
-          if (cfg->are_results_on_device) {
-            uint32_t words[RW];
-            E::store_proj_canonical(words, acc);
-            HIP_TRY(hipMemcpyAsync(results_v, words, sizeof(words), hipMemcpyHostToDevice, st), ICICLE_COPY_FAILED);
-            HIP_TRY(hipStreamSynchronize(st), ICICLE_SYNCHRONIZATION_FAILED);
-          } else {
-            E::store_proj_canonical((uint32_t*)results_v, acc);
-          }
-          return ICICLE_SUCCESS;
-        }
-        static const bool horner_on = !(getenv("ICICLE_HIP_MSM_BATCH_HORNER") && atoi(getenv("ICICLE_HIP_MSM_BATCH_HORNER")) == 0);
-        if (horner_on && bb >= 64 && wpf >= 2) {
-          k_final_horner<C><<<(unsigned)((bb + 15) / 16), 64, 0, st>>>(d_win.as<typename E::Proj>(), d_res + (size_t)b0 * RW, wpf, ww, bb);
-          LAUNCH_CHECK("k_final_horner", st);
-        } else {
-          const int nbw = (wpf + FINAL_WINDOWS_PER_BLOCK - 1) / FINAL_WINDOWS_PER_BLOCK;
-          k_final<C><<<dim3((unsigned)nbw, (unsigned)bb), 64, 0, st>>>(d_win.as<typename E::Proj>(), d_res + (size_t)b0 * RW, wpf, ww, 0, wpf, nbw > 1 ? d_part.as<typename E::Proj>() : nullptr, 0, bb);
-          LAUNCH_CHECK("k_final", st);
-          if (nbw > 1) { // more than 16 windows: one single-wave block per 16 of them, then the sum of the partials
-            k_final_combine<C><<<(unsigned)((bb + 63) / 64), 64, 0, st>>>(d_part.as<typename E::Proj>(), d_res + (size_t)b0 * RW, nbw, bb);
-            LAUNCH_CHECK("k_final_combine", st);
-          }
-        }
-        KernelTimer::end(3, st);
+    // ---- phase 1 of a group: bucket lists (pass-A scatter, pass B, overflow plan, size-balanced order)
+    icicle_error_t sort_group(int g, hipStream_t sq)
+    {
+      const bool coresident = co_ok && g > 0;
+      const int w0 = glo[g], nw = ghi[g] - glo[g];
+      const size_t bk0 = (size_t)w0 * nb, nbk_g = (size_t)nw * nb;
+      const uint32_t p0 = (uint32_t)((size_t)w0 << sp.hb), np_g = (uint32_t)((size_t)nw << sp.hb);
+      uint32_t* cursor = ws->cursor.template as<uint32_t>();
+      uint32_t* scan_g = NG > 1 ? d_gscan.as<uint32_t>() + (size_t)g * scan_words : ws->scansum.template as<uint32_t>();
+      if (sp.lb == 0) { // single level
+        if (coresident) k_a_scatter<true, CO_TPB><<<dim3(sp.nblk, (unsigned)nw), CO_TPB, ldsA_co, sq>>>(dig, offA, sorted, n, pl.nwin, wpf, pf, sp, cap, w0);
+        else k_a_scatter<true, 1024><<<dim3(sp.nblk, (unsigned)nw), 1024, ldsA, sq>>>(dig, offA, sorted, n, pl.nwin, wpf, pf, sp, cap, w0);
+        LAUNCH_CHECK("k_a_scatter<final>", sq);
+        k_tables_from_a<<<(unsigned)((nbk_g + 255) / 256), 256, 0, sq>>>(offA, count, offs, nbk_g, nb, sp.nblk, gparts * sp.nblk, bk0);
+        LAUNCH_CHECK("k_tables_from_a", sq);
       } else {
-        // main stream: sort(0), accumulate(0), accumulate(1), ... ; sort stream: sort(1), sort(2), ... ; reduce stream:
-        // reduce(0), reduce(1), ... each behind its accumulation. The main stream finally waits for the reduce stream.
-        for (int g = 0; g < NG; g++) {
-          ev_sorted[g] = ring_event();
-          ev_acc[g] = ring_event();
-          if (!ev_sorted[g] || !ev_acc[g]) return ICICLE_ALLOCATION_FAILED;
+        uint32_t* partA = ws->partA.template as<uint32_t>();
+        uint32_t* bstart = ws->bstart.template as<uint32_t>() + p0 + (NG - 1 - g); // nparts_g + 1 entries per group, groups in window order
+        const size_t elems = (size_t)bb * n * pf * (size_t)nw + 1;
+        const uint32_t nblkB = (uint32_t)std::min<size_t>(np_g + (elems >> CHUNKB_LOG) + 2, ws->maxblkB);
+        if (coresident) k_a_scatter<false, CO_TPB><<<dim3(sp.nblk, (unsigned)nw), CO_TPB, ldsA_co, sq>>>(dig, offA, partA, n, pl.nwin, wpf, pf, sp, cap, w0);
+        else k_a_scatter<false, 1024><<<dim3(sp.nblk, (unsigned)nw), 1024, ldsA, sq>>>(dig, offA, partA, n, pl.nwin, wpf, pf, sp, cap, w0);
+        LAUNCH_CHECK("k_a_scatter", sq);
+        // partitions of at most own_g elements: k_b_owned, one block each; the others (and all of them when own_g == 0):
+        // sub-chunks. The host cannot know which kind it has, so both routes are launched; an idle one returns at once.
+        const uint32_t own_g = coresident ? 0u : own_max;
+        k_b_plan<<<1, 1024, 0, sq>>>(offA, bstart, np_g, (int)tw, sp.hb, sp.nblk, p0, own_g);
+        LAUNCH_CHECK("k_b_plan", sq);
+        if (own_g) {
+          k_b_owned<1024><<<np_g, 1024, ldsOwn, sq>>>(partA, offA, count, offs, sorted, (int)tw, pf, sp, cap, nb, p0, own_g);
+          LAUNCH_CHECK("k_b_owned", sq);
+        } else {
+          HIP_TRY(hipMemsetAsync(count + bk0, 0, nbk_g * 4, sq), ICICLE_COPY_FAILED);
         }
-        ICICLE_TRY(sort_group(0, st));
-        KernelTimer::end(2, st); // (the exposed part of the sort)
-        if (co_ok) {
-          // the co-resident sort of group 1 starts WITH the accumulation of group 0, not beside the stand-alone sort of
-          // group 0 (where it would only take bandwidth from it and delay the first accumulation)
-          hipEvent_t ev_s0 = ring_event();
-          if (!ev_s0) return ICICLE_ALLOCATION_FAILED;
-          HIP_TRY(hipEventRecord(ev_s0, st), ICICLE_SYNCHRONIZATION_FAILED);
-          HIP_TRY(hipStreamWaitEvent(s_sort, ev_s0, 0), ICICLE_SYNCHRONIZATION_FAILED);
+        k_b_count<<<nblkB, 1024, ((size_t)1 << sp.lb) * 4, sq>>>(partA, offA, bstart, count, np_g, (int)tw, sp, cap, nb, p0);
+        LAUNCH_CHECK("k_b_count", sq);
+        if (own_g) {
+          k_b_scan_part<<<np_g, 1024, 0, sq>>>(offA, count, offs, cursor, (int)tw, sp, nb, p0, own_g);
+        } else {
+          const uint32_t nch = (nb + SCAN_CHUNK - 1) / SCAN_CHUNK;
+          k_scan_sums<<<dim3(nch, (unsigned)nw), 1024, 0, sq>>>(count + bk0, scan_g, nb);
+          k_scan_apply<<<dim3(nch, (unsigned)nw), 1024, 0, sq>>>(count + bk0, scan_g, offs + bk0, cursor + bk0, nullptr, nb);
         }
-        for (int g = 1; g < NG; g++) {
-          ICICLE_TRY(sort_group(g, s_sort));
-          HIP_TRY(hipEventRecord(ev_sorted[g], s_sort), ICICLE_SYNCHRONIZATION_FAILED);
-        }
-        for (int g = 0; g < NG; g++) {
-          if (g > 0) HIP_TRY(hipStreamWaitEvent(s_acc, ev_sorted[g], 0), ICICLE_SYNCHRONIZATION_FAILED);
-          ICICLE_TRY(accumulate_group(g, s_acc));
-          HIP_TRY(hipEventRecord(ev_acc[g], s_acc), ICICLE_SYNCHRONIZATION_FAILED);
-          if (g < NG - 1) {
-            HIP_TRY(hipStreamWaitEvent(s_red, ev_acc[g], 0), ICICLE_SYNCHRONIZATION_FAILED);
-            ICICLE_TRY(reduce_group(g, s_red, 0, nseg));
-          }
-        }
-        KernelTimer::begin(3, st); // (the exposed tail: the last group's reduction + the combine)
-        ICICLE_TRY(reduce_group(NG - 1, st, 0, nseg));
-        hipEvent_t ev_tail = ring_event();
-        if (!ev_tail) return ICICLE_ALLOCATION_FAILED;
-        HIP_TRY(hipEventRecord(ev_tail, s_red), ICICLE_SYNCHRONIZATION_FAILED);
-        HIP_TRY(hipStreamWaitEvent(st, ev_tail, 0), ICICLE_SYNCHRONIZATION_FAILED);
-        k_final_combine<C><<<1, 64, 0, st>>>(d_part.as<typename E::Proj>(), d_res + (size_t)b0 * RW, part_slots, bb);
-        LAUNCH_CHECK("k_final_combine", st);
-        KernelTimer::end(3, st);
+        LAUNCH_CHECK("k_scan_buckets", sq);
+        if (coresident) k_b_scatter<CO_TPB><<<nblkB, CO_TPB, ldsB_co, sq>>>(partA, offA, bstart, cursor, sorted, np_g, (int)tw, pf, sp, cap, nb, p0);
+        else k_b_scatter<1024><<<nblkB, 1024, ldsB, sq>>>(partA, offA, bstart, cursor, sorted, np_g, (int)tw, pf, sp, cap, nb, p0);
+        LAUNCH_CHECK("k_b_scatter", sq);
       }
+      uint32_t* ovfcnt = ws->ovfcnt.template as<uint32_t>() + 4 * g;
+      if (NG == 1) HIP_TRY(hipMemsetAsync(ovfcnt, 0, MsmWorkspace<C>::OVFCNT_GROUP_BYTES, sq), ICICLE_COPY_FAILED);
+      k_plan_overflow<<<(unsigned)((nbk_g + 255) / 256), 256, 0, sq>>>(count, nbk_g, pl.seg, ovfcnt, ws->ovf.template as<OvfSeg>() + g_ovf_off[g], ws->firsts.template as<uint32_t>() + g_ovf_off[g] + g, g_ovf_cap[g], bk0);
+      LAUNCH_CHECK("k_plan_overflow", sq);
+      {
+        const unsigned szblk = (unsigned)((nbk_g + SZ_CHUNK - 1) / SZ_CHUNK);
+        const size_t sz0 = (bk0 / SZ_CHUNK + (size_t)(NG - 1 - g)) * SZ_BINS; // this group's slice of the size tables (groups in window order)
+        const uint32_t m = szblk * SZ_BINS, nch = (m + SCAN_CHUNK - 1) / SCAN_CHUNK;
+        uint32_t* sztab = ws->sztab.template as<uint32_t>() + sz0;
+        uint32_t* szoff = ws->szoff.template as<uint32_t>() + sz0;
+        k_bsize_count<<<szblk, 1024, 0, sq>>>(count, sztab, nbk_g, pl.seg, bk0, nb, (uint32_t)pl.n_lo);
+        k_scan_sums<<<dim3(nch, 1), 1024, 0, sq>>>(sztab, scan_g, m);
+        k_scan_apply<<<dim3(nch, 1), 1024, 0, sq>>>(sztab, scan_g, szoff, nullptr, nullptr, m);
+        k_bsize_scatter<<<szblk, 1024, 0, sq>>>(count, szoff, ws->perm.template as<uint32_t>() + bk0, nbk_g, pl.seg, bk0, nb, (uint32_t)pl.n_lo);
+        LAUNCH_CHECK("k_bsize_scatter", sq);
+      }
+      return ICICLE_SUCCESS;
+    }
+
+    // ---- phase 2 of a group: bucket accumulation (+ the fold of the overflow partials)
+    icicle_error_t accumulate_group(int g, hipStream_t sq)
+    {
+      const int w0 = glo[g], nw = ghi[g] - glo[g];
+      const size_t bk0 = (size_t)w0 * nb, nbk_g = (size_t)nw * nb;
+      uint32_t* ovfcnt = ws->ovfcnt.template as<uint32_t>() + 4 * g;
+      OvfSeg* ovf = ws->ovf.template as<OvfSeg>() + g_ovf_off[g];
+      Proj* ovfpart = ws->ovfpart.template as<Proj>() + g_ovf_off[g];
+      const uint32_t* firsts = ws->firsts.template as<uint32_t>() + g_ovf_off[g] + g;
+      const uint32_t ocap = g_ovf_cap[g];
+      KernelTimer::begin(0, sq);
+      // threads = the group's buckets in use (perm[] lists exactly those) + its overflow slots
+      const int nlo_g = std::max(0, std::min(pl.n_lo, w0 + nw) - w0); // (bb == 1 whenever n_lo > 0)
+      const size_t nbk_used = nbk_g - (size_t)nlo_g * (nb / 2);
+      const unsigned gridn = (unsigned)((nbk_used + ocap + 127) / 128);
+      const size_t bstride = shared ? 0 : npts_one * PW;
+      const MsmAccWaves aw = msm_acc_waves(sizeof(typename E::XYZZ) > 256, sizeof(typename E::XYZZ), E::F::N, co_ok, *kn);
+      launch_accumulate<C>(aw, gridn, sq, acc_bases, sorted, count, offs, buckets, ovfpart, ovf, ovfcnt, ws->perm.template as<uint32_t>() + bk0, ocap, nb, nbk_used, cap, pl.seg, wpf, bstride);
+      LAUNCH_CHECK("k_accumulate", sq);
+      KernelTimer::end(0, sq);
+      k_fold_overflow<C><<<std::min<uint32_t>(ocap, 4096), 64, 0, sq>>>(buckets, ovfpart, ovf, firsts, ovfcnt, ocap);
+      LAUNCH_CHECK("k_fold_overflow", sq);
+      return ICICLE_SUCCESS;
+    }
+
+    // ---- phase 3 of a group: bucket reduction of its windows on the route msm_reduce_route() chose, then (several groups) their
+    // share of the window combine
+    icicle_error_t reduce_group(int g, hipStream_t sq, uint32_t seg_lo, uint32_t nsegr)
+    {
+      const int w0 = glo[g], nw = ghi[g] - glo[g];
+      const MsmReduceRoute rt = msm_reduce_route(nb, w0, nw, pl.n_lo, geo, seg_lo, nsegr, hook != nullptr, NG, bb, QUAD_OK, RWL, *kn);
+      Proj* win = ws->win.template as<Proj>() + w0;
+      Proj* cV = chunkV + (size_t)w0 * geo.nseg;
+      Proj* cT = chunkT + (size_t)w0 * geo.nseg;
+      const Proj* bk = buckets + (size_t)w0 * nb;
+      switch (rt.chunk) {
+      case MsmChunkKernel::wave_quad: // (one group of one MSM: w0 == 0)
+        if constexpr (QUAD_OK) k_reduce_wave_quad<C><<<(unsigned)((size_t)nw * rt.nsq), 64, 0, sq>>>(bk, cV, cT, rt.direct ? win : nullptr, nb, rt.mq, rt.nsq);
+        LAUNCH_CHECK("k_reduce_wave_quad", sq);
+        break;
+      case MsmChunkKernel::small:
+        k_reduce_small<C><<<(unsigned)(((size_t)nw + rt.per_wave - 1) / rt.per_wave), 64, 0, sq>>>(bk, win, nb, rt.lw_log, (uint32_t)nw);
+        LAUNCH_CHECK("k_reduce_small", sq);
+        break;
+      case MsmChunkKernel::wave:
+        k_reduce_wave<C><<<(unsigned)rt.nblocks, 64, 0, sq>>>(bk, cV, cT, rt.direct ? win : nullptr, nb, nb, geo.mrow, seg_lo, nsegr, rt.nlo_w, rt.nseg_lo, rt.mrow_lo);
+        LAUNCH_CHECK("k_reduce_wave", sq);
+        break;
+      case MsmChunkKernel::none: break;
+      }
+      if (rt.window == MsmWindowKernel::window_quad) {
+        if constexpr (QUAD_OK) k_reduce_window_quad<C><<<(unsigned)nw, rt.wthreads, 0, sq>>>(cV, cT, win, rt.wchunks, rt.wchunk_size);
+        LAUNCH_CHECK("k_reduce_window_quad", sq);
+      } else if (rt.window == MsmWindowKernel::window) {
+        k_reduce_window<C><<<(unsigned)nw, rt.wthreads, 0, sq>>>(cV, cT, win, nsegr, seg_lo, geo.log_chunk, rt.nlo_w, rt.nseg_lo, rt.log_chunk_lo);
+        LAUNCH_CHECK("k_reduce_window", sq);
+      }
+      if (NG > 1) { // (bb == 1) this group's windows, scaled, into its partial slots
+        const int nbw = (nw + FINAL_WINDOWS_PER_BLOCK - 1) / FINAL_WINDOWS_PER_BLOCK;
+        k_final<C><<<dim3((unsigned)nbw, 1), 64, 0, sq>>>(ws->win.template as<Proj>(), nullptr, wpf, ww, w0, nw, d_part.as<Proj>(), part_slot[g], 1);
+        LAUNCH_CHECK("k_final(group)", sq);
+      }
+      return ICICLE_SUCCESS;
+    }
+
+    // Window combine on the HOST when the result goes there anyway (every wrapper's default; the reference's phase 3 is
+    // host code too, cpu_msm.hpp:365-417): result = sum_w 2^offset(w) S_w is a chain of ~250 DEPENDENT doublings whatever
+    // the window size. On the GPU that is the latency floor of a small MSM (k_final: 0.65 ms with four lanes per window);
+    // one host core runs the same Jacobian chain (ec.hpp dbl_jac, 2M + 5S per step) in ~0.15 ms, and the 13 window sums
+    // are a 1.4 KB download that replaces the download of the result. Single MSMs only (a batch of 1024 combines runs in
+    // parallel on the GPU); device-resident results keep k_final. ICICLE_HIP_MSM_HOST_COMBINE=0: always k_final.
+    // (a device-resident result of a SYNCHRONOUS call takes the same route -- the call waits for the stream anyway -- and the 96 / 144
+    //  bytes go back up: 2^20 2.99 -> see profiles/r06_notes.md; an asynchronous call must not block, so it keeps k_final)
+    icicle_error_t host_combine()
+    {
+      Proj hw[64];
+      HIP_TRY(hipMemcpyAsync(hw, ws->win.ptr(), (size_t)wpf * sizeof(Proj), hipMemcpyDeviceToHost, st), ICICLE_COPY_FAILED);
+      KernelTimer::end(3, st);
+      HIP_TRY(hipStreamSynchronize(st), ICICLE_SYNCHRONIZATION_FAILED);
+      Proj acc = hw[wpf - 1];
+      for (int w = wpf - 2; w >= 0; w--) { // Horner from the top window: acc = 2^width(w) * acc + S_w
+        typename E::Jac j = E::to_jac(acc);
+        for (int i = 0; i < pl.width(w); i++)
+          j = E::dbl_jac(j);
+        acc = E::add(E::from_jac(j), hw[w]);
+      }
+      if (cfg->are_results_on_device) {
+        uint32_t words[RW];
+        E::store_proj_canonical(words, acc);
+        HIP_TRY(hipMemcpyAsync(results_v, words, sizeof(words), hipMemcpyHostToDevice, st), ICICLE_COPY_FAILED);
+        HIP_TRY(hipStreamSynchronize(st), ICICLE_SYNCHRONIZATION_FAILED);
+      } else {
+        E::store_proj_canonical((uint32_t*)results_v, acc);
+      }
+      return ICICLE_SUCCESS;
+    }
+
+    icicle_error_t device_combine(MsmCombine how)
+    {
+      Proj* win = ws->win.template as<Proj>();
+      uint32_t* res = d_res + (size_t)b0 * RW;
+      if (how == MsmCombine::final_horner) {
+        k_final_horner<C><<<(unsigned)((bb + 15) / 16), 64, 0, st>>>(win, res, wpf, ww, bb);
+        LAUNCH_CHECK("k_final_horner", st);
+        return ICICLE_SUCCESS;
+      }
+      const int nbw = (wpf + FINAL_WINDOWS_PER_BLOCK - 1) / FINAL_WINDOWS_PER_BLOCK;
+      const bool partials = how == MsmCombine::final_then_combine; // more than 16 windows: one single-wave block per 16 of them, then the sum of the partials
+      k_final<C><<<dim3((unsigned)nbw, (unsigned)bb), 64, 0, st>>>(win, res, wpf, ww, 0, wpf, partials ? d_part.as<Proj>() : nullptr, 0, bb);
+      LAUNCH_CHECK("k_final", st);
+      if (partials) {
+        k_final_combine<C><<<(unsigned)((bb + 63) / 64), 64, 0, st>>>(d_part.as<Proj>(), res, nbw, bb);
+        LAUNCH_CHECK("k_final_combine", st);
+      }
+      return ICICLE_SUCCESS;
+    }
+
+    // One window group (NG == 1): sort, accumulate, [bucket-exchange hook,] reduce, combine -- all on the call's stream.
+    // *result_written: the host combine has stored the call's (only) result; nothing is left to download.
+    icicle_error_t run_single_group(bool* result_written)
+    {
+      ICICLE_TRY(sort_group(0, st));
+      KernelTimer::end(2, st);
+      ICICLE_TRY(accumulate_group(0, st));
+      KernelTimer::begin(3, st);
+      uint32_t seg_lo = 0, nsegr = geo.nseg;
+      if (hook) {
+        bool skip = false;
+        ICICLE_TRY(hook->after_accumulate(buckets, tw, nb, geo.nseg, geo.m, st, &skip, &seg_lo, &nsegr));
+        if (skip) return ICICLE_SUCCESS; // another shard of this device (or the exchange step) produces the result
+      }
+      ICICLE_TRY(reduce_group(0, st, seg_lo, nsegr));
+      const MsmCombine how = msm_combine_route(cfg->are_results_on_device, cfg->is_async, batch, bb, hook != nullptr, wpf, *kn);
+      if (how == MsmCombine::host) {
+        *result_written = true;
+        return host_combine();
+      }
+      ICICLE_TRY(device_combine(how));
+      KernelTimer::end(3, st);
+      return ICICLE_SUCCESS;
+    }
+
+    // Several window groups ("pipelined schedule"; bb == 1, no hook). Everything behind the digit pass is
+    // independent per window, and the phases are bound by different things: the sort by memory latency, bucket accumulation by
+    // VALU issue, the window combine by the latency of one doubling chain. A single large MSM is therefore cut into NG groups of
+    // windows, HIGHEST windows first: while group g is accumulated on the main stream, group g + 1 is sorted on a second stream and
+    // group g - 1 is reduced and scaled by its 2^(c*w) on a third, so the long doubling chains of the high windows and most of the
+    // sort leave the critical path. Main stream: sort(0), accumulate(0), accumulate(1), ... ; sort stream: sort(1), sort(2), ... ;
+    // reduce stream: reduce(0), reduce(1), ... each behind its accumulation. The main stream finally waits for the reduce stream
+    // and adds the groups' partial sums.
+    icicle_error_t run_pipelined()
+    {
+      hipEvent_t ev_sorted[MSM_MAX_GROUPS] = {nullptr}, ev_acc[MSM_MAX_GROUPS] = {nullptr};
+      for (int g = 0; g < NG; g++) {
+        ev_sorted[g] = ring_event();
+        ev_acc[g] = ring_event();
+        if (!ev_sorted[g] || !ev_acc[g]) return ICICLE_ALLOCATION_FAILED;
+      }
+      ICICLE_TRY(sort_group(0, st));
+      KernelTimer::end(2, st); // (the exposed part of the sort)
+      if (co_ok) {
+        // the co-resident sort of group 1 starts WITH the accumulation of group 0, not beside the stand-alone sort of
+        // group 0 (where it would only take bandwidth from it and delay the first accumulation)
+        hipEvent_t ev_s0 = ring_event();
+        if (!ev_s0) return ICICLE_ALLOCATION_FAILED;
+        HIP_TRY(hipEventRecord(ev_s0, st), ICICLE_SYNCHRONIZATION_FAILED);
+        HIP_TRY(hipStreamWaitEvent(s_sort, ev_s0, 0), ICICLE_SYNCHRONIZATION_FAILED);
+      }
+      for (int g = 1; g < NG; g++) {
+        ICICLE_TRY(sort_group(g, s_sort));
+        HIP_TRY(hipEventRecord(ev_sorted[g], s_sort), ICICLE_SYNCHRONIZATION_FAILED);
+      }
+      for (int g = 0; g < NG; g++) {
+        if (g > 0) HIP_TRY(hipStreamWaitEvent(st, ev_sorted[g], 0), ICICLE_SYNCHRONIZATION_FAILED);
+        ICICLE_TRY(accumulate_group(g, st));
+        HIP_TRY(hipEventRecord(ev_acc[g], st), ICICLE_SYNCHRONIZATION_FAILED);
+        if (g < NG - 1) {
+          HIP_TRY(hipStreamWaitEvent(s_red, ev_acc[g], 0), ICICLE_SYNCHRONIZATION_FAILED);
+          ICICLE_TRY(reduce_group(g, s_red, 0, geo.nseg));
+        }
+      }
+      KernelTimer::begin(3, st); // (the exposed tail: the last group's reduction + the combine)
+      ICICLE_TRY(reduce_group(NG - 1, st, 0, geo.nseg));
+      hipEvent_t ev_tail = ring_event();
+      if (!ev_tail) return ICICLE_ALLOCATION_FAILED;
+      HIP_TRY(hipEventRecord(ev_tail, s_red), ICICLE_SYNCHRONIZATION_FAILED);
+      HIP_TRY(hipStreamWaitEvent(st, ev_tail, 0), ICICLE_SYNCHRONIZATION_FAILED);
+      k_final_combine<C><<<1, 64, 0, st>>>(d_part.as<Proj>(), d_res + (size_t)b0 * RW, part_slots, bb);
+      LAUNCH_CHECK("k_final_combine", st);
+      KernelTimer::end(3, st);
+      return ICICLE_SUCCESS;
+    }
+  };
+
+  template <class C>
+  static icicle_error_t msm_run_single_planned(const void* scalars_v, const void* bases_v, int n, const icicle_msm_config_t* cfg, void* results_v, MsmBucketHook<C>* hook, int plan_override)
+  {
+    using E = EC<C>;
+    using FR = FieldOps<typename C::fr>;
+    constexpr int PW = 2 * E::N32, RW = 3 * E::N32;
+    if (!cfg || !results_v || n < 0) return ICICLE_INVALID_ARGUMENT;
+    const int batch = std::max(1, cfg->batch_size);
+    if (n > 0 && (!scalars_v || !bases_v)) return ICICLE_INVALID_POINTER;
+    ICICLE_TRY(bind_current_device());
+    const MsmKnobs& kn = msm_env_knobs();
+    hipStream_t st = (hipStream_t)cfg->stream;
+    int force_windows = hook ? -1 : plan_override; // (a bucket exchange adds bucket arrays of several calls element-wise: uniform widths)
+    if (!hook && plan_override == 0 && cfg->ext) force_windows = std::max(0, reinterpret_cast<const ConfigExt*>(cfg->ext)->get_int("hip_msm_windows", 0));
+    if (force_windows == 0 && kn.windows != 0) force_windows = kn.windows; // A/B: -1 = uniform only
+    const MsmPlan pl = make_plan(std::max(n, 1), C::fr::NBITS, *cfg, force_windows);
+    const int pf = pl.pf;
+    if ((long long)n * pf >= (1ll << 31)) return ICICLE_INVALID_ARGUMENT;
+    const bool shared = cfg->are_points_shared_in_batch || batch == 1;
+    const size_t npts_one = (size_t)n * pf;
+    const size_t npts_all = shared ? npts_one : npts_one * batch;
+
+    TempBuf d_res_tmp;
+    uint32_t* d_res = (uint32_t*)results_v;
+    if (!cfg->are_results_on_device) {
+      HIP_TRY(d_res_tmp.alloc((size_t)batch * RW * 4, st), ICICLE_ALLOCATION_FAILED);
+      d_res = d_res_tmp.as<uint32_t>();
+    }
+    if (n == 0) return msm_store_identity<C>(cfg, batch, d_res, results_v, st);
+
+    TempBuf d_sc_tmp, d_b_tmp;
+    const uint32_t *d_scalars, *d_bases;
+    ICICLE_TRY(msm_stage_input(scalars_v, cfg->are_scalars_on_device, (size_t)batch * n * FR::N32 * 4, d_sc_tmp, &d_scalars, st));
+    ICICLE_TRY(msm_stage_input(bases_v, cfg->are_points_on_device, npts_all * PW * 4, d_b_tmp, &d_bases, st));
+
+    // ---- geometry (msm_plan.h)
+    SortPlan sp;
+    if (!msm_sort_plan(n, pl.c, pf, kn, &sp)) return ICICLE_INVALID_ARGUMENT;
+    const MsmReduceGeom geo = msm_reduce_geom(batch, pl.wpf, pl.nb, ReduceWindowLanes<C>::value, kn);
+    size_t free_b = 0, total_b = 0;
+    if (hipMemGetInfo(&free_b, &total_b) != hipSuccess) free_b = ~(size_t)0; // (no figure: the fixed budget alone)
+    const int BB = msm_batch_fold(pl, sp, n, sizeof(typename E::Proj), (shared || !cfg->are_points_montgomery_form) ? 0 : npts_one * PW * 4, free_b, batch, hook != nullptr);
+    if (BB == 0) return ICICLE_INVALID_ARGUMENT;
+
+    MsmWorkspace<C> ws;
+    // bases are gathered where they lie unless they need converting (reference-Montgomery input) or realigning
+    const bool stage_bases = cfg->are_points_montgomery_form || (((uintptr_t)d_bases) & 15) != 0;
+    ICICLE_TRY(ws.alloc(pl, sp, geo, n, BB, stage_bases ? (shared ? 1 : (size_t)BB) * npts_one * PW * 4 : 0, st));
+
+    MsmLaunch<C> L;
+    L.cfg = cfg, L.hook = hook, L.kn = &kn, L.ws = &ws, L.st = st;
+    L.pl = pl, L.ww = WinWidths{pl.c, pl.n_lo, pl.negate}, L.sp = sp, L.geo = geo;
+    L.n = n, L.batch = batch, L.pf = pf, L.wpf = pl.wpf, L.nb = pl.nb;
+    L.shared = shared, L.stage_bases = stage_bases, L.npts_one = L.cap = npts_one;
+    L.d_scalars = d_scalars, L.d_bases = d_bases, L.d_res = d_res, L.results_v = results_v;
+    ICICLE_TRY(L.prepare());
+
+    for (int b0 = 0; b0 < batch; b0 += BB) {
+      ICICLE_TRY(L.begin_sequence(b0, BB));
+      bool result_written = false;
+      ICICLE_TRY(L.NG == 1 ? L.run_single_group(&result_written) : L.run_pipelined());
+      L.d_part.release(), L.d_gscan.release(); // (the leases of a sequence go back before the next one takes its own)
+      if (result_written) return ICICLE_SUCCESS;
     }
     HIP_TRY(hipGetLastError(), ICICLE_INVALID_ARGUMENT);
+    return msm_deliver_results(cfg, d_res, results_v, (size_t)batch * RW * 4, st);
+  }
 
-    if (!cfg->are_results_on_device) {
-      HIP_TRY(hipMemcpyAsync(results_v, d_res, (size_t)batch * RW * 4, hipMemcpyDeviceToHost, st), ICICLE_COPY_FAILED);
-      HIP_TRY(hipStreamSynchronize(st), ICICLE_SYNCHRONIZATION_FAILED);
-    } else if (!cfg->is_async) {
-      HIP_TRY(hipStreamSynchronize(st), ICICLE_SYNCHRONIZATION_FAILED);
+  // The auto-selected mixed-width plan (2^23 terms and up) holds ~2.15 x the buckets, counters and lists of the uniform plan -- several
+  // GB more for G2 at 2^26. A call that does not get that memory is run again on the uniform plan, which fit before round 5 (ADVICE r05).
+  template <class C>
+  static icicle_error_t msm_run_single(const void* scalars_v, const void* bases_v, int n, const icicle_msm_config_t* cfg, void* results_v, MsmBucketHook<C>* hook = nullptr)
+  {
+    // (icicle_hip_test_inject_failure(0, 9): the first attempt "runs out of memory" once -- the rehearsal of this path)
+    icicle_error_t rc = (!hook && test_failure_armed(0, 9)) ? ICICLE_ALLOCATION_FAILED : msm_run_single_planned<C>(scalars_v, bases_v, n, cfg, results_v, hook, 0);
+    if (rc == ICICLE_ALLOCATION_FAILED && !hook && cfg && make_plan(std::max(n, 1), C::fr::NBITS, *cfg, 0).n_lo > 0) {
+      multi_stats().plan_fallbacks++;
+      (void)hipGetLastError();
+      if (cfg->stream) (void)hipStreamSynchronize((hipStream_t)cfg->stream);
+      (void)icicle_hip_release_workspace();
+      rc = msm_run_single_planned<C>(scalars_v, bases_v, n, cfg, results_v, hook, -1);
     }
-    return ICICLE_SUCCESS;
+    return rc;
   }
 
 } // namespace icicle_hip

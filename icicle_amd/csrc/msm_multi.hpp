@@ -196,7 +196,7 @@ namespace icicle_hip {
     {
       const MsmPlan pl = make_plan(std::max(pf > 1 ? n : (n + G - 1) / G, 1), C::fr::NBITS, *cfg, -1);
       sub.c = pl.c;
-      // the bucket exchange needs a whole batch in one launch group of msm_run_single; decided here, from the shape
+      // the bucket exchange needs a whole batch in one launch group of msm_run_single_planned (msm_plan.h msm_batch_fold); decided here, from the shape
       // alone, so that every device takes the same branch (fallback: partial-sum exchange)
       if (exchange_buckets && (size_t)batch * pl.wpf > 60000) exchange_buckets = false;
       // Partial sums need no common window size: without a base table and without the bucket exchange every shard plans for

@@ -1,7 +1,9 @@
 // Host-side planning helpers of the MSM that carry no device code (also compiled by tests/plan_harness.cpp).
 #pragma once
 #include <algorithm>
+#include <cstddef>
 #include <cstdint>
+#include <cstdlib>
 #include "../../include/icicle_hip.h"
 
 namespace icicle_hip {
@@ -29,7 +31,7 @@ namespace icicle_hip {
     return NG;
   }
 
-  constexpr int MSM_DEFAULT_GROUPS = 1; // window groups of the pipelined schedule (msm_run_single); ICICLE_HIP_MSM_GROUPS overrides
+  constexpr int MSM_DEFAULT_GROUPS = 1; // window groups of the pipelined schedule (msm_impl.hpp msm_run_pipelined); ICICLE_HIP_MSM_GROUPS overrides
   struct MsmPlan {
     int bits;    // scalar bits considered
     int c;       // window bits (of the widest windows)
@@ -171,5 +173,268 @@ namespace icicle_hip {
     return p;
   }
 
+  // ---- constants the kernels and the launch plans below share (what each is for: at its kernels in msm_impl.hpp) ----
+  constexpr int SORT_EPT = 16;                          // tile sort: elements per thread per tile
+  constexpr uint32_t SORT_TS = 1024 * SORT_EPT;         // tile size with 1024 threads
+  constexpr uint32_t SCAN_CHUNK = 8192;                 // k_scan_*: 1024 threads x 8 consecutive elements
+  constexpr uint32_t CHUNKB_LOG = 17;                   // pass B, sub-chunk route: elements per block = 2^17
+  constexpr uint32_t PASSB_OWN_MAX_DEFAULT = 1u << 18;  // pass B, owned route: largest partition one block sorts whole
+  constexpr uint32_t SZ_BINS = 257;                     // size classes of the size-balanced bucket order
+  constexpr uint32_t SZ_CHUNK = 16384;                  // k_bsize_*: buckets per block (1024 threads x 16)
+  constexpr int FINAL_WINDOWS_PER_BLOCK = 16;           // k_final: windows per single-wave block
+  // LDS bytes of a tile sort over D destinations (msm_impl.hpp tile_lds lays them out)
+#if defined(__HIPCC__)
+  __host__ __device__
+#endif
+  static inline size_t tile_lds_bytes(uint32_t D, uint32_t TS = SORT_TS) { return ((size_t)2 * D + TS + TS / 2 + 32) * 4; }
+
+  // ---- environment overrides (A/B knobs). All of them are read ONCE per process, by msm_env_knobs(); the plan functions below
+  // take the struct as an argument so that a host test can force any knob without touching the environment. ----
+  struct MsmKnobs {
+    int windows = 0;                     // ICICLE_HIP_MSM_WINDOWS: W > 0 forces W mixed-width windows, -1 = uniform only, 0 = the cost model
+    bool hb_set = false;                 // ICICLE_HIP_MSM_HB: high key bits of the two-level sort (clamped into the sort's range)
+    int hb = 0;
+    bool mrow_set = false;               // ICICLE_HIP_MSM_MROW: cap of the bucket reduction's rows per lane
+    int mrow = 0;
+    int groups = MSM_DEFAULT_GROUPS;     // ICICLE_HIP_MSM_GROUPS: window groups of the pipelined schedule
+    bool coresident = true;              // ICICLE_HIP_MSM_CORESIDENT=0: no co-resident sort beside the accumulation
+    bool acc_waves_set = false;          // ICICLE_HIP_MSM_ACC_WAVES: waves per SIMD k_accumulate is compiled for
+    int acc_waves = 0;
+    bool reduce_balance = false;         // ICICLE_HIP_MSM_REDUCE_BALANCE=1: half the rows per lane for the narrow windows of a mixed plan
+    bool reduce_small = true;            // ICICLE_HIP_MSM_REDUCE_SMALL=0: no k_reduce_small
+    bool reduce_quad = true;             // ICICLE_HIP_MSM_REDUCE_QUAD=0: no four-lane bucket reduction
+    bool host_combine = true;            // ICICLE_HIP_MSM_HOST_COMBINE=0: the window combine always on the device
+    bool batch_horner = true;            // ICICLE_HIP_MSM_BATCH_HORNER=0: no k_final_horner
+  };
+  inline const MsmKnobs& msm_env_knobs()
+  {
+    static const MsmKnobs knobs = [] {
+      MsmKnobs k;
+      auto on_unless_0 = [](const char* name) { const char* e = getenv(name); return !(e && atoi(e) == 0); };
+      if (const char* e = getenv("ICICLE_HIP_MSM_WINDOWS")) k.windows = atoi(e);
+      if (const char* e = getenv("ICICLE_HIP_MSM_HB")) k.hb_set = true, k.hb = atoi(e);
+      if (const char* e = getenv("ICICLE_HIP_MSM_MROW")) k.mrow_set = true, k.mrow = std::max(1, atoi(e));
+      if (const char* e = getenv("ICICLE_HIP_MSM_GROUPS")) k.groups = atoi(e);
+      k.coresident = on_unless_0("ICICLE_HIP_MSM_CORESIDENT");
+      if (const char* e = getenv("ICICLE_HIP_MSM_ACC_WAVES")) k.acc_waves_set = true, k.acc_waves = atoi(e);
+      if (const char* e = getenv("ICICLE_HIP_MSM_REDUCE_BALANCE")) k.reduce_balance = atoi(e) != 0;
+      k.reduce_small = on_unless_0("ICICLE_HIP_MSM_REDUCE_SMALL");
+      k.reduce_quad = on_unless_0("ICICLE_HIP_MSM_REDUCE_QUAD");
+      k.host_combine = on_unless_0("ICICLE_HIP_MSM_HOST_COMBINE");
+      k.batch_horner = on_unless_0("ICICLE_HIP_MSM_BATCH_HORNER");
+      return k;
+    }();
+    return knobs;
+  }
+
+  // ---- two-level counting sort (msm_impl.hpp section 2+3) ----
+  struct SortPlan {
+    int hb, lb;       // high / low bucket-key bits, hb + lb = c - 1
+    int jb;           // bits for the precompute index j
+    int chunk_log;    // scalars per pass-A block = 2^chunk_log
+    int nblk;         // pass-A blocks
+  };
+  // The sort geometry of n scalars in windows of c bits with precompute factor pf. false: the shape does not fit the sort
+  // (the caller answers ICICLE_INVALID_ARGUMENT).
+  static inline bool msm_sort_plan(int n, int c, int pf, const MsmKnobs& kn, SortPlan* sp)
+  {
+    const int kb = c - 1;
+    // each tile-sorted pass ranks into <= 1024 destinations (one per thread of the block); small
+    // windows (kb <= 10) need a single level: pass A already produces the bucket lists
+    int hb = kb <= 10 ? kb : (kb + 1) / 2;
+    if (kn.hb_set) hb = kn.hb;
+    hb = std::max(kb - 11, std::min(std::min(kb, 10), hb)); // pass A: at most 2^10 partitions; pass B: up to 2^11 bins (c = 22)
+    if (hb < 0 || hb > 10 || kb - hb > 11) return false;
+    sp->hb = hb;
+    sp->lb = kb - hb;
+    sp->jb = 0;
+    while ((1 << sp->jb) < pf)
+      sp->jb++;
+    int logn = 0;
+    while (((size_t)1 << logn) < (size_t)n)
+      logn++;
+    const int max_chunk = 31 - sp->lb - sp->jb;
+    if (max_chunk < 10) return false;
+    sp->chunk_log = std::max(10, std::min(max_chunk, std::max(17, logn - 9)));
+    if (sp->chunk_log < logn - 9) return false; // would need more than 512 pass-A blocks per window
+    sp->nblk = (int)(((size_t)n + ((size_t)1 << sp->chunk_log) - 1) >> sp->chunk_log);
+    return true;
+  }
+
+  // ---- bucket reduction geometry: a wave owns a chunk of 64*mrow buckets; at most rwl chunks per window (one thread of the
+  // per-window kernel each; rwl = ReduceWindowLanes<C>::value), at least 16 rows per lane when the window is big enough to
+  // amortise the wave scans ----
+  struct MsmReduceGeom {
+    uint32_t mrow;      // rows per lane
+    uint32_t m;         // buckets per chunk = 64 * mrow ("segment" of the exchange hook)
+    uint32_t nseg;      // chunks per window
+    uint32_t log_chunk; // ceil(log2(m))
+  };
+  // Rows per lane: 16 amortise the wave scans; a single mid-size MSM has fewer reduction waves than the chip has SIMDs
+  // and is bound by the length of one wave's chain, so there the rows shrink until the waves fill the SIMDs once
+  // (2^16, c = 15: 272 waves of 16 rows -> 544 of 8, 1.78 -> 1.59 ms; at 2^20 16 rows already make 960 waves). The rule
+  // depends on the window plan only (every shard of a multi-device call derives the same geometry).
+  static inline MsmReduceGeom msm_reduce_geom(int batch, int wpf, uint32_t nb, uint32_t rwl, const MsmKnobs& kn)
+  {
+    uint32_t mrow_cap = 16;
+    if (batch == 1 && nb >= 8192) {
+      uint32_t need = (uint32_t)(((uint64_t)wpf * nb + 65535) / 65536), p2 = 2;
+      while (p2 < need)
+        p2 <<= 1;
+      mrow_cap = std::min<uint32_t>(16, p2);
+    }
+    if (kn.mrow_set) mrow_cap = (uint32_t)kn.mrow; // (A/B knob)
+    MsmReduceGeom g;
+    g.mrow = std::max<uint32_t>(1, std::max<uint32_t>(nb / (64 * rwl), std::min<uint32_t>(mrow_cap, nb / 64)));
+    g.m = 64 * g.mrow;
+    g.nseg = std::max<uint32_t>(1, nb / g.m);
+    g.log_chunk = 0;
+    while ((1u << g.log_chunk) < g.m)
+      g.log_chunk++;
+    return g;
+  }
+
+  // ---- batch folding: BB MSMs of the batch run as ONE launch sequence with BB*wpf windows
+  // (wrappers/rust/icicle-core/src/msm/tests.rs:92-254 batches; small MSMs would otherwise leave the
+  // GPU idle). BB is bounded by a memory budget -- half of `free_bytes`, at most 48 GiB -- and by the grid.y limit.
+  // per_msm_bytes: digits + bucket lists (two copies with a two-level sort) + buckets and their counters + pass-A tables +
+  // `staged_base_bytes` (the converted copy of bases that are neither shared nor canonical). proj_bytes = sizeof(Proj).
+  // Returns BB, or 0 when a bucket-exchange hook needs the whole batch in one launch group and that exceeds the grid
+  // (msm_multi_run checked the limit).
+  static inline int msm_batch_fold(const MsmPlan& pl, const SortPlan& sp, int n, size_t proj_bytes, size_t staged_base_bytes, size_t free_bytes, int batch, bool has_hook)
+  {
+    const size_t cap = (size_t)n * pl.pf;
+    const size_t per_msm_bytes = (size_t)pl.nwin * n * 4 + (sp.lb == 0 ? 1 : 2) * (size_t)pl.wpf * cap * 4 + (size_t)pl.wpf * pl.nb * (proj_bytes + 12) +
+                                 (size_t)pl.wpf * ((size_t)1 << sp.hb) * sp.nblk * 8 + staged_base_bytes;
+    const size_t budget = std::min((size_t)48 << 30, free_bytes / 2);
+    int BB = (int)std::max<size_t>(1, std::min<size_t>((size_t)batch, budget / std::max<size_t>(per_msm_bytes, 1)));
+    BB = std::min(BB, std::max(1, 60000 / pl.wpf));
+    if (has_hook && BB < batch) {
+      BB = batch;
+      if ((size_t)BB * pl.wpf > 60000) return 0;
+    }
+    return BB;
+  }
+
+  // ---- bucket reduction of one window group: THE place where its kernels are decided (msm_impl.hpp MsmLaunch::reduce_group
+  // launches what this returns). Windows [w0, w0 + nw) of a plan whose windows below n_lo are narrow (half the buckets);
+  // chunks [seg_lo, seg_lo + nsegr) of every window (the whole window unless a bucket-exchange hook left this device a slice). ----
+  enum class MsmChunkKernel { none, wave_quad, small, wave };
+  enum class MsmWindowKernel { none, window_quad, window };
+  struct MsmReduceRoute {
+    MsmChunkKernel chunk;
+    MsmWindowKernel window; // none: the chunk kernel writes the window sums itself
+    bool direct;            // ... which it does
+    uint32_t nlo_w;         // narrow windows of the group
+    // k_reduce_wave_quad: nsq chunks of 16 * mq buckets per window, four lanes per bucket column
+    uint32_t nsq, mq;
+    // k_reduce_small: 2^lw_log lanes per window, per_wave windows per wave
+    uint32_t lw_log, per_wave;
+    // k_reduce_wave: one block per chunk; the narrow windows have nseg_lo chunks of 64 * mrow_lo buckets
+    size_t nblocks;
+    uint32_t mrow_lo, nseg_lo, log_chunk_lo;
+    // window kernel: k_reduce_window_quad over wchunks chunks of wchunk_size buckets, or k_reduce_window; wthreads per block
+    uint32_t wchunks, wchunk_size, wthreads;
+    // what the quad decision compared (0 when it was not reached): additions on the chain x instructions per addition (in
+    // hundreds) x rounds of waves on the 1024 SIMDs, four-lane against one-lane
+    uint64_t cost_q, cost_s;
+  };
+  static inline MsmReduceRoute msm_reduce_route(uint32_t nb, int w0, int nw, int n_lo, const MsmReduceGeom& geo, uint32_t seg_lo, uint32_t nsegr, bool has_hook, int NG, int bb, bool quad_ok, uint32_t rwl, const MsmKnobs& kn)
+  {
+    MsmReduceRoute r{};
+    const uint32_t mrow = geo.mrow, nseg = geo.nseg;
+    // windows [w0, split) of the group are the narrow windows of a mixed-width plan (half the buckets, nseg_lo chunks), the
+    // rest wide; one launch of each kernel serves both (a uniform plan has n_lo = 0: no narrow windows). (bb == 1 whenever n_lo > 0)
+    const int split = std::min(std::max(n_lo, w0), w0 + nw);
+    r.nlo_w = (uint32_t)(split - w0);
+    // narrow windows: half the rows per lane, so that they have as many chunks as the wide ones (see k_reduce_wave)
+    // Measured and left OFF (profiles/r06_msm_reduce_balance_ab.txt, same box, BN254 2^26): tail 4.72 / 4.75 ms without, 4.90 / 4.86 ms
+    // with -- the extra 1280 waves bring 19 scan additions each, more than the evened-out SIMD load gives back. ICICLE_HIP_MSM_REDUCE_BALANCE=1: on.
+    r.mrow_lo = (kn.reduce_balance && r.nlo_w > 0 && mrow >= 2 && !has_hook) ? mrow / 2 : mrow;
+    r.nseg_lo = std::max<uint32_t>(1, (nb / 2) / (64 * r.mrow_lo));
+    r.log_chunk_lo = r.mrow_lo == mrow ? geo.log_chunk : geo.log_chunk - 1;
+    r.nblocks = (size_t)r.nlo_w * r.nseg_lo + (size_t)(nw - r.nlo_w) * nsegr;
+    const bool whole_single_chunk = (nseg == 1 && nsegr == 1 && seg_lo == 0); // the one-lane chunk kernel writes the window sums
+    auto window_quad_threads = [](uint32_t chunks) { // four lanes per chunk, a power of two
+      uint32_t t = 64;
+      while (t < 4 * chunks)
+        t <<= 1;
+      return t;
+    };
+    // whole small windows: several per wave (k_reduce_small); rows per lane: 8, or 4 for the tiniest windows
+    const bool small_path = kn.reduce_small && whole_single_chunk && r.nlo_w == 0 && nb >= 16 && nb <= 512 && nw >= 64;
+    // Four lanes per bucket column while the reduction is a latency chain (single MSM, uniform plan, one device): the window kernel
+    // whenever a window has at most 64 chunks, the wave kernel when its shorter additions beat the one-lane kernel's 3.5 x fewer
+    // lanes -- up to ~2^18 terms; beyond, the reduction is work and the one-lane kernel wins (2^20: 0.56 against 0.43 ms).
+    // ICICLE_HIP_MSM_REDUCE_QUAD=0: off (A/B). quad_ok: G1, and the G2 whose point fits the registers four lanes deep (BN254's --
+    // BLS12-381's 28-limb Fq2 elements do not).
+    bool quad_window = false;
+    if (quad_ok && kn.reduce_quad && !has_hook && NG == 1 && bb == 1 && n_lo == 0 && seg_lo == 0 && nsegr == nseg && nb >= 16 && !small_path) {
+      quad_window = nseg <= 64 && !whole_single_chunk;
+      if (nb <= 65536) {
+        // chunks per window so that the waves fill the SIMDs once (a wave past 1024 doubles the time of its SIMD), rows to match
+        uint32_t nsq = std::min<uint32_t>(std::min<uint32_t>(64, std::max<uint32_t>(1, 1024 / (uint32_t)nw)), nb / 16);
+        const uint32_t mq = (nb + 16 * nsq - 1) / (16 * nsq);
+        nsq = (nb + 16 * mq - 1) / (16 * mq);
+        r.cost_q = (uint64_t)(2 * mq + 13) * 13 * (((uint64_t)nw * nsq + 1023) / 1024);
+        r.cost_s = (uint64_t)(2 * mrow + 19) * 29 * (((uint64_t)nw * nseg + 1023) / 1024);
+        if (r.cost_q < r.cost_s) {
+          r.chunk = MsmChunkKernel::wave_quad;
+          r.nsq = nsq, r.mq = mq;
+          r.direct = nsq == 1;
+          if (!r.direct) r.window = MsmWindowKernel::window_quad, r.wchunks = nsq, r.wchunk_size = 16 * mq, r.wthreads = window_quad_threads(nsq);
+          return r;
+        }
+      }
+    }
+    r.direct = whole_single_chunk;
+    if (small_path) {
+      r.chunk = MsmChunkKernel::small;
+      r.lw_log = 2;
+      while ((nb >> r.lw_log) > 8 && r.lw_log < 5)
+        r.lw_log++;
+      r.per_wave = 64u >> r.lw_log;
+    } else if (r.nblocks) {
+      r.chunk = MsmChunkKernel::wave;
+    }
+    if (r.direct) return r;
+    if (quad_window) {
+      r.window = MsmWindowKernel::window_quad, r.wchunks = nseg, r.wchunk_size = 64 * mrow, r.wthreads = window_quad_threads(nseg);
+    } else {
+      r.window = MsmWindowKernel::window;
+      r.wthreads = 64; // power of two (LDS tree), >= the chunks of a window
+      while (r.wthreads < std::max(nsegr, r.nlo_w ? r.nseg_lo : 0u) && r.wthreads < rwl)
+        r.wthreads <<= 1;
+    }
+    return r;
+  }
+
+  // ---- window combine of a single-group launch sequence ----
+  // Host: when the result goes there anyway or the call waits for the stream anyway (msm_impl.hpp MsmLaunch::host_combine says why);
+  // single MSMs only. k_final_horner: big batches. Else k_final, one single-wave block per FINAL_WINDOWS_PER_BLOCK windows, and
+  // with more than one block per MSM k_final_combine adds their partial sums.
+  enum class MsmCombine { host, final_horner, final_only, final_then_combine };
+  static inline MsmCombine msm_combine_route(bool results_on_device, bool is_async, int batch, int bb, bool has_hook, int wpf, const MsmKnobs& kn)
+  {
+    if (kn.host_combine && (!results_on_device || !is_async) && batch == 1 && bb == 1 && !has_hook && wpf <= 64) return MsmCombine::host;
+    if (kn.batch_horner && bb >= 64 && wpf >= 2) return MsmCombine::final_horner;
+    return wpf > FINAL_WINDOWS_PER_BLOCK ? MsmCombine::final_then_combine : MsmCombine::final_only;
+  }
+
+  // ---- the k_accumulate instantiation to launch: waves per SIMD the register allocator must leave room for (3 fits BN254 G1,
+  // 157 VGPRs, without spilling; 2 fits BLS12-381 G1 -- 14-limb elements -- and BN254 G2; 1 for BLS12-381 G2), and the padded
+  // two-wave form that leaves room for the co-resident sort (9-limb G1 only: co_ok is never set for another curve class).
+  // is_g2: the XYZZ point is larger than 256 bytes; limbs: limbs of a base-field element (EC<C>::F::N). ----
+  struct MsmAccWaves {
+    int minw;
+    bool pad;
+  };
+  static inline MsmAccWaves msm_acc_waves(bool is_g2, size_t xyzz_bytes, int limbs, bool co_ok, const MsmKnobs& kn)
+  {
+    const int want = kn.acc_waves_set ? kn.acc_waves : (is_g2 ? (xyzz_bytes <= 288 ? 2 : 1) : (limbs <= 9 ? 3 : 2));
+    if (is_g2) return {(xyzz_bytes <= 288 && want >= 2) ? 2 : 1, false};
+    if (co_ok) return {2, true};
+    return {(want == 1 || want == 2 || want == 4) ? want : 3, false};
+  }
 
 } // namespace icicle_hip

@@ -407,3 +407,58 @@ extern "C" int ecntt_route_probe(int point_bytes, int logn, uint64_t tot, int in
     out[6 + i] = rt.widths[i];
   return 0;
 }
+
+// ---- MSM launch decisions (msm_plan.h), each for one shape and one set of knobs. knobs[]: hb_set, hb, mrow_set, mrow, acc_waves_set,
+// acc_waves, reduce_balance, reduce_small, reduce_quad, host_combine, batch_horner (tests/test_plan.py _knobs) ----
+static MsmKnobs probe_knobs(const int* k)
+{
+  MsmKnobs kn;
+  kn.hb_set = k[0] != 0, kn.hb = k[1], kn.mrow_set = k[2] != 0, kn.mrow = k[3], kn.acc_waves_set = k[4] != 0, kn.acc_waves = k[5];
+  kn.reduce_balance = k[6] != 0, kn.reduce_small = k[7] != 0, kn.reduce_quad = k[8] != 0, kn.host_combine = k[9] != 0, kn.batch_horner = k[10] != 0;
+  return kn;
+}
+// returns whether the shape fits the sort; out = hb, lb, jb, chunk_log, nblk
+extern "C" int msm_sort_probe(int n, int c, int pf, const int* knobs, int* out)
+{
+  SortPlan sp{};
+  if (!msm_sort_plan(n, c, pf, probe_knobs(knobs), &sp)) return 0;
+  out[0] = sp.hb, out[1] = sp.lb, out[2] = sp.jb, out[3] = sp.chunk_log, out[4] = sp.nblk;
+  return 1;
+}
+// geometry of (batch, wpf, nb, rwl), then the route of windows [w0, w0 + nw) on it; seg_lo / nsegr < 0: the whole window.
+// out = mrow, m, nseg, log_chunk | chunk kernel (0 none, 1 wave_quad, 2 small, 3 wave), window kernel (0 none, 1 window_quad,
+// 2 window), direct, nlo_w, nsq, mq, lw_log, per_wave, nblocks, mrow_lo, nseg_lo, log_chunk_lo, wchunks, wchunk_size, wthreads, cost_q, cost_s
+extern "C" int msm_reduce_probe(int batch, int wpf, uint32_t nb, uint32_t rwl, int w0, int nw, int n_lo, int seg_lo, int nsegr, int has_hook, int NG, int bb, int quad_ok,
+                                const int* knobs, int* out)
+{
+  const MsmKnobs kn = probe_knobs(knobs);
+  const MsmReduceGeom g = msm_reduce_geom(batch, wpf, nb, rwl, kn);
+  out[0] = (int)g.mrow, out[1] = (int)g.m, out[2] = (int)g.nseg, out[3] = (int)g.log_chunk;
+  const MsmReduceRoute r = msm_reduce_route(nb, w0, nw, n_lo, g, seg_lo < 0 ? 0u : (uint32_t)seg_lo, nsegr < 0 ? g.nseg : (uint32_t)nsegr, has_hook != 0, NG, bb, quad_ok != 0, rwl, kn);
+  out[4] = (int)r.chunk, out[5] = (int)r.window, out[6] = r.direct, out[7] = (int)r.nlo_w, out[8] = (int)r.nsq, out[9] = (int)r.mq, out[10] = (int)r.lw_log;
+  out[11] = (int)r.per_wave, out[12] = (int)r.nblocks, out[13] = (int)r.mrow_lo, out[14] = (int)r.nseg_lo, out[15] = (int)r.log_chunk_lo;
+  out[16] = (int)r.wchunks, out[17] = (int)r.wchunk_size, out[18] = (int)r.wthreads, out[19] = (int)r.cost_q, out[20] = (int)r.cost_s;
+  return 0;
+}
+// 0 host, 1 k_final_horner, 2 k_final, 3 k_final + k_final_combine
+extern "C" int msm_combine_probe(int results_on_device, int is_async, int batch, int bb, int has_hook, int wpf, const int* knobs)
+{
+  return (int)msm_combine_route(results_on_device != 0, is_async != 0, batch, bb, has_hook != 0, wpf, probe_knobs(knobs));
+}
+// out = MINW, PAD of the k_accumulate instantiation
+extern "C" int msm_acc_probe(int is_g2, int xyzz_bytes, int limbs, int co_ok, const int* knobs, int* out)
+{
+  const MsmAccWaves aw = msm_acc_waves(is_g2 != 0, (size_t)xyzz_bytes, limbs, co_ok != 0, probe_knobs(knobs));
+  out[0] = aw.minw, out[1] = aw.pad;
+  return 0;
+}
+// BB of msm_batch_fold for a plan made by make_plan (0: a hook's batch does not fit one launch group)
+extern "C" int msm_fold_probe(int n, int bits, int batch, int c, int proj_bytes, uint64_t staged_base_bytes, uint64_t free_bytes, int has_hook, const int* knobs)
+{
+  icicle_msm_config_t cfg{};
+  cfg.batch_size = batch, cfg.c = c;
+  const MsmPlan pl = make_plan(n, bits, cfg);
+  SortPlan sp{};
+  if (!msm_sort_plan(n, pl.c, pl.pf, probe_knobs(knobs), &sp)) return -1;
+  return msm_batch_fold(pl, sp, n, (size_t)proj_bytes, (size_t)staged_base_bytes, (size_t)free_bytes, batch, has_hook != 0);
+}
