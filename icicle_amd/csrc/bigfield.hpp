@@ -373,6 +373,7 @@ namespace icicle_hip {
     // complement), so nothing here is undefined behaviour.
     //   sadd / ssub / sneg / sadd2 (2a + b) / scneg   limb-wise, no carry: limb ranges add up
     //   snormalise                                    one signed carry pass: limbs 0..N-2 back in [0, 2^29), signed top limb
+    //   smul_small<K>                                 K a for a small constant K with the carry pass folded in: normalised
     //   smul / ssqr / smul_add / *_inplace            Montgomery products of signed operands: (a b + m p) / R with 0 <= m < R, so a
     //                                                 result lies in (a b / R, a b / R + p) and comes out normalised (signed top)
     //   to_unsigned<K>                                a + K p, carry-normalised: back to the operations above (cold paths)
@@ -585,6 +586,34 @@ namespace icicle_hip {
       }
       BF_ASSERT(x.tlo + clo >= -I32_LIM && x.thi + chi <= I32_LIM, "snormalise: top limb + carry can leave int32");
       sset(r, normalised(x.lo, x.hi));
+#endif
+      return r;
+    }
+    // K a for a small integer constant K (3 b of a curve whose b is small, 3 X1 X2), normalised. K times a limb need not fit an
+    // int32 (9 * 2^29 does not), so the product and the carry pass are one 64-bit multiply-add per limb: any int32 limb goes in.
+    template <int K>
+    static HD fe smul_small(const fe& a)
+    {
+      static_assert(K != 0 && K >= -64 && K <= 64, "a small constant");
+      fe r;
+      int64_t c = 0;
+#pragma unroll
+      for (int i = 0; i < N - 1; i++) {
+        const int64_t t = (int64_t)(int32_t)a.l[i] * K + c;
+        r.l[i] = (uint32_t)t & MASK;
+        c = t >> RB; // arithmetic
+      }
+      r.l[N - 1] = (uint32_t)((int64_t)(int32_t)a.l[N - 1] * K + c);
+#ifdef BIGFIELD_BOUNDS
+      const SB x = sview(a);
+      const double k = (double)K;
+      double clo = 0, chi = 0; // (|K| * 2^31 + carry is far inside an int64 and exact in a double)
+      for (int i = 0; i < N - 1; i++) {
+        clo = __builtin_floor(((K > 0 ? x.llo : x.lhi) * k + clo) / (double)(1u << RB));
+        chi = __builtin_floor(((K > 0 ? x.lhi : x.llo) * k + chi) / (double)(1u << RB));
+      }
+      BF_ASSERT((K > 0 ? x.tlo : x.thi) * k + clo >= -I32_LIM && (K > 0 ? x.thi : x.tlo) * k + chi <= I32_LIM, "smul_small: top limb can leave int32");
+      sset(r, normalised(K > 0 ? k * x.lo : k * x.hi, K > 0 ? k * x.hi : k * x.lo));
 #endif
       return r;
     }

@@ -20,7 +20,9 @@
 //   affine (plain words) x <= 1.2, y <= 2.2         XYZZ  X <= 8, Y <= 4, ZZ,ZZZ <= 2
 //   projective           X,Y,Z <= 4
 // G1 over a 9-limb field (bn254, grumpkin) runs the hot loop on bigfield.hpp's SIGNED layer instead (madd_signed): limb-wise
-// subtraction and negation, no K*p; its accumulator is two-sided, X in [-4, 6], Y in [-1, 4], ZZ, ZZZ in [-0.25, 2].
+// subtraction and negation, no K*p; its accumulator is two-sided, X in [-4, 6], Y in [-1, 4], ZZ, ZZZ in [-0.25, 2]. The one-lane
+// bucket reduction of these curves runs the complete addition on that layer as well (add_signed: operands in [-1.5, 4], results in
+// (-1.5, 1.75), normalised); what it stores is unsigned again, below 4.
 //
 // The same code serves G1 (coordinates in Fq, FieldOps) and G2 (coordinates in Fq2, fq2.hpp):
 // C::EXT_DEGREE selects the field-ops class, everything below only uses their common interface.
@@ -320,6 +322,73 @@ namespace icicle_hip {
       r.x = F::template sub<2>(F::mul(t3, t1m), F::mul(t4, y3));
       r.y = F::add(F::mul(t1m, z3), F::mul(y3, t0_3));
       r.z = F::add(F::mul(z3, t4), F::mul(t0_3, t3));
+      return r;
+    }
+    // The same complete addition (Algorithm 7, a = 0; no branch, no zero test) on the signed layer, for the bucket reduction of the
+    // curves with SIGNED_MADD: 12 products and 9 reductions instead of 14 and 14 -- the six single products t0, t1, t2 and the three
+    // Karatsuba products, X3, Y3 and Z3 one smul_add each, 3 b (bn254: 9) and 3 t0 by smul_small -- and every linear step one
+    // instruction per limb. A curve without B3_SMALL (grumpkin) multiplies by b3(): 14 products, 11 reductions.
+    // Operand contract (units of p), asserted and re-imposed on the tracker at the top of every addition: all six coordinates
+    // NORMALISED (limbs 0..N-2 in [0, 2^29), signed top limb) with a value in [ADD_LO, ADD_IN_HI] = [-1.5, 4]. That takes a bucket or
+    // a chunk sum as it lies in memory (unsigned, below 4 p) and a "loop value", which is what comes out: normalised, in
+    // (ADD_LO, ADD_HI) = (-1.5, 1.75), asserted at the end, so that one step proves the fixed point for any mix of the two kinds.
+    // With R / p >= 128 (a product of |a| <= A p, |b| <= B p lies in (-A B / 128, A B / 128 + 1) p) the tracker walks through:
+    //   t0, t1, t2 in (-0.05, 1.13)   sums of two coordinates: limbs in [0, 2^30), those of p carry-normalised before the product
+    //   (9 products of 2^30 x 2^30 and the reduction's 9 do not fit a column)   m3, m4, m5 in (-0.19, 1.5)
+    //   t3, t4 = m - t - t' in (-2.5, 1.6), carry-normalised (X3's and Z3's columns)   t5 likewise, normalised by the step 9 t5
+    //   3 t0 in (-0.15, 3.4), normalised by its step (Y3's column)   9 t2 in (-0.45, 10.2)   z3 = t1 + 9 t2 in (-0.5, 11.3): limbs in
+    //   [0, 2^30), which the columns of Y3 and Z3 still take beside three normalised operands
+    //   t1m = t1 - 9 t2 in (-10.2, 1.6): limbs in (-2^29, 2^29)   y3 = 9 t5 in (-22.5, 14.4)
+    //   X3 in (-0.6, 1.5)   Y3 in (-1.5, 1.5)   Z3 in (-0.3, 1.2)
+    // The widest column is that of Y3 = t1m z3 + y3 (3 t0): 9 products below 2^59, 9 below 2^58 and the reduction's 9, below 2^63.
+    // A store goes through to_unsigned<2> (below 3.75 p: the format in memory does not change).
+    static constexpr double ADD_LO = -1.5, ADD_HI = 1.75, ADD_IN_HI = 4.0;
+    static HD Proj add_signed(const Proj& p_, const Proj& q_)
+    {
+      static_assert(SIGNED_MADD, "add_signed: G1 over a 9-limb field");
+      Proj p = p_, q = q_;
+      F::sassume_normalised(p.x, ADD_LO, ADD_IN_HI);
+      F::sassume_normalised(p.y, ADD_LO, ADD_IN_HI);
+      F::sassume_normalised(p.z, ADD_LO, ADD_IN_HI);
+      F::sassume_normalised(q.x, ADD_LO, ADD_IN_HI);
+      F::sassume_normalised(q.y, ADD_LO, ADD_IN_HI);
+      F::sassume_normalised(q.z, ADD_LO, ADD_IN_HI);
+      const fe t0 = F::smul(p.x, q.x);
+      const fe t1 = F::smul(p.y, q.y);
+      const fe t2 = F::smul(p.z, q.z);
+      const fe m3 = F::smul(F::snormalise(F::sadd(p.x, p.y)), F::sadd(q.x, q.y));
+      const fe m4 = F::smul(F::snormalise(F::sadd(p.y, p.z)), F::sadd(q.y, q.z));
+      const fe m5 = F::smul(F::snormalise(F::sadd(p.x, p.z)), F::sadd(q.x, q.z));
+      const fe t3 = F::snormalise(F::ssub(m3, F::sadd(t0, t1))); // X1Y2 + X2Y1
+      const fe t4 = F::snormalise(F::ssub(m4, F::sadd(t1, t2))); // Y1Z2 + Y2Z1
+      const fe t5 = F::ssub(m5, F::sadd(t0, t2));                // X1Z2 + X2Z1
+      const fe t0_3 = F::template smul_small<3>(t0);             // 3 X1X2
+      fe bt2, y3;
+      if constexpr (C::B3_SMALL != 0) {
+        bt2 = F::template smul_small<(int)C::B3_SMALL>(t2);
+        y3 = F::template smul_small<(int)C::B3_SMALL>(t5);
+      } else {
+        bt2 = F::smul(b3(), t2);
+        y3 = F::smul(b3(), t5);
+      }
+      const fe z3 = F::sadd(t1, bt2);
+      const fe t1m = F::ssub(t1, bt2);
+      Proj r;
+      r.x = F::smul_add(t3, t1m, F::sneg(t4), y3);
+      r.y = F::smul_add(t1m, z3, y3, t0_3);
+      r.z = F::smul_add(z3, t4, t0_3, t3);
+      F::sassume_normalised(r.x, ADD_LO, ADD_HI);
+      F::sassume_normalised(r.y, ADD_LO, ADD_HI);
+      F::sassume_normalised(r.z, ADD_LO, ADD_HI);
+      return r;
+    }
+    // a value of add_signed() as the unsigned operations and every reader in memory take it
+    static HD Proj signed_to_unsigned(const Proj& p)
+    {
+      Proj r;
+      r.x = F::template to_unsigned<2>(p.x);
+      r.y = F::template to_unsigned<2>(p.y);
+      r.z = F::template to_unsigned<2>(p.z);
       return r;
     }
     // Renes-Costello-Batina 2016, Algorithm 9 (a = 0), the reference's dbl (projective.h:73-99):

@@ -17,7 +17,8 @@
 //      integer-ALU bound (v_mad_u64_u32), see DESIGN.md. Buckets longer than `seg` points are
 //      split (k_plan_overflow) and their partial sums folded back in parallel (k_fold_overflow).
 //   5. bucket reduction: k_reduce_wave (wave64 suffix scans over 64*m-bucket chunks) -> k_reduce_window (256
-//      lanes per window) -> k_final (4 lanes per window, Horner over windows).
+//      lanes per window) -> k_final (4 lanes per window, Horner over windows). The additions of the first two run on signed
+//      limbs for bn254 and grumpkin (ec.hpp add_signed).
 // A batch of MSMs is folded into the window dimension: all of the above is launched once for up
 // to BB MSMs x wpf windows.
 //
@@ -1016,30 +1017,48 @@ namespace icicle_hip {
       dst[i] = __shfl_down(src[i], d);
     return r;
   }
+  // The additions of k_reduce_wave and k_reduce_window. SGN (the curves with EC::SIGNED_MADD, MsmKnobs::reduce_signed): ec.hpp's
+  // add_signed -- 12 products and 9 reductions on signed limbs against the 14 and 14 of EC::add, a third fewer instructions. The
+  // values of a kernel then stay signed from one addition to the next (add_signed takes its own results and what lies in memory
+  // alike); a doubling and every store go through reduce_unsigned(), so nothing in memory changes its format.
+  template <class C, bool SGN>
+  __device__ __forceinline__ typename EC<C>::Proj reduce_add(const typename EC<C>::Proj& a, const typename EC<C>::Proj& b)
+  {
+    if constexpr (SGN)
+      return EC<C>::add_signed(a, b);
+    else
+      return EC<C>::add(a, b);
+  }
+  template <class C, bool SGN>
+  __device__ __forceinline__ typename EC<C>::Proj reduce_unsigned(const typename EC<C>::Proj& a)
+  {
+    if constexpr (SGN)
+      return EC<C>::signed_to_unsigned(a);
+    else
+      return a;
+  }
   // inclusive suffix sum over the 64 lanes of a wave: lane l gets sum_{l' >= l} v_l'
-  template <class C>
+  template <class C, bool SGN = false>
   __device__ __forceinline__ typename EC<C>::Proj wave_suffix_sum(typename EC<C>::Proj v, int lane)
   {
-    using E = EC<C>;
     for (int d = 1; d < 64; d <<= 1) {
-      const typename E::Proj o = proj_shfl_down(v, d);
-      if (lane + d < 64) v = E::add(v, o);
+      const typename EC<C>::Proj o = proj_shfl_down(v, d);
+      if (lane + d < 64) v = reduce_add<C, SGN>(v, o);
     }
     return v;
   }
   // sum over the wave, valid in lane 0
-  template <class C>
+  template <class C, bool SGN = false>
   __device__ __forceinline__ typename EC<C>::Proj wave_sum(typename EC<C>::Proj v, int lane)
   {
-    using E = EC<C>;
     for (int d = 32; d >= 1; d >>= 1) {
-      const typename E::Proj o = proj_shfl_down(v, d);
-      if (lane < d) v = E::add(v, o);
+      const typename EC<C>::Proj o = proj_shfl_down(v, d);
+      if (lane < d) v = reduce_add<C, SGN>(v, o);
     }
     return v;
   }
 
-  template <class C>
+  template <class C, bool SGN>
   __global__ __launch_bounds__(64) void k_reduce_wave(const typename EC<C>::Proj* __restrict__ buckets, typename EC<C>::Proj* __restrict__ chunkV, typename EC<C>::Proj* __restrict__ chunkT, typename EC<C>::Proj* __restrict__ winsum_direct, uint32_t nb_stride, uint32_t nb_wide, uint32_t m_wide, uint32_t seg_lo, uint32_t nsegr, uint32_t nlo_w, uint32_t nseg_lo, uint32_t m_lo)
   {
     // m_wide / m_lo: rows per lane of a wide / narrow window's chunks (a chunk = 64 m buckets). Round 5 gave both kinds the same m, so
@@ -1069,21 +1088,22 @@ namespace icicle_hip {
     typename E::Proj line = E::proj_identity(), tri0 = E::proj_identity();
     for (int i = (int)m - 1; i >= 0; i--) {
       const uint32_t k = k0 + 64u * (uint32_t)i + (uint32_t)lane;
-      tri0 = E::add(tri0, line);
-      if (k < nb) line = E::add(line, b[k]);
+      tri0 = reduce_add<C, SGN>(tri0, line);
+      if (k < nb) line = reduce_add<C, SGN>(line, b[k]);
     }
-    const typename E::Proj suf = wave_suffix_sum<C>(line, lane); // lane 0: T
-    typename E::Proj x = proj_shfl_down(suf, 1);                 // exclusive suffix
+    const typename E::Proj suf = wave_suffix_sum<C, SGN>(line, lane); // lane 0: T
+    typename E::Proj x = proj_shfl_down(suf, 1);                      // exclusive suffix
     if (lane == 63) x = E::proj_identity();
+    tri0 = reduce_unsigned<C, SGN>(tri0);
     for (int q = 0; q < 6; q++)
       tri0 = E::dbl(tri0); // 64 * tri0
-    const typename E::Proj v = wave_sum<C>(E::add(x, tri0), lane);
+    const typename E::Proj v = wave_sum<C, SGN>(reduce_add<C, SGN>(x, tri0), lane);
     if (lane == 0) {
       if (winsum_direct) { // the chunk is the whole window (small windows, batches of small MSMs): S = V + T
-        winsum_direct[oi] = E::add(v, suf);
+        winsum_direct[oi] = reduce_unsigned<C, SGN>(reduce_add<C, SGN>(v, suf));
       } else {
-        chunkV[oi] = v;
-        chunkT[oi] = suf;
+        chunkV[oi] = reduce_unsigned<C, SGN>(v);
+        chunkT[oi] = reduce_unsigned<C, SGN>(suf);
       }
     }
   }
@@ -1126,7 +1146,7 @@ namespace icicle_hip {
 
   // per window: S = sum_c (V_c + T_c) + chunk * sum_c c * T_c over the nsegr <= blockDim chunks of this device's slice
   // (c = global chunk index = seg_lo + local index)
-  template <class C>
+  template <class C, bool SGN>
   __global__ __launch_bounds__(ReduceWindowLanes<C>::value) void k_reduce_window(const typename EC<C>::Proj* __restrict__ chunkV, const typename EC<C>::Proj* __restrict__ chunkT, typename EC<C>::Proj* __restrict__ winsum, uint32_t nsegr_wide, uint32_t seg_lo_wide, uint32_t log_chunk_wide, uint32_t nlo_w, uint32_t nseg_lo, uint32_t log_chunk_lo)
   {
     // (windows [0, nlo_w) of the launch: narrow windows of a mixed-width plan, nseg_lo chunks of 2^log_chunk_lo buckets from 0; chunk rows are nsegr_wide apart)
@@ -1139,17 +1159,17 @@ namespace icicle_hip {
     const int wp = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const bool have = (uint32_t)tid < nsegr;
     const typename E::Proj t = have ? chunkT[(size_t)wp * nsegr_wide + tid] : E::proj_identity();
-    typename E::Proj u = have ? E::add(chunkV[(size_t)wp * nsegr_wide + tid], t) : E::proj_identity();
+    typename E::Proj u = have ? reduce_add<C, SGN>(chunkV[(size_t)wp * nsegr_wide + tid], t) : E::proj_identity();
     // exclusive suffix sum of T over the block
-    const typename E::Proj suf = wave_suffix_sum<C>(t, lane);
+    const typename E::Proj suf = wave_suffix_sum<C, SGN>(t, lane);
     if (lane == 0) sh[wave] = suf; // wave totals
     __syncthreads();
     typename E::Proj x = proj_shfl_down(suf, 1);
     if (lane == 63) x = E::proj_identity();
     typename E::Proj ttot = E::proj_identity(); // sum of T over the whole block (needed for a slice that does not start at 0)
     for (int w = NW - 1; w >= 0; w--) {
-      if (w > wave) x = E::add(x, sh[w]);
-      ttot = E::add(ttot, sh[w]);
+      if (w > wave) x = reduce_add<C, SGN>(x, sh[w]);
+      ttot = reduce_add<C, SGN>(ttot, sh[w]);
     }
     __syncthreads();
     auto block_sum = [&](typename E::Proj v) { // valid in thread 0
@@ -1157,7 +1177,7 @@ namespace icicle_hip {
       __syncthreads();
       for (int s2 = blockDim.x / 2; s2 >= 1; s2 >>= 1) {
         if (tid < s2) {
-          v = E::add(v, sh[tid + s2]);
+          v = reduce_add<C, SGN>(v, sh[tid + s2]);
           sh[tid] = v;
         }
         __syncthreads();
@@ -1167,10 +1187,11 @@ namespace icicle_hip {
     const typename E::Proj U = block_sum(u);
     typename E::Proj X = block_sum(x);
     if (tid == 0) {
-      if (seg_lo) X = E::add(X, E::mul_small(ttot, seg_lo));
+      if (seg_lo) X = reduce_add<C, SGN>(X, E::mul_small(reduce_unsigned<C, SGN>(ttot), seg_lo));
+      X = reduce_unsigned<C, SGN>(X);
       for (uint32_t q = 0; q < log_chunk; q++)
         X = E::dbl(X);
-      winsum[wp] = E::add(U, X);
+      winsum[wp] = reduce_unsigned<C, SGN>(reduce_add<C, SGN>(U, X));
     }
   }
 
@@ -2045,7 +2066,11 @@ namespace icicle_hip {
         LAUNCH_CHECK("k_reduce_small", sq);
         break;
       case MsmChunkKernel::wave:
-        k_reduce_wave<C><<<(unsigned)rt.nblocks, 64, 0, sq>>>(bk, cV, cT, rt.direct ? win : nullptr, nb, nb, geo.mrow, seg_lo, nsegr, rt.nlo_w, rt.nseg_lo, rt.mrow_lo);
+        if (E::SIGNED_MADD && kn->reduce_signed) {
+          if constexpr (E::SIGNED_MADD) k_reduce_wave<C, true><<<(unsigned)rt.nblocks, 64, 0, sq>>>(bk, cV, cT, rt.direct ? win : nullptr, nb, nb, geo.mrow, seg_lo, nsegr, rt.nlo_w, rt.nseg_lo, rt.mrow_lo);
+        } else {
+          k_reduce_wave<C, false><<<(unsigned)rt.nblocks, 64, 0, sq>>>(bk, cV, cT, rt.direct ? win : nullptr, nb, nb, geo.mrow, seg_lo, nsegr, rt.nlo_w, rt.nseg_lo, rt.mrow_lo);
+        }
         LAUNCH_CHECK("k_reduce_wave", sq);
         break;
       case MsmChunkKernel::none: break;
@@ -2054,7 +2079,11 @@ namespace icicle_hip {
         if constexpr (QUAD_OK) k_reduce_window_quad<C><<<(unsigned)nw, rt.wthreads, 0, sq>>>(cV, cT, win, rt.wchunks, rt.wchunk_size);
         LAUNCH_CHECK("k_reduce_window_quad", sq);
       } else if (rt.window == MsmWindowKernel::window) {
-        k_reduce_window<C><<<(unsigned)nw, rt.wthreads, 0, sq>>>(cV, cT, win, nsegr, seg_lo, geo.log_chunk, rt.nlo_w, rt.nseg_lo, rt.log_chunk_lo);
+        if (E::SIGNED_MADD && kn->reduce_signed) {
+          if constexpr (E::SIGNED_MADD) k_reduce_window<C, true><<<(unsigned)nw, rt.wthreads, 0, sq>>>(cV, cT, win, nsegr, seg_lo, geo.log_chunk, rt.nlo_w, rt.nseg_lo, rt.log_chunk_lo);
+        } else {
+          k_reduce_window<C, false><<<(unsigned)nw, rt.wthreads, 0, sq>>>(cV, cT, win, nsegr, seg_lo, geo.log_chunk, rt.nlo_w, rt.nseg_lo, rt.log_chunk_lo);
+        }
         LAUNCH_CHECK("k_reduce_window", sq);
       }
       if (NG > 1) { // (bb == 1) this group's windows, scaled, into its partial slots

@@ -203,6 +203,7 @@ namespace icicle_hip {
     bool reduce_balance = false;         // ICICLE_HIP_MSM_REDUCE_BALANCE=1: half the rows per lane for the narrow windows of a mixed plan
     bool reduce_small = true;            // ICICLE_HIP_MSM_REDUCE_SMALL=0: no k_reduce_small
     bool reduce_quad = true;             // ICICLE_HIP_MSM_REDUCE_QUAD=0: no four-lane bucket reduction
+    bool reduce_signed = true;           // ICICLE_HIP_MSM_REDUCE_SIGNED=0: the one-lane bucket reduction adds with EC::add, not EC::add_signed
     bool host_combine = true;            // ICICLE_HIP_MSM_HOST_COMBINE=0: the window combine always on the device
     bool batch_horner = true;            // ICICLE_HIP_MSM_BATCH_HORNER=0: no k_final_horner
   };
@@ -220,6 +221,7 @@ namespace icicle_hip {
       if (const char* e = getenv("ICICLE_HIP_MSM_REDUCE_BALANCE")) k.reduce_balance = atoi(e) != 0;
       k.reduce_small = on_unless_0("ICICLE_HIP_MSM_REDUCE_SMALL");
       k.reduce_quad = on_unless_0("ICICLE_HIP_MSM_REDUCE_QUAD");
+      k.reduce_signed = on_unless_0("ICICLE_HIP_MSM_REDUCE_SIGNED");
       k.host_combine = on_unless_0("ICICLE_HIP_MSM_HOST_COMBINE");
       k.batch_horner = on_unless_0("ICICLE_HIP_MSM_BATCH_HORNER");
       return k;
