@@ -378,6 +378,9 @@ BLAKE_HANDLE_SYMBOLS = {"icicle_create_blake2s": ctypes.c_void_p, "icicle_create
 # the Poseidon2 factories (poseidon2_c_api.cpp:13), per field: name -> restype
 POSEIDON2_FIELDS = ["babybear", "koalabear"]
 POSEIDON2_HANDLE_SYMBOLS = {f"{f}_create_poseidon2_hasher": ctypes.c_void_p for f in POSEIDON2_FIELDS}
+# the Poseidon factories (poseidon_c_api.cpp), per scalar field: name -> restype
+POSEIDON_FIELDS = ["bn254", "bls12_381", "bls12_377", "grumpkin"]
+POSEIDON_HANDLE_SYMBOLS = {f"{f}_create_poseidon_hasher": ctypes.c_void_p for f in POSEIDON_FIELDS}
 # the two FRI functions that return a proof handle: name -> restype
 FRI_HANDLE_SYMBOLS = {f"{p}_{s}": ctypes.c_void_p for p in FRI_PREFIXES + FRI_WIDE_PREFIXES for s in ("icicle_initialize_fri_proof", "icicle_create_with_arguments_fri_proof")}
 # the sumcheck, program and symbol functions that return a handle or a pointer: name -> restype
@@ -496,7 +499,7 @@ lib.icicle_hip_test_inject_failure.argtypes = [ctypes.c_int, ctypes.c_int]
 _size_p = ctypes.POINTER(ctypes.c_size_t)
 for _n in ("icicle_create_keccak_256", "icicle_create_keccak_512", "icicle_create_sha3_256", "icicle_create_sha3_512"):
     getattr(lib, _n).argtypes = [ctypes.c_uint64]
-for _s, _r in POSEIDON2_HANDLE_SYMBOLS.items():
+for _s, _r in {**POSEIDON2_HANDLE_SYMBOLS, **POSEIDON_HANDLE_SYMBOLS}.items():
     getattr(lib, _s).restype = _r
     getattr(lib, _s).argtypes = [ctypes.c_uint, ctypes.POINTER(ctypes.c_uint32), ctypes.c_uint]
 lib.icicle_hasher_hash.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64, ctypes.POINTER(HashConfig), ctypes.c_void_p]

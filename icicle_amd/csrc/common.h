@@ -364,6 +364,19 @@ namespace icicle_hip {
   icicle_error_t poseidon2_launch_leaves(Poseidon2Hasher& h, const uint8_t* leaves, uint64_t chunk, uint64_t first, uint64_t n, uint64_t valid, const uint8_t* last,
                                          uint64_t es, uint8_t* out, hipStream_t st);
 
+  // ---- what hash.hip reads from poseidon.hip ----
+  // A Poseidon hasher over a 256-bit scalar field: the tables of the optimized schedule, derived on the host when it is made (no
+  // device needed), and their copy in device memory, uploaded and freed as a Poseidon2 hasher's is.
+  struct PoseidonHasher;
+  // field 0 = bn254, 1 = bls12_381, 2 = bls12_377, 3 = grumpkin; tag: 8 words canonical, or nullptr; nullptr for a width outside
+  // 3, 5, 9, 12, for bls12_381 at t = 3 and for a tag >= p
+  std::shared_ptr<PoseidonHasher> poseidon_make(int field, unsigned t, const uint32_t* tag);
+  // n messages of 32 * arity bytes at in + i * stride -> n digests of 32 bytes at out; in, stride and out multiples of 4
+  icicle_error_t poseidon_launch_batch(PoseidonHasher& h, const uint8_t* in, uint64_t len, uint64_t stride, uint64_t n, uint8_t* out, hipStream_t st);
+  // layer-0 chunks [first, first + n) of a tree whose leaves end inside or in front of them (ReadPadded of hash_readers.hpp)
+  icicle_error_t poseidon_launch_leaves(PoseidonHasher& h, const uint8_t* leaves, uint64_t chunk, uint64_t first, uint64_t n, uint64_t valid, const uint8_t* last,
+                                        uint64_t es, uint8_t* out, hipStream_t st);
+
   // ---- dominant-kernel timing with hipEvents on the launch stream (bench.py roofline figure) ----
   struct KernelTimer {
     static bool enabled();

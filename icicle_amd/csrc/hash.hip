@@ -1,6 +1,7 @@
 // Keccak / SHA3 / Blake2s / Blake3 batch hashing, Merkle trees and the proof-of-work search on the device. The Blake compression and
 // absorb code is blake.hpp, the four message readers hash_readers.hpp (both also compile for the host); the kernels over them are below.
 // Poseidon2 over BabyBear and KoalaBear hashes through the same hasher and tree paths; its kernels and its state are poseidon2.hip.
+// Poseidon over the 256-bit scalar fields does the same through poseidon.hip.
 // Batched openings and verification (icicle_hip_merkle_tree_get_proofs, icicle_hip_merkle_tree_verify_batch: one gather launch for all
 // openings, one hash launch per layer for all verifications) are this backend's own; their index arithmetic is merkle_batch.h.
 //
@@ -180,7 +181,7 @@ namespace icicle_hip {
   }
 
   // ---- Blake2s / Blake3 ---------------------------------------------------------------------------------------------------------
-  enum : int { HASH_KECCAK = 0, HASH_BLAKE2S = 1, HASH_BLAKE3 = 2, HASH_POSEIDON2 = 3 }; // Poseidon2: kernels and state in poseidon2.hip
+  enum : int { HASH_KECCAK = 0, HASH_BLAKE2S = 1, HASH_BLAKE3 = 2, HASH_POSEIDON2 = 3, HASH_POSEIDON = 4 }; // Poseidon2: kernels and state in poseidon2.hip, Poseidon: poseidon.hip
 
   __device__ __forceinline__ void store_digest32(uint8_t* out, bool aligned, const uint32_t (&h)[8])
   {
@@ -393,12 +394,13 @@ namespace icicle_hip {
 
   // ---- host side ----------------------------------------------------------------------------------------------------------------
   struct Hasher {
-    int kind;       // HASH_KECCAK, HASH_BLAKE2S, HASH_BLAKE3, HASH_POSEIDON2
+    int kind;       // HASH_KECCAK, HASH_BLAKE2S, HASH_BLAKE3, HASH_POSEIDON2, HASH_POSEIDON
     int rate_words; // Keccak only -- 17: 256-bit digest, 9: 512-bit digest
     int out_words;
     uint32_t suffix; // Keccak only -- 0x01 Keccak, 0x06 SHA3
     uint64_t chunk;  // default input size, 0 = none
     std::shared_ptr<Poseidon2Hasher> p2; // Poseidon2 only -- field, width, tag and constants, shared with the trees that copy this hasher
+    std::shared_ptr<PoseidonHasher> p1;  // Poseidon only -- the same; `chunk` is the only message length it hashes
     uint64_t out_bytes() const { return kind == HASH_POSEIDON2 ? 4 : kind == HASH_KECCAK ? 8ull * out_words : 32; }
     // Blake3 over more than one chunk: several launches and a buffer of chaining values; not for the fused top kernel
     bool multi_chunk(uint64_t len) const { return kind == HASH_BLAKE3 && len > BLAKE3_CHUNK; }
@@ -476,6 +478,7 @@ namespace icicle_hip {
     if (((uintptr_t)in & 15) == 0 && (stride & 15) == 0) flags |= HASH_IN_ALIGNED16;
     if (((uintptr_t)out & 7) == 0) flags |= HASH_OUT_ALIGNED8;
     if (h.kind == HASH_POSEIDON2) return poseidon2_launch_batch(*h.p2, in, len, stride, n, out, st);
+    if (h.kind == HASH_POSEIDON) return len == h.chunk ? poseidon_launch_batch(*h.p1, in, len, stride, n, out, st) : ICICLE_INVALID_ARGUMENT;
     if (h.kind != HASH_KECCAK) return launch_blake_batch(h, in, len, stride, n, a8, flags, out, st);
     if (h.rate_words == 17 && a8)
       k_keccak_batch<17, 4, true><<<grid_for(n), 256, 0, st>>>(in, len, stride, n, h.suffix, flags, out);
@@ -494,6 +497,7 @@ namespace icicle_hip {
   {
     if (n == 0) return ICICLE_SUCCESS;
     if (h.kind == HASH_POSEIDON2) return poseidon2_launch_leaves(*h.p2, leaves, chunk, first, n, valid, last, es, out, st);
+    if (h.kind == HASH_POSEIDON) return chunk == h.chunk ? poseidon_launch_leaves(*h.p1, leaves, chunk, first, n, valid, last, es, out, st) : ICICLE_INVALID_ARGUMENT;
     if (h.kind != HASH_KECCAK) return launch_blake_leaves(h, leaves, chunk, first, n, valid, last, es, out, st);
     if (h.rate_words == 17)
       k_keccak_leaves<17, 4><<<grid_for(n), 256, 0, st>>>(leaves, chunk, first, n, valid, last, es, h.suffix, out);
@@ -517,12 +521,23 @@ namespace icicle_hip {
     return new (std::nothrow) Hasher{HASH_POSEIDON2, 0, 0, 0, 4 * elems, std::move(p2)};
   }
 
+  // <field>_create_poseidon_hasher: one permutation per message, so input_size is 0 or the arity (t, or t - 1 beside a domain tag)
+  static Hasher* make_poseidon(int field, unsigned t, const uint32_t* domain_tag, unsigned input_size)
+  {
+    std::shared_ptr<PoseidonHasher> p1 = poseidon_make(field, t, domain_tag);
+    if (!p1) return nullptr;
+    const unsigned arity = domain_tag ? t - 1 : t;
+    if (input_size != 0 && input_size != arity) return nullptr;
+    return new (std::nothrow) Hasher{HASH_POSEIDON, 0, 0, 0, 32ull * arity, nullptr, std::move(p1)};
+  }
+
   static icicle_error_t hasher_hash(const Hasher* h, const uint8_t* input, uint64_t input_len, const icicle_hash_config_t* cfg, uint8_t* output)
   {
     if (!h || !cfg) return ICICLE_INVALID_POINTER;
     const uint64_t len = input_len ? input_len : h->chunk;
     if (len == 0) return ICICLE_INVALID_ARGUMENT;
     if (h->kind == HASH_POSEIDON2 && len % 4 != 0) return ICICLE_INVALID_ARGUMENT; // whole field elements
+    if (h->kind == HASH_POSEIDON && len != h->chunk) return ICICLE_INVALID_ARGUMENT; // one permutation: exactly the arity
     const uint64_t batch = cfg->batch;
     if (batch == 0) return ICICLE_SUCCESS;
     if (!input || !output) return ICICLE_INVALID_POINTER;
@@ -588,7 +603,7 @@ namespace icicle_hip {
                                  PowPlan* p)
   {
     if (!h || !cfg || (!challenge && challenge_size)) return ICICLE_INVALID_POINTER;
-    if (h->kind == HASH_POSEIDON2) return ICICLE_INVALID_ARGUMENT; // a digest of one field element is no 64-bit candidate
+    if (h->kind == HASH_POSEIDON2 || h->kind == HASH_POSEIDON) return ICICLE_INVALID_ARGUMENT; // a digest of one field element is no 64-bit candidate
     if (solution_bits < 1 || solution_bits > 60) return ICICLE_INVALID_ARGUMENT;
     p->len = (uint64_t)challenge_size + 8 + cfg->padding_size;
     if (h->kind == HASH_BLAKE3 && p->len > BLAKE3_CHUNK) return ICICLE_INVALID_ARGUMENT; // one chunk: no tree inside a lane
@@ -762,9 +777,9 @@ namespace icicle_hip {
     ICICLE_TRY(launch_batch(t.hashers[0], src.base + first * c0, c0, c0, n_full, out[0], st));
     ICICLE_TRY(launch_leaves(t.hashers[0], src.base, c0, first + n_full, count - n_full, src.valid, src.last, p.leaf_element_size,
                              out[0] + n_full * p.layers[0].out, st));
-    int fuse_from = 1; // first layer with no multi-chunk Blake3 layer and no Poseidon2 layer (k_merkle_top has no case for it) at or above it
+    int fuse_from = 1; // first layer with no multi-chunk Blake3 layer and no Poseidon2 or Poseidon layer (k_merkle_top has no case for them) at or above it
     for (int j = 1; j < upto; j++)
-      if (t.hashers[j].multi_chunk(p.layers[j].chunk) || t.hashers[j].kind == HASH_POSEIDON2) fuse_from = j + 1;
+      if (t.hashers[j].multi_chunk(p.layers[j].chunk) || t.hashers[j].kind == HASH_POSEIDON2 || t.hashers[j].kind == HASH_POSEIDON) fuse_from = j + 1;
     uint64_t n = count;
     for (int i = 1; i < upto; i++) {
       n /= p.arity(i);
@@ -1401,6 +1416,22 @@ icicle_hasher_handle_t babybear_create_poseidon2_hasher(unsigned t, const uint32
 icicle_hasher_handle_t koalabear_create_poseidon2_hasher(unsigned t, const uint32_t* domain_tag, unsigned input_size)
 {
   HASH_GUARDED((icicle_hasher_handle_t)make_poseidon2(1, t, domain_tag, input_size), nullptr)
+}
+icicle_hasher_handle_t bn254_create_poseidon_hasher(unsigned t, const uint32_t* domain_tag, unsigned input_size)
+{
+  HASH_GUARDED((icicle_hasher_handle_t)make_poseidon(0, t, domain_tag, input_size), nullptr)
+}
+icicle_hasher_handle_t bls12_381_create_poseidon_hasher(unsigned t, const uint32_t* domain_tag, unsigned input_size)
+{
+  HASH_GUARDED((icicle_hasher_handle_t)make_poseidon(1, t, domain_tag, input_size), nullptr)
+}
+icicle_hasher_handle_t bls12_377_create_poseidon_hasher(unsigned t, const uint32_t* domain_tag, unsigned input_size)
+{
+  HASH_GUARDED((icicle_hasher_handle_t)make_poseidon(2, t, domain_tag, input_size), nullptr)
+}
+icicle_hasher_handle_t grumpkin_create_poseidon_hasher(unsigned t, const uint32_t* domain_tag, unsigned input_size)
+{
+  HASH_GUARDED((icicle_hasher_handle_t)make_poseidon(3, t, domain_tag, input_size), nullptr)
 }
 
 icicle_error_t icicle_hasher_hash(icicle_hasher_handle_t h, const uint8_t* input, uint64_t input_len, const icicle_hash_config_t* config, uint8_t* output)

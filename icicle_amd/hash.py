@@ -1,11 +1,11 @@
-"""Keccak / SHA3 / Blake2s / Blake3 / Poseidon2 batch hashing on the device: mirror of wrappers/rust/icicle-core/src/hash (Hasher,
-HashConfig) over icicle_create_keccak_256 .. icicle_create_blake3, <field>_create_poseidon2_hasher / icicle_hasher_hash
-(include/icicle_hip.h)."""
+"""Keccak / SHA3 / Blake2s / Blake3 / Poseidon2 / Poseidon batch hashing on the device: mirror of wrappers/rust/icicle-core/src/hash
+(Hasher, HashConfig) over icicle_create_keccak_256 .. icicle_create_blake3, <field>_create_poseidon2_hasher,
+<field>_create_poseidon_hasher / icicle_hasher_hash (include/icicle_hip.h)."""
 import ctypes
 
 import numpy as np
 
-from ._lib import lib, check, HashConfig, POSEIDON2_FIELDS
+from ._lib import lib, check, HashConfig, POSEIDON2_FIELDS, POSEIDON_FIELDS
 from .runtime import DeviceVec
 
 
@@ -20,8 +20,8 @@ def _ptr(x):
 
 
 class Hasher:
-    """One of the four Keccak-f[1600] sponges, Blake2s-256, Blake3 or Poseidon2 over a 31-bit field; `chunk` is the default message
-    size in bytes (a Merkle layer's input size)."""
+    """One of the four Keccak-f[1600] sponges, Blake2s-256, Blake3, Poseidon2 over a 31-bit field or Poseidon over a 256-bit scalar
+    field; `chunk` is the default message size in bytes (a Merkle layer's input size)."""
 
     def __init__(self, handle, chunk):
         if not handle:
@@ -64,6 +64,27 @@ class Hasher:
         if not handle:
             raise ValueError(f"Poseidon2 has no width {t}")
         return cls(handle, 4 * (input_size or (t if domain_tag is None else t - 1)))
+
+    @classmethod
+    def poseidon(cls, field, t, domain_tag=None, input_size=0):
+        """Poseidon of width t (3, 5, 9, 12) over the scalar field of "bn254", "bls12_381" (not t = 3), "bls12_377" or "grumpkin":
+        messages and digests are canonical residues of 8 little-endian uint32 words, the digest one element. A message is exactly
+        the arity: t elements, or t - 1 beside a `domain_tag` (an int, or an array of 8 words); `input_size` is 0 or the arity."""
+        if field not in POSEIDON_FIELDS:
+            raise ValueError(f"Poseidon is built over {POSEIDON_FIELDS}, not {field!r}")
+        tag = None
+        if domain_tag is not None:
+            if isinstance(domain_tag, (int, np.integer)):
+                if not 0 <= int(domain_tag) < 1 << 256:
+                    raise ValueError("a domain tag is one field element")
+                words = [int(domain_tag) >> (32 * i) & 0xFFFFFFFF for i in range(8)]
+            else:
+                words = [int(w) for w in np.asarray(domain_tag, dtype=np.uint32).reshape(8)]
+            tag = (ctypes.c_uint32 * 8)(*words)
+        handle = getattr(lib, f"{field}_create_poseidon_hasher")(t, tag, input_size)
+        if not handle:
+            raise ValueError(f"Poseidon over {field} has no width {t} with this tag and input size")
+        return cls(handle, 32 * (t if domain_tag is None else t - 1))
 
     @property
     def output_size(self) -> int:

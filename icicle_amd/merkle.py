@@ -81,7 +81,8 @@ def _leaves(leaves, size):
 class MerkleTree:
     """layer_hashers: one Hasher per layer, leaf layer first, each created with its layer's input chunk size; the layers may mix all
     six byte hashers (Keccak / SHA3 256 and 512, Blake2s, Blake3); Poseidon2 layers (leaf elements of 4 bytes, digests of one
-    element) build, open and verify the same way"""
+    element) build, open and verify the same way, and so do Poseidon layers over the 256-bit scalar fields (leaf elements and
+    digests of 32 bytes, arity t, or t - 1 beside a domain tag)"""
 
     def __init__(self, layer_hashers, leaf_element_size, output_store_min_layer=0):
         arr = (ctypes.c_void_p * len(layer_hashers))(*[h.handle for h in layer_hashers])

@@ -360,7 +360,8 @@ ICICLE_HIP_DECLARE_TRANSPOSE(stark252, matrix_transpose)
  * sumcheck, whose transcript hashes through the same entry points, follows FRI; execute_program, which runs the same programs over
  * vectors, follows sumcheck.
  * Poseidon2 over BabyBear and KoalaBear hashes and builds trees through the same entry points (its factories follow the Blake ones).
- * Poseidon (the first), Poseidon2 over the other fields, proof serialisation (Merkle, FRI and sumcheck) and the extension_ / rns_
+ * Poseidon over the scalar fields of BN254, BLS12-381, BLS12-377 and Grumpkin does the same (its factories follow Poseidon2's).
+ * Poseidon over the other fields and in sponge mode, Poseidon2 over the other fields, proof serialisation (Merkle, FRI and sumcheck) and the extension_ / rns_
  * variants of execute_program are not built.
  * ====================================================================================== */
 typedef struct {
@@ -407,6 +408,20 @@ icicle_hasher_handle_t icicle_create_blake3(uint64_t input_chunk_size);     /* :
  * the host; they are uploaded when the hasher first hashes on a device and freed with the hasher and the trees that copied it. */
 icicle_hasher_handle_t babybear_create_poseidon2_hasher(unsigned t, const uint32_t* domain_tag, unsigned input_size);
 icicle_hasher_handle_t koalabear_create_poseidon2_hasher(unsigned t, const uint32_t* domain_tag, unsigned input_size);
+/* Poseidon (src/hash/poseidon_c_api.cpp, semantics of backend/cpu/src/hash/cpu_poseidon.cpp) of width t in {3, 5, 9, 12} over the
+ * scalar field of BN254, BLS12-381, BLS12-377 or Grumpkin: S-box x^5, 8 full rounds, 56 / 56 / 57 / 57 partial rounds, the Cauchy
+ * matrix 1 / (i + j + t), round constants from the Grain LFSR. Elements are 8 little-endian 32-bit words, canonical; the digest is
+ * one element (32 bytes: state[1]). domain_tag: NULL, or one element (8 words) that becomes state[0]; the arity is t, or t - 1
+ * beside a tag. input_size: 0 or the arity. NULL for any other width, for bls12_381 at t = 3 (the reference has no defined result
+ * there), for a tag >= p and for any other input_size. icicle_hasher_hash takes messages of exactly 32 * arity bytes and answers
+ * INVALID_ARGUMENT to any other length: the reference refuses longer messages and reads past the end of shorter ones, so shorter
+ * ones are refused here. Device operands 4-aligned. proof_of_work and proof_of_work_verify refuse these hashers
+ * (INVALID_ARGUMENT). The tables of the optimized schedule are derived when the hasher is created
+ * (icicle_amd/csrc/poseidon_params.h), on the host; they are uploaded when a hasher of that (field, t) first hashes on a device. */
+icicle_hasher_handle_t bn254_create_poseidon_hasher(unsigned t, const uint32_t* domain_tag, unsigned input_size);
+icicle_hasher_handle_t bls12_381_create_poseidon_hasher(unsigned t, const uint32_t* domain_tag, unsigned input_size);
+icicle_hasher_handle_t bls12_377_create_poseidon_hasher(unsigned t, const uint32_t* domain_tag, unsigned input_size);
+icicle_hasher_handle_t grumpkin_create_poseidon_hasher(unsigned t, const uint32_t* domain_tag, unsigned input_size);
 /* config->batch messages of input_len bytes each, back to back (input_len = 0: the hasher's default chunk size; both 0:
  * INVALID_ARGUMENT); digests of 32 / 64 bytes back to back. Any length, any pointer alignment (Poseidon2: see its factories). */
 icicle_error_t icicle_hasher_hash(icicle_hasher_handle_t h, const uint8_t* input, uint64_t input_len, const icicle_hash_config_t* config, uint8_t* output); /* :22 */

@@ -21,12 +21,17 @@ messages of one permutation at t = 16 and t = 24, device to device, beside a dev
 over the same input, in interleaved rounds; and the build of a binary tree (leaf layer: a t = 16 sponge over 8 elements, upper layers:
 t = 2 compressions) beside a Blake3 tree over the same leaves. The registers and scratch of every kernel come from the library
 (tools/kernel_regs.py).
+--poseidon times Poseidon over the scalar fields of BN254, BLS12-381, BLS12-377 and Grumpkin (profiles/poseidon_notes.md): batches of
+2^--log-batch messages of one permutation per built (field, t), device to device, as hashes/s and as Montgomery products/s beside two
+yardsticks of the same run -- the register-resident product rate behind icicle_hip_ubench_mixed_add and the plain 256-bit vector_mul;
+and the build of a tree of about 2^--p1-log-leaves leaves with tagged t = 3 (t = 5 over BLS12-381) layers.
 usage: tools/hash_merkle_bench.py [--hash keccak256 [blake2s blake3]] [--log-batch 22] [--log-leaves 22 10] [--top-max 0 256 1024] [--reps 5]
        tools/hash_merkle_bench.py --pow [--hash keccak256 blake2s blake3] [--reps 9] [--pow-bits 20 25 30] [--pow-span-log2 24 28 32]
        tools/hash_merkle_bench.py --fri [--field babybear_extension|goldilocks|goldilocks_extension|stark252|bn254|bls12_381|bls12_377]
                                         [--fri-log-n 20 24] [--reps 5]
        tools/hash_merkle_bench.py --openings [--open-log-leaves 20] [--open-counts 200 4000] [--reps 5]
-       tools/hash_merkle_bench.py --poseidon2 [--log-batch 20] [--p2-log-leaves 18] [--reps 5] [--notes profiles/poseidon2_notes.md]"""
+       tools/hash_merkle_bench.py --poseidon2 [--log-batch 20] [--p2-log-leaves 18] [--reps 5] [--notes profiles/poseidon2_notes.md]
+       tools/hash_merkle_bench.py --poseidon [--log-batch 18] [--p1-log-leaves 16] [--reps 5] [--notes <file>]"""
 import argparse
 import ctypes
 import os
@@ -261,6 +266,11 @@ def openings_bench(a):
 
 def poseidon2_kernel_rows():
     """name -> (VGPRs, SGPRs, scratch bytes per lane) of every Poseidon2 kernel in the library"""
+    return kernel_rows("k_poseidon2_")
+
+
+def kernel_rows(prefix):
+    """name -> (VGPRs, SGPRs, scratch bytes per lane) of every kernel in the library whose name begins with `prefix`"""
     import importlib.util
     import re
     import tempfile
@@ -276,7 +286,7 @@ def poseidon2_kernel_rows():
         dm = kr.demangle([r["name"] for r in rows])
         for r in rows:
             name = re.sub(r"\(.*", "", dm[r["name"]]).replace("icicle_hip::", "").replace("void ", "")
-            if name.startswith("k_poseidon2_"):
+            if name.startswith(prefix):
                 out[name] = (r.get("vgpr_count"), r.get("sgpr_count"), int(r.get("private_segment_fixed_size", 0)))
     return out
 
@@ -346,9 +356,91 @@ def poseidon2_bench(a):
                     "(`DESIGN.md` 9e).\n\n```\n" + "\n".join(lines) + "\n```\n")
 
 
+def poseidon_products(t, r_p):
+    """Montgomery products of one hash as poseidon.hpp computes it: t conversions in and one out, 7 full rounds of t (t + 3), r_p partial
+    rounds of 3 + t + (t - 1), the last round of 3 t S-box products and one column of t"""
+    return t + 1 + 7 * t * (t + 3) + r_p * (3 + 2 * t - 1) + 3 * t + t
+
+
+def poseidon_bench(a):
+    import ctypes
+
+    from icicle_amd import MerkleTreeConfig, runtime, vecops
+    from icicle_amd._lib import lib, check, POSEIDON_FIELDS
+    from icicle_amd.hash import Hasher
+    from icicle_amd.merkle import MerkleTree
+    from icicle_amd.runtime import DeviceVec
+
+    runtime.set_device(0)
+    rng = np.random.default_rng(1)
+    logb = min(a.log_batch, 18)
+    n = 1 << logb
+    med = lambda t: t[len(t) // 2]
+    lines = []
+
+    def say(line):
+        print(line, flush=True)
+        lines.append(line)
+
+    # the yardsticks of the same build and run: the integer-ALU roof as field products per second (an XYZZ mixed addition over
+    # BN254's 9-limb base field is 8 multiplications and 2 squarings, every operand in registers) and the plain 256-bit vector_mul
+    adds = ctypes.c_double(0)
+    check(lib.icicle_hip_ubench_mixed_add(0, ctypes.byref(adds)), "icicle_hip_ubench_mixed_add")
+    roof = 10 * adds.value
+    say(f"register-resident roof: {adds.value:.3e} bn254 mixed additions/s = {roof:.3e} 9-limb products/s")
+    va, vb, vo = (DeviceVec.from_host(rng.integers(0, 1 << 28, 8 * n, dtype=np.uint64).astype(np.uint32)) for _ in range(3))
+    ts = all_interleaved([lambda: vecops.vector_mul("bn254", va, vb, out=vo, size=n)], a.reps)
+    say(f"vector_mul bn254 2^{logb} elements device->device: median {med(ts[0]):.3f} ms ({ts[0][0]:.3f} .. {ts[0][-1]:.3f}), {n / med(ts[0]) * 1e3:.3e} products/s")
+    for v in (va, vb, vo):
+        v.free()
+    for field in POSEIDON_FIELDS:
+        for t in (3, 5, 9, 12):
+            if (field, t) == ("bls12_381", 3):
+                continue
+            d_in, d_out = DeviceVec.from_host(rng.integers(0, 1 << 28, 8 * t * n, dtype=np.uint64).astype(np.uint32)), DeviceVec(32 * n)
+            h = Hasher.poseidon(field, t)
+            ts = all_interleaved([lambda: h.hash(d_in, size=32 * t, batch=n, out=d_out)], a.reps)
+            rate = n / med(ts[0]) * 1e3
+            prods = poseidon_products(t, 56 if t < 9 else 57)
+            say(f"poseidon {field} t={t} batch 2^{logb} x {32 * t} B device->device: median {med(ts[0]):.3f} ms ({ts[0][0]:.3f} .. {ts[0][-1]:.3f}), "
+                f"{rate:.3e} hashes/s | {prods} products per hash, {rate * prods:.3e} products/s = {rate * prods / roof:.2f} of the roof")
+            d_in.free(), d_out.free()
+            h.close()
+    logl = a.p1_log_leaves
+    cfg = MerkleTreeConfig.default()
+    cfg.is_tree_on_device = True
+    for field in POSEIDON_FIELDS:
+        t = 3 if field != "bls12_381" else 5
+        arity = t - 1
+        layers = -(-logl // (arity.bit_length() - 1))
+        count = arity ** layers
+        d_leaves = DeviceVec.from_host(rng.integers(0, 1 << 28, 8 * count, dtype=np.uint64).astype(np.uint32))
+        hashers = [Hasher.poseidon(field, t, domain_tag=0)] * layers
+
+        def build():
+            tree = MerkleTree(hashers, 32)
+            tree.build(d_leaves, cfg=cfg)
+            tree.close()
+
+        ts = all_interleaved([build], a.reps)
+        hashes = (count - 1) // (arity - 1)
+        say(f"poseidon {field} merkle build {count} leaves x 32 B (t={t} with a tag, arity {arity}), {layers} layers, {hashes} hashes: median {med(ts[0]):.3f} ms "
+            f"({ts[0][0]:.3f} .. {ts[0][-1]:.3f}), {hashes / med(ts[0]) * 1e3:.3e} hashes/s")
+        d_leaves.free()
+    regs = kernel_rows("k_poseidon_")
+    for name in sorted(regs, key=lambda k: (k.split("<")[0], k.split("<")[1].split(",")[0], int(k.split(", ")[1].rstrip(">")))):
+        v, sg, scratch = regs[name]
+        say(f"{name}: {v} VGPRs, {sg} SGPRs, {scratch} B of scratch per lane")
+    if a.notes:
+        with open(a.notes, "w") as f:
+            f.write("```\n" + "\n".join(lines) + "\n```\n")
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--poseidon2", action="store_true")
+    ap.add_argument("--poseidon", action="store_true")
+    ap.add_argument("--p1-log-leaves", type=int, default=16)
     ap.add_argument("--p2-log-leaves", type=int, default=18)
     ap.add_argument("--notes", default=None)
     ap.add_argument("--openings", action="store_true")
@@ -375,6 +467,8 @@ def main():
         return openings_bench(a)
     if a.poseidon2:
         return poseidon2_bench(a)
+    if a.poseidon:
+        return poseidon_bench(a)
     import icicle_amd
     from icicle_amd import runtime
     from icicle_amd._lib import lib
