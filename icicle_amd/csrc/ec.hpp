@@ -501,6 +501,14 @@ namespace icicle_hip {
     // (X + Y^2)^2} -> E (D - X3). All four lanes of a quad hold the same point; lane `role` computes one product of
     // each level, the results are broadcast with quad_perm DPP moves, and the cheap linear steps run redundantly.
     // Same operands, same bounds and the same values as dbl_jac, three product latencies per step instead of seven.
+    //
+    // Contract of every *_quad function here and in ec_dbl_quad.hpp (quad_bcast reads the registers of the other three lanes):
+    //   * ALL FOUR lanes of the quad are active at the call and hold the same operands. A kernel may diverge at quad granularity
+    //     only (a trip count or an early return that is the same in the four lanes); a lane that is masked off contributes
+    //     whatever its registers hold.
+    //   * `role` is the PHYSICAL lane number mod 4 (threadIdx.x & 3 in a one-dimensional block whose size is a multiple of 4):
+    //     quad_perm addresses lanes by their position in the hardware quad, not by a number the kernel hands out.
+    //   Every lane returns the full result. tests/device_math_harness.hip (k_ec_quad) runs them under exactly this contract.
     template <int SRC>
     static __device__ __forceinline__ fe quad_bcast(const fe& v)
     {

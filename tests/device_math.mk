@@ -6,7 +6,7 @@ HIPCC ?= /opt/rocm/bin/hipcc
 ARCH  ?= gfx950
 OUT   := $(HERE)_build
 FLAGS := -std=c++17 -O3 -fPIC --offload-arch=$(ARCH) -Wno-unused-result -Wno-pass-failed -fvisibility=hidden -shared
-DEPS  := $(HERE)device_math_harness.hip $(HERE)math_cases.hpp $(addprefix $(CSRC)/,bigfield.hpp mont_asm.hpp fq2.hpp ec.hpp goldfield.hpp smallfield.hpp field_consts.h)
+DEPS  := $(HERE)device_math_harness.hip $(HERE)math_cases.hpp $(addprefix $(CSRC)/,bigfield.hpp mont_asm.hpp fq2.hpp ec.hpp ec_dbl_quad.hpp goldfield.hpp smallfield.hpp field_consts.h)
 
 all: $(OUT)/libdevice_math_asm.so $(OUT)/libdevice_math_noasm.so
 

@@ -73,6 +73,99 @@ namespace DM_NS {
       if (math_cases::ec_case<C>(op, pts + (size_t)offs[s] * 2 * N32, offs[s + 1] - offs[s], aux + offs[s], out + s * 3 * N32)) *bad = 1;
     }
 
+    // ---- quad tier: the four-lane EC operations (ec.hpp add_quad / dbl_jac_quad, ec_dbl_quad.hpp EcQuadAdd::add / dbl_quad), which no
+    // host build reaches. One SEQUENCE PER DPP QUAD: a block of 64 threads holds 16 quads, role = threadIdx.x & 3 is the physical lane
+    // number mod 4, all four lanes of a quad load the same operands and run the same chain, and EVERY lane stores its own canonical
+    // result at out[(seq * 4 + role) * 3 * N32] (lanes 1..3 feed the next operation of every real chain). The kernel diverges at
+    // quad granularity only -- sequence lengths and doubling counts differ per quad, quads past nseq return -- as the product's
+    // kernels do. One instantiation per (curve, op) the product has; nothing else is compiled.
+    //   OP 0: complete sum with EcQuadAdd::add from proj_identity(); aux & 1 negates, (0, 0) is the identity   (ec_case op 1's twin)
+    //   OP 1: the same with EC::add_quad
+    //   OP 2: 2^aux[0] * pts[0] by dbl_quad, the point given a non-trivial Z by an addition of the identity    (ec_case op 8's twin)
+    //   OP 3: to_jac, aux[0] x dbl_jac_quad, from_jac                                                          (ec_case op 5's twin)
+    //   OP 4: the Horner walk of k_final_horner, branch for branch: acc = 2^(aux[i] >> 1) * acc + (-1)^(aux[i] & 1) pts[i], i = 1 ..;
+    //         acc and every addend come out of a quad addition, so each operand carries the bound the previous op really leaves
+    //   RAW (OP 0: two points per sequence, OP 2: one point, one doubling): the operands are math_cases::RawProj limb rows
+    template <class C>
+    inline constexpr bool has_quad_add = C::EXT_DEGREE == 1 || std::is_same<C, bn254_g2>::value; // k_reduce_*_quad: G1 and BN254 G2
+    template <class C, int OP>
+    inline constexpr bool has_quad_op = OP == 0 ? has_quad_add<C> : OP == 2 ? has_small_b3<C>::value : OP == 4 ? true : !has_small_b3<C>::value;
+
+    template <class C, int OP, bool RAW>
+    __global__ __launch_bounds__(BLOCK) void k_ec_quad(int nseq, const uint32_t* pts, const int* offs, const uint32_t* aux, uint32_t* out, uint32_t* tag)
+    {
+      put_tag(tag);
+      using E = EC<C>;
+      using F = typename E::F;
+      using Proj = typename E::Proj;
+      constexpr size_t N32 = E::N32;
+      const uint32_t role = threadIdx.x & 3u;
+      const size_t s = (size_t)blockIdx.x * (BLOCK / 4) + (threadIdx.x >> 2);
+      if (s >= (size_t)nseq) return; // whole quads only
+      const int o0 = offs[s], n = offs[s + 1] - o0;
+      auto is_identity = [&](int i) { return E::words_are_zero(pts + (size_t)(o0 + i) * 2 * N32); };
+      auto point = [&](int i, bool signed_aux = true) { // pts[i] as a projective operand, negated when aux & 1 says so; (0, 0) = the identity
+        const uint32_t* w = pts + (size_t)(o0 + i) * 2 * N32;
+        typename E::Aff a;
+        a.x = F::from_canonical(w);
+        a.y = F::from_canonical(w + N32);
+        return is_identity(i) ? E::proj_identity() : E::to_proj(E::cneg(a, signed_aux && (aux[o0 + i] & 1u) != 0));
+      };
+      auto qadd = [&](const Proj& a, const Proj& b) { // the complete addition the product pairs with this op on this curve
+        if constexpr (OP == 0 || (OP != 1 && has_small_b3<C>::value))
+          return EcQuadAdd<C>::add(a, b, role);
+        else
+          return E::add_quad(a, b, role);
+      };
+      Proj r;
+      if constexpr (RAW) {
+        using RP = math_cases::RawProj<C>;
+        const uint32_t* l = pts + (size_t)o0 * RP::ROW;
+        if constexpr (OP == 0)
+          r = EcQuadAdd<C>::add(RP::load(l, 0), RP::load(l + RP::ROW, 0), role);
+        else
+          r = EcDblSmallB<C>::dbl_quad(RP::load(l, 0), role);
+      } else if constexpr (OP == 0 || OP == 1) {
+        r = E::proj_identity();
+        for (int i = 0; i < n; i++)
+          r = qadd(r, point(i));
+      } else if constexpr (OP == 2 || OP == 3) {
+        r = qadd(point(0, false), E::proj_identity()); // a non-trivial Z (aux[0] is the doubling count)
+        if (is_identity(0)) r = E::proj_identity(); // (as the one-lane twins start)
+        const uint32_t k = aux[o0];
+        if constexpr (OP == 2) {
+          for (uint32_t i = 0; i < k; i++)
+            r = EcDblSmallB<C>::dbl_quad(r, role);
+        } else {
+          typename E::Jac j = E::to_jac(r);
+          for (uint32_t i = 0; i < k; i++)
+            j = E::dbl_jac_quad(j, role);
+          r = E::from_jac(j);
+        }
+      } else {
+        r = E::proj_identity();
+        for (int i = 0; i < n; i++) {
+          const Proj sw = qadd(E::proj_identity(), point(i)); // a window sum as a quad addition leaves it
+          if (i == 0) {
+            r = sw;
+            continue;
+          }
+          const int nd = (int)(aux[o0 + i] >> 1);
+          if constexpr (has_small_b3<C>::value) {
+            for (int q = 0; q < nd; q++)
+              r = EcDblSmallB<C>::dbl_quad(r, role);
+            r = EcQuadAdd<C>::add(r, sw, role);
+          } else {
+            typename E::Jac j = E::to_jac(r);
+            for (int q = 0; q < nd; q++)
+              j = E::dbl_jac_quad(j, role);
+            r = E::add_quad(E::from_jac(j), sw, role);
+          }
+        }
+      }
+      E::store_proj_canonical(out + (s * 4 + role) * 3 * N32, r);
+    }
+
     // host side: device copies of the host arrays, freed on every path
     struct Staged {
       static constexpr int MAX = 10;
@@ -198,14 +291,16 @@ DM_EXPORT int dm_small(int field, int op, int n, const uint32_t* a, const uint32
   return finish(st, dbad);
 }
 
-// EC tier: sequence s = points offs[s] .. offs[s+1]-1 (at least one each; aux words at the same indices); out: nseq * 3 * E::N32 words
+// EC tier: sequence s = points offs[s] .. offs[s+1]-1 (at least one each; aux words at the same indices); out: nseq * 3 * E::N32 words.
+// op 7 (add_signed) only for the curves with SIGNED_MADD, op 8 (EcDblSmallB::dbl) only for those with a small 3 b: -1 otherwise
 DM_EXPORT int dm_ec(int curve, int op, int nseq, const uint32_t* pts, const int* offs, const uint32_t* aux, uint32_t* out, uint32_t* tag)
 {
-  if (nseq <= 0 || op < 0 || op > 6) return -1;
+  if (nseq <= 0 || op < 0 || op > 8) return -1;
   for (int s = 0; s < nseq; s++)
     if (offs[s + 1] <= offs[s] || offs[s] < 0) return -1;
   return math_cases::with_curve(curve, [&](auto t) {
     using C = typename decltype(t)::type;
+    if ((op == 7 && !EC<C>::SIGNED_MADD) || (op == 8 && !has_small_b3<C>::value)) return -1; // (nothing launched)
     constexpr size_t N32 = EC<C>::N32;
     const size_t npts = (size_t)offs[nseq], ocnt = (size_t)nseq * 3 * N32;
     Staged st;
@@ -221,5 +316,59 @@ DM_EXPORT int dm_ec(int curve, int op, int nseq, const uint32_t* pts, const int*
     st.back(out, dout, ocnt);
     st.back(tag, dtag, 1);
     return finish(st, dbad);
+  });
+}
+
+// quad tier (k_ec_quad): op = 0..4, | 0x100 for raw limb-row operands (ops 0 and 2 only: exactly two points / one point per sequence).
+// pts: affine canonical words as for dm_ec, or RawProj rows; out: nseq * 4 * 3 * E::N32 words, one result per lane of every quad.
+// -1 (nothing launched) for a (curve, op) pair the product does not instantiate.
+namespace DM_NS {
+  namespace {
+    template <class C, int OP, bool RAW>
+    int run_ec_quad(int nseq, const uint32_t* pts, const int* offs, const uint32_t* aux, uint32_t* out, uint32_t* tag)
+    {
+      if constexpr (!has_quad_op<C, OP>) {
+        return -1;
+      } else {
+        constexpr size_t N32 = EC<C>::N32;
+        const size_t npts = (size_t)offs[nseq], ocnt = (size_t)nseq * 4 * 3 * N32;
+        Staged st;
+        auto dp = st.in(pts, npts * (RAW ? (size_t)math_cases::RawProj<C>::ROW : 2 * N32));
+        auto doffs = st.in(offs, (size_t)nseq + 1);
+        auto daux = st.in(aux, npts);
+        auto dout = st.out<uint32_t>(ocnt), dtag = st.out<uint32_t>(1);
+        if (st.err == hipSuccess) {
+          k_ec_quad<C, OP, RAW><<<(nseq + BLOCK / 4 - 1) / (BLOCK / 4), BLOCK>>>(nseq, dp, doffs, daux, dout, dtag);
+          st.launched();
+        }
+        st.back(out, dout, ocnt);
+        st.back(tag, dtag, 1);
+        return (int)st.err;
+      }
+    }
+  } // namespace
+} // namespace DM_NS
+
+DM_EXPORT int dm_ec_quad(int curve, int op, int nseq, const uint32_t* pts, const int* offs, const uint32_t* aux, uint32_t* out, uint32_t* tag)
+{
+  const bool raw = (op & 0x100) != 0;
+  const int o = op & ~0x100;
+  if (nseq <= 0 || o < 0 || o > 4 || (raw && o != 0 && o != 2) || offs[0] != 0) return -1;
+  for (int s = 0; s < nseq; s++) {
+    const int n = offs[s + 1] - offs[s];
+    if (n <= 0 || (raw && n != (o == 0 ? 2 : 1))) return -1;
+  }
+  return math_cases::with_curve(curve, [&](auto t) {
+    using C = typename decltype(t)::type;
+    switch (op) {
+    case 0: return run_ec_quad<C, 0, false>(nseq, pts, offs, aux, out, tag);
+    case 1: return run_ec_quad<C, 1, false>(nseq, pts, offs, aux, out, tag);
+    case 2: return run_ec_quad<C, 2, false>(nseq, pts, offs, aux, out, tag);
+    case 3: return run_ec_quad<C, 3, false>(nseq, pts, offs, aux, out, tag);
+    case 4: return run_ec_quad<C, 4, false>(nseq, pts, offs, aux, out, tag);
+    case 0x100: return run_ec_quad<C, 0, true>(nseq, pts, offs, aux, out, tag);
+    case 0x102: return run_ec_quad<C, 2, true>(nseq, pts, offs, aux, out, tag);
+    }
+    return -1;
   });
 }

@@ -202,12 +202,26 @@ extern "C" int host_small_batch(int field, int op, int n, const uint32_t* a, con
 // sequence s holds the points offs[s] .. offs[s+1]-1 (and the aux words of the same indices); 3 * E::N32 words out per sequence
 extern "C" int host_ec_batch(int curve, int op, int nseq, const uint32_t* pts, const int* offs, const uint32_t* aux, uint32_t* out)
 {
-  if (op < 0 || op > 6) return -1;
+  if (op < 0 || op > 8) return -1; // (ops 7 and 8 answer -1 themselves for the curves that do not have them)
   return math_cases::with_curve(curve, [&](auto tag) {
     using C = typename decltype(tag)::type;
     constexpr size_t N32 = EC<C>::N32;
     for (int s = 0; s < nseq; s++)
       if (int e = math_cases::ec_case<C>(op, pts + (size_t)offs[s] * 2 * N32, offs[s + 1] - offs[s], aux + offs[s], out + (size_t)s * 3 * N32)) return e;
+    return 0;
+  });
+}
+
+// the one-lane twins of the device harness's quad tier on RAW projective operands (math_cases::RawProj limb rows), every component
+// with the stated bound K: fn 0 = E::add of two points per case, fn 2 = EcDblSmallB::dbl of one. The tracker aborts the process when
+// K is outside a precondition, which is how the tests learn the range the headers' contracts really cover.
+extern "C" int host_ec_raw(int curve, int fn, int K, int n, const uint32_t* limbs, uint32_t* out)
+{
+  return math_cases::with_curve(curve, [&](auto tag) {
+    using C = typename decltype(tag)::type;
+    const size_t stride = (size_t)(fn == 0 ? 2 : 1) * math_cases::RawProj<C>::ROW;
+    for (int t = 0; t < n; t++)
+      if (int e = math_cases::ec_raw_case<C>(fn, K, limbs + t * stride, out + (size_t)t * 3 * EC<C>::N32)) return e;
     return 0;
   });
 }

@@ -7,6 +7,7 @@
 #include <cstdint>
 #include <type_traits>
 #include "../icicle_amd/csrc/ec.hpp"
+#include "../icicle_amd/csrc/ec_dbl_quad.hpp"
 #include "../icicle_amd/csrc/smallfield.hpp"
 #include "../icicle_amd/csrc/goldfield.hpp"
 
@@ -226,7 +227,8 @@ namespace math_cases {
     return 0;
   }
 
-  // ---- EC tier. points: affine canonical words (x,y); identity (0,0). ops 0, 1, 2, 3, 4, 5, 6 of host_ec_op ---------------------
+  // ---- EC tier. points: affine canonical words (x,y); identity (0,0). ops 0, 1, 2, 3, 4, 5, 6 of host_ec_op; 7 (add_signed) and 8
+  // (EcDblSmallB::dbl) answer -1 for the curves that do not have them ---------------------------------------------------------------
   template <class C>
   HD int ec_case(int op, const uint32_t* pts, int n, const uint32_t* aux, uint32_t* out)
   {
@@ -305,7 +307,82 @@ namespace math_cases {
       E::store_proj_canonical(out, E::from_jac(j));
       return 0;
     }
+    case 7: { // one lane of k_reduce_wave on the signed layer (the curves with SIGNED_MADD): the buckets b_0 .. b_{n-1} as they lie in memory
+              // (unsigned normalised Proj, the identity as proj_identity()), tri = add_signed(tri, line); line = add_signed(line, b_i) from two
+              // identities; output signed_to_unsigned(add_signed(tri, line)) = sum (n - i) b_i
+      if constexpr (E::SIGNED_MADD) {
+        auto tri = E::proj_identity(), line = E::proj_identity();
+        for (int i = 0; i < n; i++) {
+          const uint32_t* w = pts + (size_t)i * 2 * N32;
+          const auto b = E::words_are_zero(w) ? E::proj_identity() : E::to_proj(E::cneg(load(w), aux && (aux[i] & 1)));
+          tri = E::add_signed(tri, line);
+          line = E::add_signed(line, b);
+        }
+        E::store_proj_canonical(out, E::signed_to_unsigned(E::add_signed(tri, line)));
+        return 0;
+      } else {
+        return -1;
+      }
+    }
+    case 8: { // op 5's chain by the complete doubling of ec_dbl_quad.hpp on one lane (the curves with a small 3 b): 2^aux[0] * pts[0]
+      if constexpr (has_small_b3<C>::value) {
+        auto p = E::words_are_zero(pts) ? E::proj_identity() : E::add(E::to_proj(load(pts)), E::proj_identity()); // a non-trivial Z
+        for (uint32_t i = 0; i < aux[0]; i++)
+          p = EcDblSmallB<C>::dbl(p);
+        E::store_proj_canonical(out, p);
+        return 0;
+      } else {
+        return -1;
+      }
+    }
     default: return -1;
     }
+  }
+
+  // ---- raw projective operands: (X, Y, Z), each coordinate F::N normalised 29-bit limbs per base-field component, taken as they are
+  // (Montgomery form, no conversion); K = the bound (units of p) stated for every component, which the host build hands to the tracker
+  template <class C>
+  struct RawProj {
+    using E = EC<C>;
+    using F = typename E::F;
+    static constexpr int ROW = 3 * (int)C::EXT_DEGREE * F::N; // limbs per point
+    template <class BFE>
+    static HD void comp(BFE& dst, const uint32_t* l, int K)
+    {
+      for (int i = 0; i < F::N; i++)
+        dst.l[i] = l[i];
+      BF_SET_BOUND(dst, (double)K);
+      (void)K;
+    }
+    static HD typename E::Proj load(const uint32_t* l, int K)
+    {
+      typename E::Proj r;
+      if constexpr (C::EXT_DEGREE == 2) {
+        comp(r.x.c0, l, K), comp(r.x.c1, l + F::N, K);
+        comp(r.y.c0, l + 2 * F::N, K), comp(r.y.c1, l + 3 * F::N, K);
+        comp(r.z.c0, l + 4 * F::N, K), comp(r.z.c1, l + 5 * F::N, K);
+      } else {
+        comp(r.x, l, K), comp(r.y, l + F::N, K), comp(r.z, l + 2 * F::N, K);
+      }
+      return r;
+    }
+  };
+  // the one-lane twins of the quad tier on raw operands (host: under the tracker). fn 0: E::add of two points, fn 2: EcDblSmallB::dbl of one
+  template <class C>
+  HD int ec_raw_case(int fn, int K, const uint32_t* limbs, uint32_t* out)
+  {
+    using E = EC<C>;
+    using RP = RawProj<C>;
+    if (fn == 0) {
+      E::store_proj_canonical(out, E::add(RP::load(limbs, K), RP::load(limbs + RP::ROW, K)));
+      return 0;
+    }
+    if (fn == 2) {
+      if constexpr (has_small_b3<C>::value) {
+        E::store_proj_canonical(out, EcDblSmallB<C>::dbl(RP::load(limbs, K)));
+        return 0;
+      }
+    }
+    return -1;
   }
 } // namespace math_cases

@@ -11,10 +11,17 @@ Which tuples an op sees:
 Fq2 has its own directed element list (canon_operands): every directed base-field value in one component against the named values in
 the other, both ways round; all pairs of base-field values are the base field's own test.
 Raw mode: the representatives a0 + j*p of directed_operands.raw_seeds; one-operand ops see every j in 0..K-1, products and sums
-see j in {0, 1, K-1} of a subset of the seeds, for every admissible combination of stated bounds."""
+see j in {0, 1, K-1} of a subset of the seeds, for every admissible combination of stated bounds.
+EC tier: sequences of affine points, one per thread (ec_plan). Quad tier (device only): the four-lane operations, one sequence per DPP quad
+(quad_plan), every lane's words, every position in the wave, the one-lane twins, raw operands up to the headers' stated bounds."""
 import ctypes
 import functools
+import os
 import random
+import signal
+import subprocess
+import sys
+import tempfile
 
 import numpy as np
 
@@ -81,6 +88,20 @@ class Backend:
         out = np.zeros((len(offs) - 1, out_words), dtype=np.uint32)
         self._call("ec_batch" if not self.device else "ec", curve, op, len(offs) - 1, _p(pts), _p(offs, _i32p), _p(aux), _p(out))
         return out
+
+    def ec_quad(self, curve, op, pts, offs, aux, out_words):
+        """device only: one sequence per DPP quad; out[s, role] = the words lane `role` of the quad stored"""
+        out = np.zeros((len(offs) - 1, 4, out_words), dtype=np.uint32)
+        self._call("ec_quad", curve, op, len(offs) - 1, _p(pts), _p(offs, _i32p), _p(aux), _p(out))
+        return out
+
+    def refuses(self, fn, curve, op, npts=1):
+        """the entry point answers -1 (nothing launched) for a (curve, op) pair it does not have; one well-formed sequence of npts points"""
+        z, o = np.zeros(1024, dtype=np.uint32), np.array([0, npts], dtype=np.int32)
+        args = (curve, op, 1, _p(z), _p(o, _i32p), _p(z), _p(np.zeros(1024, dtype=np.uint32)))
+        if not self.device:
+            return getattr(self.lib, "host_" + fn)(*args) == -1
+        return getattr(self.lib, "dm_" + fn)(*args, _p(np.zeros(1, dtype=np.uint32))) == -1
 
 
 def words(vals, W):
@@ -447,6 +468,53 @@ G1 = {0: pyref.BN254, 1: pyref.BLS12_381, 4: pyref.BLS12_377, 5: pyref.GRUMPKIN}
 G2 = {2: pyref.BN254_G2, 3: pyref.BLS12_381_G2, 6: pyref.BLS12_377_G2}
 
 
+SIGNED_ADD = (0, 5)   # EC::SIGNED_MADD: G1 over a 9-limb field (bn254, grumpkin) -- ec_case op 7
+SMALL_B3 = (0, 1, 4)  # has_small_b3: bn254, bls12_381, bls12_377 G1 -- ec_case op 8, the quad tier's dbl_quad
+
+
+class _Group:
+    """a curve id's integer group law (oracle/pyref.py) and what the encodings need"""
+
+    def __init__(self, ci):
+        self.ci, self.g2 = ci, ci in G2
+        self.c = G2[ci] if self.g2 else G1[ci]
+        self.INF = pyref.INF2 if self.g2 else pyref.INF
+        fns = (pyref.g2_add, pyref.g2_neg, pyref.g2_mul) if self.g2 else (pyref.ec_add, pyref.ec_neg, pyref.ec_mul)
+        self.add, self.neg, self.mul = (functools.partial(f, self.c) for f in fns)
+        self.order = self.c.base.r if self.g2 else self.c.r
+        self.q = self.c.base.q if self.g2 else self.c.q
+        self.n32 = self.c.base.limbs_q if self.g2 else self.c.limbs_q
+        self.comp = 2 if self.g2 else 1
+        self.zero = (0, 0) if self.g2 else 0
+
+    def sum(self, pts, ng):
+        acc = self.INF
+        for p_, n_ in zip(pts, ng):
+            acc = self.add(acc, self.neg(p_) if n_ else p_)
+        return acc
+
+    def affine(self, v):
+        """3 * comp coordinate integers (X, Y, Z as the harnesses store them) -> (affine point, X, Y, Z)"""
+        if self.g2:
+            X, Y, Z = (v[0], v[1]), (v[2], v[3]), (v[4], v[5])
+            return pyref.g2_proj_to_affine(self.c, X, Y, Z), X, Y, Z
+        X, Y, Z = v
+        return pyref.proj_to_affine(self.c, X, Y, Z), X, Y, Z
+
+
+@functools.lru_cache(maxsize=None)
+def group(ci):
+    return _Group(ci)
+
+
+@functools.lru_cache(maxsize=None)
+def ec_base(ci):
+    """the base points of ec_plan (its seed's first draw is their offset)"""
+    G = group(ci)
+    k0 = random.Random((142 if G.g2 else 42) + ci).randrange(G.order)
+    return pyref.g2_gen_points(G.c, 20, k0=k0) if G.g2 else pyref.gen_points(G.c, 30, k0=k0)
+
+
 @functools.lru_cache(maxsize=None)
 def ec_plan(ci):
     """{op: list of (points, aux words, expected affine point)}"""
@@ -456,7 +524,8 @@ def ec_plan(ci):
     add, neg, mul = (pyref.g2_add, pyref.g2_neg, pyref.g2_mul) if g2 else (pyref.ec_add, pyref.ec_neg, pyref.ec_mul)
     rnd = random.Random((142 if g2 else 42) + ci)
     order = c.base.r if g2 else c.r
-    base = (pyref.g2_gen_points(c, 20, k0=rnd.randrange(order)) if g2 else pyref.gen_points(c, 30, k0=rnd.randrange(order)))
+    rnd.randrange(order)  # (the offset of the base points)
+    base = ec_base(ci)
     seqs = []
     for trial in range(16 if g2 else 24):
         k = rnd.randrange(1, 14 if g2 else 16)
@@ -486,43 +555,366 @@ def ec_plan(ci):
     plan[4] = [([base[2]], [k], mul(c, 1 << k, base[2])) for k in [0, 1, 5, 16]]
     plan[5] = [([base[2]], [k], mul(c, 1 << k, base[2])) for k in [0, 1, 2, 7, 64, 300]] + [([INF], [9], INF)]
     plan[6] = [([b], [k], mul(c, 1 << k, b)) for k in [0, 1, 2, 3, 17, 84, 300] for b in (base[2], base[5])] + [([INF], [9], INF)]
+    if ci in SIGNED_ADD:
+        # op 7, one lane of k_reduce_wave on the signed layer: tri = add_signed(tri, line); line = add_signed(line, b_i) from two identities,
+        # output signed_to_unsigned(add_signed(tri, line)) = sum (m - i) b_i over the buckets b_0 .. b_{m-1}
+        P, Q, T = base[0], base[1], base[6]
+        buckets = [(pts, ng) for pts, ng, _ in seqs]
+        buckets += [([INF], [0]), ([INF] * 7, [0] * 7)]                                              # all-identity
+        buckets += [([P] + [INF] * 6, [0] * 7), ([INF] * 3 + [P] + [INF] * 3, [0] * 7), ([INF] * 6 + [P], [0] * 7)]  # one bucket, first / middle / last
+        buckets += [([P, P], [0, 0]), ([INF, Q, Q, INF, T, T, T], [0] * 7), ([Q, Q, P, P], [1, 1, 0, 0])]   # equal neighbouring buckets
+        buckets += [([P, P], [0, 1]), ([Q, P, P, T], [0, 1, 0, 0]), ([P, P, Q, Q, INF, T, T], [0, 1, 1, 0, 0, 0, 1])]  # b, -b pairs
+        plan[7] = []
+        for pts, ng in buckets:
+            tri, line = INF, INF
+            for p_, n_ in zip(pts, ng):
+                tri = add(c, tri, line)
+                line = add(c, line, neg(c, p_) if n_ else p_)
+            plan[7].append((pts, ng, add(c, tri, line)))
+    if ci in SMALL_B3:  # op 8: op 5's cases through EcDblSmallB::dbl, the one-lane twin of dbl_quad
+        plan[8] = plan[5]
     return plan
 
 
+IDENTITY_FORM_OPS = (0, 1, 2, 5, 7, 8)  # complete formulas (and from_jac): the identity comes out as (0 : y != 0 : 0)
+
+
+def encode_cases(G, cases):
+    """(point words, offsets, aux words) of a case list as dm_ec / dm_ec_quad / host_ec_batch take them"""
+    flat, offs, aux = [], [0], []
+    for pts, ax, _ in cases:
+        for (x, y) in pts:
+            flat += list(x) + list(y) if G.g2 else [x, y]
+        aux += list(ax) if len(ax) == len(pts) else list(ax) + [0] * (len(pts) - len(ax))
+        offs.append(offs[-1] + len(pts))
+    return words(flat, G.n32).reshape(-1), np.array(offs, dtype=np.int32), np.array(aux, dtype=np.uint32)
+
+
+def run_ec(be: Backend, ci, op, cases):
+    """one-lane tier: the canonical projective words of every case, one row each"""
+    G = group(ci)
+    return be.ec(ci, op, *encode_cases(G, cases), 3 * G.comp * G.n32)
+
+
+def verify_points(G, rows, cases, ctx, identity_form=True):
+    """rows of canonical projective words against the cases' expected affine points"""
+    vals = row_ints(np.ascontiguousarray(rows).reshape(-1, G.n32), 32)
+    k = 3 * G.comp
+    for s, (pts, ax, exp) in enumerate(cases):
+        v = vals[s * k:(s + 1) * k]
+        assert all(t < G.q for t in v), (ctx, s, "a coordinate is not below q")
+        got, X, Y, Z = G.affine(v)
+        assert got == exp, f"{ctx} sequence {s}: aux {list(ax)}, points {[_hexpt(p_) for p_ in pts]}: got {_hexpt(got)} expected {_hexpt(exp)}"
+        if exp == G.INF and identity_form:
+            assert Z == G.zero and Y != G.zero, (ctx, s, "identity must be (0 : y != 0 : 0)")
+    return len(cases)
+
+
 def check_ec(be: Backend, ci):
-    g2 = ci in G2
-    c = G2[ci] if g2 else G1[ci]
-    q = c.base.q if g2 else c.q
-    n32 = c.base.limbs_q if g2 else c.limbs_q
-    comp = 2 if g2 else 1
-    INF = pyref.INF2 if g2 else pyref.INF
+    G = group(ci)
     n = 0
     for op, cases in ec_plan(ci).items():
-        flat, offs, aux = [], [0], []
-        for pts, ax, _ in cases:
-            for (x, y) in pts:
-                flat += list(x) + list(y) if g2 else [x, y]
-            aux += ax if len(ax) == len(pts) else ax + [0] * (len(pts) - len(ax))
-            offs.append(offs[-1] + len(pts))
-        out = be.ec(ci, op, words(flat, n32).reshape(-1), np.array(offs, dtype=np.int32), np.array(aux, dtype=np.uint32), 3 * comp * n32)
-        vals = row_ints(out.reshape(-1, n32), 32)
-        for s, (pts, ax, exp) in enumerate(cases):
-            v = vals[s * 3 * comp:(s + 1) * 3 * comp]
-            assert all(t < q for t in v), (c.name, op, s, be.name)
-            if g2:
-                X, Y, Z = (v[0], v[1]), (v[2], v[3]), (v[4], v[5])
-                got = pyref.g2_proj_to_affine(c, X, Y, Z)
-                zero = (0, 0)
-            else:
-                X, Y, Z = v
-                got = pyref.proj_to_affine(c, X, Y, Z)
-                zero = 0
-            assert got == exp, f"{c.name} {'G2' if g2 else 'G1'} ec op {op} sequence {s} variant {be.name}: aux {ax}, points {[_hexpt(p_) for p_ in pts]}: got {_hexpt(got)} expected {_hexpt(exp)}"
-            if exp == INF and op in (0, 1, 2, 5):
-                assert Z == zero and Y != zero, (c.name, op, s, "identity must be (0 : y != 0 : 0)", be.name)
-            n += 1
+        out = run_ec(be, ci, op, cases)
+        n += verify_points(G, out, cases, f"{G.c.name} {'G2' if G.g2 else 'G1'} ec op {op} variant {be.name}", identity_form=op in IDENTITY_FORM_OPS)
     return n
+
+
+def ec_unsupported(ci):
+    """(op) pairs of the one-lane tier that must answer -1 for this curve"""
+    return [op for op, ok in ((7, ci in SIGNED_ADD), (8, ci in SMALL_B3)) if not ok]
 
 
 def _hexpt(pt):
     return "(" + ", ".join(_hex(v) for v in pt) + ")"
+
+
+# ---- quad tier (device only): the four-lane EC operations, one sequence per DPP quad (device_math_harness.hip k_ec_quad) ------------
+# Q0 complete sum with EcQuadAdd::add | Q1 the same with EC::add_quad | Q2 2^k P by dbl_quad | Q3 to_jac, k x dbl_jac_quad, from_jac |
+# Q4 the Horner walk of k_final_horner, acc = 2^w acc + S down the sequence (aux = width << 1 | negate). Each function only for the
+# curves the product instantiates it for; every other (curve, op) pair answers -1.
+Q_ADD, Q_ADDQ, Q_DBL, Q_JAC, Q_HORNER = 0, 1, 2, 3, 4
+Q_RAW = 0x100  # Q0 (two points per sequence) and Q2 (one point, one doubling): operands as raw Montgomery limb rows (X, Y, Z)
+QUAD_CURVES = {Q_ADD: (0, 1, 4, 5, 2), Q_ADDQ: (5, 2, 3, 6), Q_DBL: SMALL_B3, Q_JAC: (5, 2, 3, 6), Q_HORNER: (0, 1, 2, 3, 4, 5, 6)}
+QUAD_NAME = {Q_ADD: "EcQuadAdd::add", Q_ADDQ: "EC::add_quad", Q_DBL: "EcDblSmallB::dbl_quad", Q_JAC: "EC::dbl_jac_quad", Q_HORNER: "Horner walk"}
+QUAD_TWIN = {Q_ADD: (1, "EC::add"), Q_ADDQ: (1, "EC::add"), Q_DBL: (8, "EcDblSmallB::dbl"), Q_JAC: (5, "EC::dbl_jac")}  # ec_case op of the one-lane twin
+HORNER_CANCEL = -2  # index of the cancelling Horner case in quad_plan(ci)[Q_HORNER]
+
+
+@functools.lru_cache(maxsize=None)
+def quad_plan(ci):
+    """{op: list of (points, aux words, expected affine point)} for the ops this curve has"""
+    G = group(ci)
+    base, INF = ec_base(ci), G.INF
+    P, Q = base[0], base[1]
+    plan = {}
+    sums = list(ec_plan(ci)[1])
+    for pts, ng in (([INF], [0]), ([INF, INF], [0, 0]), ([P, INF], [0, 0]), ([P] * 4, [0] * 4),  # [P] * 4: the sum meets the operand again after a doubling
+                    ([P, Q, Q, P, Q, P], [0, 0, 1, 1, 0, 0])):                                        # the running sum returns to O in the middle and goes on
+        sums.append((pts, ng, G.sum(pts, ng)))
+    for op in (Q_ADD, Q_ADDQ):
+        if ci in QUAD_CURVES[op]:
+            plan[op] = sums
+    for op in (Q_DBL, Q_JAC):
+        if ci in QUAD_CURVES[op]:
+            plan[op] = ec_plan(ci)[5]  # k in 0, 1, 2, 7, 64, 300 on a point with a non-trivial Z, and P = O
+
+    def horner(pts, aux):
+        acc = G.neg(pts[0]) if aux[0] & 1 else pts[0]
+        for p_, a in zip(pts[1:], aux[1:]):
+            acc = G.add(G.mul(1 << (a >> 1), acc), G.neg(p_) if a & 1 else p_)
+        return acc
+
+    H = []
+
+    def case(pts, widths, ng=None):
+        aux = [(w << 1) | n for w, n in zip(widths, ng or [0] * len(pts))]
+        H.append((pts, aux, horner(pts, aux)))
+
+    rnd = random.Random(4242 + ci)
+    for t in range(11):
+        n = rnd.randrange(3, 9)
+        pts = [rnd.choice(base) for _ in range(n)]
+        ws = [0] + [rnd.randrange(1, 23) for _ in range(n - 1)]
+        if t == 0:
+            ws[1], ws[-1] = 1, 22
+        if t % 2 == 0:
+            pts[rnd.randrange(1, n)] = INF
+        case(pts, ws, [rnd.randrange(2) for _ in range(n)])
+    case([INF] * 5, [0, 3, 22, 1, 8])           # every window sum the identity
+    case([P, INF, INF, INF], [0, 22, 13, 1])    # only the top window
+    case([INF, INF, INF, P], [0, 5, 1, 22])     # only window 0
+    w1, w3 = 5, 22                                # S_i = -2^{w_i} acc: the addition after a doubling chain cancels, in the middle and at the end
+    case([P, G.neg(G.mul(1 << w1, P)), Q, G.neg(G.mul(1 << w3, Q))], [0, w1, 7, w3])
+    case([P, G.mul(1 << 4, P), Q], [0, 4, 9])   # S_i = +2^{w_i} acc: the addition is a doubling
+    plan[Q_HORNER] = H
+    return plan
+
+
+def run_quad(be: Backend, ci, op, cases):
+    G = group(ci)
+    return be.ec_quad(ci, op, *encode_cases(G, cases), 3 * G.comp * G.n32)
+
+
+def lanes_agree(out, ctx):
+    """the four lanes of every quad stored identical words (lanes 1..3 feed the next operation of every real chain)"""
+    for role in (1, 2, 3):
+        bad = np.nonzero((out[:, role, :] != out[:, 0, :]).any(axis=1))[0]
+        assert not len(bad), (ctx, f"lane {role} of the quad differs from lane 0 in sequences {bad[:8].tolist()}")
+    return np.ascontiguousarray(out[:, 0, :])
+
+
+_QUAD_VERIFIED = {}  # (ci, op) -> lane-0 bytes that passed the integer checks (a second build that returns the same bytes is not checked twice)
+
+
+def check_ec_quad(be: Backend, ci):
+    """every quad op of the curve on its directed sequences; returns ({op: comparisons}, {op: output bytes}, {op: twin claim held})"""
+    G = group(ci)
+    res, outs, twin_ok = {}, {}, {}
+    for op in range(5):
+        ctx = f"{G.c.name} {'G2' if G.g2 else 'G1'} quad op {op} ({QUAD_NAME[op]}) variant {be.name}"
+        if ci not in QUAD_CURVES[op]:
+            assert be.refuses("ec_quad", ci, op), (ctx, "the product does not instantiate this pair: the harness must answer -1")
+            continue
+        cases = quad_plan(ci)[op]
+        rows = lanes_agree(run_quad(be, ci, op, cases), ctx)
+        outs[op] = rows.tobytes()
+        if _QUAD_VERIFIED.get((ci, op)) != outs[op]:
+            verify_points(G, rows, cases, ctx)
+            _QUAD_VERIFIED[(ci, op)] = outs[op]
+        if op in QUAD_TWIN:  # the comment of each function claims "the same values" as its one-lane form
+            top, tname = QUAD_TWIN[op]
+            twin = run_ec(be, ci, top, cases)
+            bad = np.nonzero((twin != rows).any(axis=1))[0]
+            twin_ok[op] = not len(bad)
+            assert not len(bad), (ctx, f"projective words differ from the one-lane twin {tname} in sequences {bad[:8].tolist()} (affine values agree: a projective scale)")
+        res[op] = len(cases)
+    for op, npts in ((Q_ADD | Q_RAW, 2), (Q_DBL | Q_RAW, 1), (Q_ADDQ | Q_RAW, 2), (Q_JAC | Q_RAW, 1), (Q_HORNER | Q_RAW, 2), (5, 1)):
+        if (op & 0xFF) not in (Q_ADD, Q_DBL) or not op & Q_RAW or ci not in QUAD_CURVES[op & 0xFF]:
+            assert be.refuses("ec_quad", ci, op, npts), (G.c.name, hex(op), "must answer -1")
+    return res, outs, twin_ok
+
+
+def check_ec_quad_placement(be: Backend, ci):
+    """one complete-sum sequence and one Horner sequence in each of the 16 quad positions of a wave, the other 15 quads running different
+    sequences of different lengths; once more in a launch whose sequence count is no multiple of 16. A sequence must give the same
+    words wherever it runs (quads 3 and 4 sit on either side of the 16-lane DPP row boundary); the integers are consulted once per sequence.
+    Returns {op: (sequence, placement) comparisons}"""
+    G = group(ci)
+    res = {}
+    for op, ti in ((Q_ADD if ci in QUAD_CURVES[Q_ADD] else Q_ADDQ, 0), (Q_HORNER, HORNER_CANCEL)):
+        ctx = f"{G.c.name} {'G2' if G.g2 else 'G1'} quad op {op} ({QUAD_NAME[op]}) placement, variant {be.name}"
+        cases = quad_plan(ci)[op]
+        target = cases[ti]  # sums: doubling at the start, inserted identity, cancellation at the end; Horner: the cancelling walk
+        fillers = [c for c in cases if c is not target][:15]
+        assert len(fillers) == 15 and len({len(c[0]) for c in fillers}) >= 4
+        full = []
+        for pos in range(16):
+            full += fillers[:pos] + [target] + fillers[pos:]
+        ragged = full + fillers[:2] + [target] + fillers[2:4]
+        assert len(full) == 256 and len(ragged) % 16 == 5
+        words_of = {}
+        n = 0
+        for layout in (full, ragged):
+            rows = lanes_agree(run_quad(be, ci, op, layout), ctx)
+            if not words_of:  # the first block holds every sequence once: position 0 for the target
+                verify_points(G, rows[:16], layout[:16], ctx)
+                words_of = {id(c): rows[i].tobytes() for i, c in enumerate(layout[:16])}
+            for i, c in enumerate(layout):
+                assert rows[i].tobytes() == words_of[id(c)], (ctx, f"sequence at index {i} (quad {i % 16} of its wave, launch of {len(layout)}) differs from the same sequence in another position")
+            n += len(layout)
+        res[op] = n
+    return res
+
+
+# raw operands at the documented bounds: ec_dbl_quad.hpp states X, Y, Z <= 8 p for the doubling, the additions are laid out for <= 4 p
+CURVE_FIELD = {0: 0, 1: 2, 4: 4, 5: 1, 2: 0, 3: 2, 6: 4}  # curve id -> id of the field its coordinates (G2: their components) live in
+RAW_STATED = {Q_ADD: 4, Q_DBL: 8}
+HOST_RAW_FN = {Q_ADD: 0, Q_DBL: 2}  # host_ec_raw: 0 = E::add, 2 = EcDblSmallB::dbl (what host op 7 runs under the tracker)
+
+
+@functools.lru_cache(maxsize=None)
+def raw_quad_cases(ci, op, K):
+    """(limb rows (points, 3 * comp * NL), offsets, cases): projective points with a non-trivial Z whose coordinates are the Montgomery
+    representatives a0 + j p, j from _edge_js(K): 0, 1 and the largest inside the stated bound K p"""
+    G = group(ci)
+    _, p, NL, _ = BIG[CURVE_FIELD[ci]]
+    assert p == G.q
+    R = 1 << (RB * NL)
+    A = Fp2(Fp(p, 1, 0)) if G.g2 else Fp(p, 1, 0)
+    base = ec_base(ci)
+    P, Q2, T = base[0], base[1], base[3]
+    rnd = random.Random(8800 + 16 * ci + op)
+    js = _edge_js(K)
+
+    def elem():
+        return tuple(rnd.randrange(1, p) for _ in range(2)) if G.g2 else rnd.randrange(1, p)
+
+    def proj(pt):
+        if pt == G.INF:
+            return [G.zero, elem(), G.zero]
+        lam = elem()
+        return [A.mul(pt[0], lam), A.mul(pt[1], lam), lam]
+
+    def reps(coords, jl):  # one j per coordinate (both components of an Fq2 coordinate take it)
+        out = []
+        for e, j in zip(coords, jl):
+            out += [(v * R) % p + j * p for v in (e if G.g2 else (e,))]
+        return out
+
+    vals, offs, cases = [], [0], []
+
+    def emit(points, jls, exp):
+        for pt, jl in zip(points, jls):
+            vals.extend(reps(proj(pt), jl))
+        offs.append(offs[-1] + len(points))
+        cases.append((points, [j for jl in jls for j in jl], exp))
+
+    if op == Q_ADD:
+        for a, b in ((P, Q2), (P, P), (P, G.neg(P)), (P, G.INF), (G.INF, P), (G.INF, G.INF)):
+            exp = G.add(a, b)
+            for ja in js:
+                for jb in js:
+                    emit([a, b], [[ja] * 3, [jb] * 3], exp)
+            for _ in range(3):
+                emit([a, b], [[rnd.choice(js) for _ in range(3)] for _ in range(2)], exp)
+    else:
+        for a in (P, T, G.INF):
+            exp = G.add(a, a)
+            for j in js:
+                emit([a], [[j] * 3], exp)
+            for _ in range(4):
+                emit([a], [[rnd.choice(js) for _ in range(3)]], exp)
+    assert all(v < K * p and v < R for v in vals)
+    limbs = limb_rows(vals, NL).reshape(offs[-1], 3 * G.comp * NL)
+    return np.ascontiguousarray(limbs), np.array(offs, dtype=np.int32), cases
+
+
+HERE = os.path.dirname(os.path.abspath(__file__))
+HOST_SO = os.path.join(HERE, "_build", "libhost_math.so")
+HOST_SRC = os.path.join(HERE, "host_math_harness.cpp")
+HOST_DEPS = [HOST_SRC, os.path.join(HERE, "math_cases.hpp")] + [os.path.join(HERE, "..", "icicle_amd", "csrc", f) for f in
+                                                                ("bigfield.hpp", "fq2.hpp", "ec.hpp", "smallfield.hpp", "goldfield.hpp", "field_consts.h", "glv.hpp", "ec_dbl_quad.hpp")]
+
+
+def host_lib():
+    """tests/_build/libhost_math.so, the host build of the arithmetic headers with the bound tracker on; rebuilt when stale"""
+    os.makedirs(os.path.dirname(HOST_SO), exist_ok=True)
+    if not os.path.exists(HOST_SO) or any(os.path.getmtime(d) > os.path.getmtime(HOST_SO) for d in HOST_DEPS):
+        subprocess.check_call(["g++", "-std=c++17", "-O1", "-DBIGFIELD_BOUNDS", "-fPIC", "-shared", HOST_SRC, "-o", HOST_SO + ".tmp"])
+        os.replace(HOST_SO + ".tmp", HOST_SO)
+    return HOST_SO
+
+
+def _host_raw_child(ci, op, K, outpath):
+    """(child process) the one-lane twin of a quad function on the raw operands of raw_quad_cases, bound tracker on: the tracker aborts
+    the process when a stated bound K is outside a precondition"""
+    G = group(ci)
+    lib = ctypes.CDLL(HOST_SO)
+    limbs, offs, cases = raw_quad_cases(ci, op, K)
+    out = np.zeros((len(cases), 3 * G.comp * G.n32), dtype=np.uint32)
+    rc = lib.host_ec_raw(ci, HOST_RAW_FN[op], K, len(cases), _p(limbs), _p(out))
+    np.save(outpath, out)
+    return rc
+
+
+@functools.lru_cache(maxsize=None)
+def host_raw_twin(ci, op, K):
+    """(canonical projective words of the one-lane twin under the tracker, None) or (None, the tracker's message) when it aborted"""
+    host_lib()
+    root = os.path.dirname(HERE)
+    with tempfile.TemporaryDirectory() as tmp:
+        path = os.path.join(tmp, "out.npy")
+        code = f"import sys; sys.path.insert(0, {root!r}); from tests import math_expect as X; sys.exit(X._host_raw_child({ci}, {op}, {K}, {path!r}))"
+        r = subprocess.run([sys.executable, "-c", code], capture_output=True, text=True, cwd=root, timeout=300)
+        if r.returncode == 0:
+            return np.load(path), None
+    assert r.returncode == -signal.SIGABRT and "bigfield bound violation" in r.stderr, (ci, op, K, r.returncode, r.stderr[-2000:])
+    return None, r.stderr.strip().splitlines()[0]
+
+
+@functools.lru_cache(maxsize=None)
+def accepted_raw_bound(ci, op):
+    """(largest K <= the header's stated bound that the tracker accepts for the one-lane twin, its output rows, the refusals on the way)"""
+    K, refused = RAW_STATED[op], []
+    while K >= 1:
+        rows, msg = host_raw_twin(ci, op, K)
+        if rows is not None:
+            return K, rows, tuple(refused)
+        refused.append((K, msg))
+        K //= 2
+    raise AssertionError((ci, op, "the tracker accepts no bound", refused))
+
+
+def check_host_raw(ci):
+    """CPU leg: the tracker's accepted range against the header's, and the one-lane twin against the integers. {op: (accepted K, stated K, cases)}"""
+    G = group(ci)
+    res = {}
+    for op in (Q_ADD, Q_DBL):
+        if ci not in QUAD_CURVES[op]:
+            continue
+        K, rows, refused = accepted_raw_bound(ci, op)
+        _, _, cases = raw_quad_cases(ci, op, K)
+        verify_points(G, rows, cases, f"{G.c.name} {'G2' if G.g2 else 'G1'} host twin of {QUAD_NAME[op]} on raw operands below {K} p")
+        res[op] = (K, RAW_STATED[op], len(cases), refused)
+    return res
+
+
+def check_ec_quad_raw(be: Backend, ci):
+    """the quad addition and doubling on raw representatives up to the bound the tracker accepted for the one-lane twin (an operand
+    outside it never reaches the device). Returns ({op: (accepted K, stated K, cases)}, {op: output bytes})"""
+    G = group(ci)
+    res, outs = {}, {}
+    for op in (Q_ADD, Q_DBL):
+        if ci not in QUAD_CURVES[op]:
+            continue
+        K, host_rows, _ = accepted_raw_bound(ci, op)
+        limbs, offs, cases = raw_quad_cases(ci, op, K)
+        ctx = f"{G.c.name} {'G2' if G.g2 else 'G1'} {QUAD_NAME[op]} on raw operands below {K} p, variant {be.name}"
+        out = be.ec_quad(ci, op | Q_RAW, limbs.reshape(-1), offs, np.zeros(offs[-1], dtype=np.uint32), 3 * G.comp * G.n32)
+        rows = lanes_agree(out, ctx)
+        outs[op] = rows.tobytes()
+        verify_points(G, rows, cases, ctx)
+        bad = np.nonzero((rows != host_rows).any(axis=1))[0]
+        assert not len(bad), (ctx, f"projective words differ from the one-lane twin on the host in cases {bad[:8].tolist()}")
+        res[op] = (K, RAW_STATED[op], len(cases))
+    return res, outs

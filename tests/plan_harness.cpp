@@ -462,3 +462,12 @@ extern "C" int msm_fold_probe(int n, int bits, int batch, int c, int proj_bytes,
   if (!msm_sort_plan(n, pl.c, pl.pf, probe_knobs(knobs), &sp)) return -1;
   return msm_batch_fold(pl, sp, n, (size_t)proj_bytes, (size_t)staged_base_bytes, (size_t)free_bytes, batch, has_hook != 0);
 }
+// the window plan msm() makes for one MSM of n terms with config.c = c (0: the cost model): out = c, nwin, wpf, nb, n_lo
+extern "C" int msm_plan_probe(int n, int bits, int c, int* out)
+{
+  icicle_msm_config_t cfg{};
+  cfg.batch_size = 1, cfg.c = c;
+  const MsmPlan pl = make_plan(n, bits, cfg);
+  out[0] = pl.c, out[1] = pl.nwin, out[2] = pl.wpf, out[3] = (int)pl.nb, out[4] = pl.n_lo;
+  return 0;
+}

@@ -10,6 +10,7 @@ running sums meet: an addition that is a doubling), cancelled buckets between fu
 Every result is compared on affine limbs with the reference CPU backend; one reference run per input. The environment knobs are
 read once per process, hence a child process for ICICLE_HIP_MSM_REDUCE_QUAD=0 (uniform plans on the one-lane kernels) and one for
 ICICLE_HIP_MSM_REDUCE_SIGNED=0 (the additions of the parent)."""
+import functools
 import os
 import subprocess
 import sys
@@ -75,6 +76,74 @@ def _plan_widths(bits, nwin):
     return out
 
 
+# ---- the directed inputs, shared with tests/test_gpu_msm_quad_reduce.py (the same bucket patterns through the four-lane kernels).
+# r: the scalar modulus; bases_fn(n, period=1024): n base rows; neg_fn(rows): the rows of the negated points. Each returns (scalars, bases).
+def _g1_fns(C):
+    return C.r, functools.partial(_bases, C), functools.partial(_neg_rows, C)
+
+
+def in_all_scalars_equal(r, bases_fn, neg_fn):
+    """one full bucket per window, every other bucket the identity: line and tri0 stay the identity until that row"""
+    rng = np.random.default_rng(9102)
+    n = (1 << 10) + 1
+    s = rand_scalars(rng, 1, r)[0]
+    return [s] * n, bases_fn(n)
+
+
+def in_equal_bases_under_scalars_k_and_k_plus_one(r, bases_fn, neg_fn):
+    """every bucket holds a multiple of ONE point and neighbouring buckets are full: column sums and running sums that are equal
+    or negatives of each other meet in the lane scans (an addition that is a doubling, one that gives the identity)"""
+    rng = np.random.default_rng(9103)
+    n = 1 << 10
+    bases = np.ascontiguousarray(np.tile(bases_fn(1), (n, 1)))
+    vals = rand_scalars(rng, n, r)
+    for i in range(0, n, 2):
+        vals[i + 1] = (vals[i] + 1) % r
+    vals[0:64] = [5, 6] * 32  # the same number of points in buckets 5 and 6 of window 0: equal bucket sums side by side
+    return vals, bases
+
+
+def in_cancelling_pairs(r, bases_fn, neg_fn):
+    """cancelled buckets (the identity) between full ones"""
+    rng = np.random.default_rng(9104)
+    n = 1 << 12
+    half = bases_fn(n // 2)
+    bases = np.empty((n, half.shape[1]), dtype=np.uint32)
+    bases[0::2] = half
+    bases[1::2] = neg_fn(half)
+    vals = rand_scalars(rng, n, r)
+    for i in range(0, n // 2, 2):  # the first half of the pairs share a scalar: their buckets cancel where nothing else lands
+        vals[i + 1] = vals[i]
+    return vals, bases
+
+
+def in_scalars_one_and_r_minus_one(r, bases_fn, neg_fn):
+    """only bucket 1 of window 0 is populated, with both signs: every other chunk sums identities"""
+    n = (1 << 11) + 7
+    return [r - 1 if i % 3 else 1 for i in range(n)], bases_fn(n, period=300)
+
+
+def in_top_bucket_only(r, bases_fn, wins):
+    """every second window's digit is 2^(width - 1), the largest a signed digit takes; wins: (bit offset, width) of every window"""
+    bits = r.bit_length()
+    n = 1 << 10
+    s_even = sum(1 << (off + width - 1) for k, (off, width) in enumerate(wins) if k % 2 == 0 and off + width < bits)
+    s_odd = sum(1 << (off + width - 1) for k, (off, width) in enumerate(wins) if k % 2 == 1 and off + width < bits)
+    assert 0 < s_even < r and 0 < s_odd < r
+    return [s_even if i % 2 == 0 else s_odd for i in range(n)], bases_fn(n)
+
+
+def in_identity_bases(r, bases_fn, neg_fn):
+    rng = np.random.default_rng(9107)
+    n = 1 << 12
+    bases = bases_fn(n)
+    bases[0:3] = 0
+    bases[100:2000:2] = 0
+    bases[3000:3500] = 0
+    bases[-1] = 0
+    return rand_scalars(rng, n, r), bases
+
+
 @pytest.mark.parametrize("cname", SIGNED)
 def test_spread_scalars(hip, cname):
     C = pyref.CURVES[cname]
@@ -86,50 +155,29 @@ def test_spread_scalars(hip, cname):
 @pytest.mark.parametrize("cname", SIGNED)
 def test_all_scalars_equal(hip, cname):
     """one full bucket per window, every other bucket the identity: line and tri0 stay the identity until that row"""
-    C = pyref.CURVES[cname]
-    rng = np.random.default_rng(9102)
-    n = (1 << 10) + 1
-    s = rand_scalars(rng, 1, C.r)[0]
-    _check(hip, cname, to_words([s] * n, 8), _bases(C, n))
+    vals, bases = in_all_scalars_equal(*_g1_fns(pyref.CURVES[cname]))
+    _check(hip, cname, to_words(vals, 8), bases)
 
 
 @pytest.mark.parametrize("cname", SIGNED)
 def test_equal_bases_under_scalars_k_and_k_plus_one(hip, cname):
     """every bucket holds a multiple of ONE point and neighbouring buckets are full: column sums and running sums that are equal
     or negatives of each other meet in the lane scans (an addition that is a doubling, one that gives the identity)"""
-    C = pyref.CURVES[cname]
-    rng = np.random.default_rng(9103)
-    n = 1 << 10
-    bases = np.ascontiguousarray(np.tile(points_to_array(C, cached_points(C, 1)), (n, 1)))
-    vals = rand_scalars(rng, n, C.r)
-    for i in range(0, n, 2):
-        vals[i + 1] = (vals[i] + 1) % C.r
-    vals[0:64] = [5, 6] * 32  # the same number of points in buckets 5 and 6 of window 0: equal bucket sums side by side
+    vals, bases = in_equal_bases_under_scalars_k_and_k_plus_one(*_g1_fns(pyref.CURVES[cname]))
     _check(hip, cname, to_words(vals, 8), bases)
 
 
 @pytest.mark.parametrize("cname", SIGNED)
 def test_cancelling_pairs_leave_identity_buckets_between_full_ones(hip, cname):
-    C = pyref.CURVES[cname]
-    rng = np.random.default_rng(9104)
-    n = 1 << 12
-    half = _bases(C, n // 2)
-    bases = np.empty((n, half.shape[1]), dtype=np.uint32)
-    bases[0::2] = half
-    bases[1::2] = _neg_rows(C, half)
-    vals = rand_scalars(rng, n, C.r)
-    for i in range(0, n // 2, 2):  # the first half of the pairs share a scalar: their buckets cancel where nothing else lands
-        vals[i + 1] = vals[i]
+    vals, bases = in_cancelling_pairs(*_g1_fns(pyref.CURVES[cname]))
     _check(hip, cname, to_words(vals, 8), bases)
 
 
 @pytest.mark.parametrize("cname", SIGNED)
 def test_scalars_one_and_r_minus_one(hip, cname):
     """only bucket 1 of window 0 is populated, with both signs: every other chunk sums identities"""
-    C = pyref.CURVES[cname]
-    n = (1 << 11) + 7
-    vals = [C.r - 1 if i % 3 else 1 for i in range(n)]
-    _check(hip, cname, to_words(vals, 8), _bases(C, n, period=300))
+    vals, bases = in_scalars_one_and_r_minus_one(*_g1_fns(pyref.CURVES[cname]))
+    _check(hip, cname, to_words(vals, 8), bases)
 
 
 @pytest.mark.parametrize("cname", SIGNED)
@@ -138,27 +186,15 @@ def test_top_bucket_only(hip, cname, c):
     """every second window's digit is 2^(width - 1), the largest a signed digit takes: the last bucket of the last chunk (row 0 of
     lane 63), with the identity everywhere else but for what a carry leaves in bucket 1 of the window above"""
     C = pyref.CURVES[cname]
-    bits = C.r.bit_length()
-    n = 1 << 10
-    wins = _plan_widths(bits, WINDOWS[c])
-    s_even = sum(1 << (off + width - 1) for k, (off, width) in enumerate(wins) if k % 2 == 0 and off + width < bits)
-    s_odd = sum(1 << (off + width - 1) for k, (off, width) in enumerate(wins) if k % 2 == 1 and off + width < bits)
-    assert 0 < s_even < C.r and 0 < s_odd < C.r
-    vals = [s_even if i % 2 == 0 else s_odd for i in range(n)]
-    _check(hip, cname, to_words(vals, 8), _bases(C, n), plans=(c,))
+    r, bases_fn, _ = _g1_fns(C)
+    vals, bases = in_top_bucket_only(r, bases_fn, _plan_widths(C.r.bit_length(), WINDOWS[c]))
+    _check(hip, cname, to_words(vals, 8), bases, plans=(c,))
 
 
 @pytest.mark.parametrize("cname", SIGNED)
 def test_identity_bases(hip, cname):
-    C = pyref.CURVES[cname]
-    rng = np.random.default_rng(9107)
-    n = 1 << 12
-    bases = _bases(C, n)
-    bases[0:3] = 0
-    bases[100:2000:2] = 0
-    bases[3000:3500] = 0
-    bases[-1] = 0
-    _check(hip, cname, to_words(rand_scalars(rng, n, C.r), 8), bases)
+    vals, bases = in_identity_bases(*_g1_fns(pyref.CURVES[cname]))
+    _check(hip, cname, to_words(vals, 8), bases)
 
 
 @pytest.mark.parametrize("cname", SIGNED)

@@ -5,15 +5,12 @@ projective formulas (reference: icicle/include/icicle/curves/projective.h:73-188
 import ctypes
 import os
 import random
-import subprocess
 
 import pytest
 
 from oracle import pyref
 
 HERE = os.path.dirname(os.path.abspath(__file__))
-SO = os.path.join(HERE, "_build", "libhost_math.so")
-SRC = os.path.join(HERE, "host_math_harness.cpp")
 FIELDS = {0: pyref.BN254.q, 1: pyref.BN254.r, 2: pyref.BLS12_381.q, 3: pyref.BLS12_381.r,
           4: pyref.BLS12_377.q, 5: pyref.BLS12_377.r, 6: pyref.STARK252.p, 7: pyref.GOLDILOCKS.p}
 NL = {0: 8, 1: 8, 2: 12, 3: 8, 4: 12, 5: 8, 6: 8, 7: 2}
@@ -21,11 +18,9 @@ NL = {0: 8, 1: 8, 2: 12, 3: 8, 4: 12, 5: 8, 6: 8, 7: 2}
 
 @pytest.fixture(scope="module")
 def lib():
-    os.makedirs(os.path.dirname(SO), exist_ok=True)
-    deps = [SRC, os.path.join(HERE, "math_cases.hpp")] + [os.path.join(HERE, "..", "icicle_amd", "csrc", f) for f in ("bigfield.hpp", "fq2.hpp", "ec.hpp", "smallfield.hpp", "goldfield.hpp", "field_consts.h", "glv.hpp", "ec_dbl_quad.hpp")]
-    if not os.path.exists(SO) or any(os.path.getmtime(d) > os.path.getmtime(SO) for d in deps):
-        subprocess.check_call(["g++", "-std=c++17", "-O1", "-DBIGFIELD_BOUNDS", "-fPIC", "-shared", SRC, "-o", SO])
-    return ctypes.CDLL(SO)
+    from tests import math_expect
+
+    return ctypes.CDLL(math_expect.host_lib())  # (built with g++ -O1 -DBIGFIELD_BOUNDS when stale)
 
 
 def w(x, n):
@@ -342,4 +337,23 @@ def test_ec_sequences_batched(lib, ci):
     """the EC sequences exactly as the device tier runs them (one per thread there, one after the other here)"""
     from tests import math_expect
 
-    assert math_expect.check_ec(_host_backend(lib), ci) > 0
+    be = _host_backend(lib)
+    assert math_expect.check_ec(be, ci) > 0
+    # op 7: the one-lane bucket reduction on the signed layer (add_signed, bn254 and grumpkin); op 8: EcDblSmallB::dbl chains
+    assert (7 in math_expect.ec_plan(ci)) == (ci in (0, 5)) and (8 in math_expect.ec_plan(ci)) == (ci in (0, 1, 4))
+    for op in math_expect.ec_unsupported(ci):
+        assert be.refuses("ec_batch", ci, op), (ci, op)
+
+
+@pytest.mark.parametrize("ci", [0, 1, 2, 4, 5])
+def test_quad_twins_on_raw_operands_at_the_stated_bounds(lib, ci):
+    """E::add with every coordinate stated <= 4 p and EcDblSmallB::dbl with <= 8 p (ec_dbl_quad.hpp's header), on representatives
+    a0 + j p up to the largest inside the bound: the tracker accepts the whole stated range (a refusal aborts a child process, not
+    this one) and the results are the integers'. tests/test_gpu_device_math.py sends the same operands through the four-lane forms."""
+    from tests import math_expect
+
+    res = math_expect.check_host_raw(ci)
+    print({math_expect.QUAD_NAME[op]: v for op, v in res.items()})
+    assert res
+    for op, (K, stated, n, refused) in res.items():
+        assert K == stated and not refused and n > 0, (ci, math_expect.QUAD_NAME[op], refused)

@@ -253,6 +253,35 @@ def test_msm_reduce_route_on_each_side_of_every_switch():
     assert _reduce(lib, nb, 12, n_lo=10)["mrow_lo"] == 128 and _reduce(lib, nb, 12, n_lo=10, reduce_balance=1)["mrow_lo"] == 64
 
 
+# the uniform single MSMs of tests/test_gpu_msm_quad_reduce.py: (scalar bits, c) -> (windows, buckets) by make_plan, and for c = 8, 13, 16 of a
+# 254-bit scalar the two costs msm_reduce_route compares (four-lane against one-lane)
+QUAD_REDUCE_SHAPES = {(254, 8): (32, 128), (254, 13): (20, 4096), (254, 16): (16, 32768), (255, 8): (32, 128), (255, 13): (20, 4096), (255, 16): (16, 32768)}
+QUAD_REDUCE_COSTS = {8: (195, 667), 13: (325, 1479), 16: (1001, 1015)}
+
+
+def test_directed_quad_reduce_shapes_take_the_four_lane_kernels():
+    """tests/test_gpu_msm_quad_reduce.py must not drift onto the one-lane kernels unnoticed: every (scalar bits, c) it runs as a uniform single
+    MSM of 2^10 .. 2^12 terms reduces its buckets with k_reduce_wave_quad and k_reduce_window_quad, for G1 and for the G2 with quad_ok
+    (BN254's, c = 8 and 13). c = 16 sits next to the switch: 1001 against 1015."""
+    lib = _lib()
+    for (bits, c), (nw, nb) in QUAD_REDUCE_SHAPES.items():
+        for n in ((1 << 10) + 1, 1 << 11, 1 << 12):
+            out = (ctypes.c_int * 5)()
+            assert lib.msm_plan_probe(n, bits, c, out) == 0
+            assert tuple(out) == (c, nw, nw, nb, 0), (bits, c, n, tuple(out))  # uniform: no narrow windows, no base table
+        r = _reduce(lib, nb, nw)
+        assert r["chunk"] == "k_reduce_wave_quad" and r["window"] == "k_reduce_window_quad" and not r["direct"], (bits, c, r)
+        assert (r["cost_q"], r["cost_s"]) == QUAD_REDUCE_COSTS[c] and r["cost_q"] < r["cost_s"], (bits, c, r)
+        assert r["wchunks"] == r["nsq"] > 1 and r["wchunk_size"] == 16 * r["mq"] and r["nsq"] * 16 * r["mq"] >= nb, (bits, c, r)
+        # the knob of the one-lane tests really is what keeps them off these kernels
+        off = _reduce(lib, nb, nw, reduce_quad=0)
+        assert off["chunk"] == "k_reduce_wave" and off["window"] in (None, "k_reduce_window"), (bits, c, off)
+    # a G2 curve without quad_ok (BLS12-381's, BLS12-377's) never takes them
+    for nw, nb in set(QUAD_REDUCE_SHAPES.values()):
+        r = _reduce(lib, nb, nw, quad_ok=False)
+        assert r["chunk"] == "k_reduce_wave" and r["window"] != "k_reduce_window_quad", (nb, nw, r)
+
+
 def test_msm_combine_route_and_accumulate_waves():
     """msm_plan.h msm_combine_route: the host Horner combine exactly for a single MSM without a hook whose result goes to the host or whose
     call is synchronous, with at most 64 windows; else k_final_horner for 64 and more MSMs of two and more windows; else k_final, followed by
