@@ -10,6 +10,6 @@ from .pow import pow_solve, pow_verify  # noqa: F401
 from .fri import FriTranscriptConfig, FriProof, fri_merkle_tree_prove, fri_merkle_tree_verify  # noqa: F401
 from .sumcheck import Symbol, ReturningValueProgram, SumcheckTranscriptConfig, Sumcheck, SumcheckProof  # noqa: F401
 from .program import Program  # noqa: F401
-from .vecops import execute_program, vector_inv, vector_div, vector_sum, vector_product, vector_mixed_mul  # noqa: F401
+from .vecops import execute_program, vector_inv, vector_div, vector_sum, vector_product, vector_mixed_mul, highest_non_zero_idx, poly_eval, poly_division  # noqa: F401
 
-__all__ = ["runtime", "msm", "ntt", "vecops", "hash", "merkle", "fri", "sumcheck", "program", "Symbol", "ReturningValueProgram", "Program", "execute_program", "vector_inv", "vector_div", "vector_sum", "vector_product", "SumcheckConfig", "SumcheckTranscriptConfig", "Sumcheck", "SumcheckProof", "pow_solve", "pow_verify", "FriConfig", "FriTranscriptConfig", "FriProof", "fri_merkle_tree_prove", "fri_merkle_tree_verify", "HashConfig", "MerkleTreeConfig", "PowConfig", "VecOpsConfig", "IcicleError", "Device", "MSMConfig", "NTTConfigU32", "NTTConfigU64", "NTTConfigU256", "NTTInitDomainConfig", "vector_mixed_mul"]
+__all__ = ["runtime", "msm", "ntt", "vecops", "hash", "merkle", "fri", "sumcheck", "program", "Symbol", "ReturningValueProgram", "Program", "execute_program", "vector_inv", "vector_div", "vector_sum", "vector_product", "SumcheckConfig", "SumcheckTranscriptConfig", "Sumcheck", "SumcheckProof", "pow_solve", "pow_verify", "FriConfig", "FriTranscriptConfig", "FriProof", "fri_merkle_tree_prove", "fri_merkle_tree_verify", "HashConfig", "MerkleTreeConfig", "PowConfig", "VecOpsConfig", "IcicleError", "Device", "MSMConfig", "NTTConfigU32", "NTTConfigU64", "NTTConfigU256", "NTTInitDomainConfig", "vector_mixed_mul", "highest_non_zero_idx", "poly_eval", "poly_division"]

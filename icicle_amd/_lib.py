@@ -320,6 +320,8 @@ PROGRAM_FUNCTIONS = ["generate_program", "execute_program"]
 # the extension-field vector operations (src/vec_ops.cpp:24-464, EXT_FIELD), for NTT_FIELDS + [GOLD]: two operands, one operand
 EXT_VEC_OPS_2 = ["vector_add", "vector_sub", "vector_mul", "vector_div", "vector_mixed_mul", "scalar_add_vec", "scalar_sub_vec", "scalar_mul_vec"]
 EXT_VEC_OPS_1 = ["vector_inv", "vector_sum", "vector_product", "bit_reverse"]
+# slice, highest_non_zero_idx, poly_eval, poly_division (src/vec_ops.cpp:472-677), for NTT_FIELDS + BIG_VEC_FIELDS + [GOLD]
+POLY_OPS = ["slice", "highest_non_zero_idx", "poly_eval", "poly_division"]
 API_SYMBOLS = (
     [f"{c}_{s}" for c in CURVES for s in ("msm", "msm_precompute_bases", "hip_generate_affine_points", "hip_projective_sum")]
     + [f"{c}_g2_{s}" for c in G2_CURVES for s in ("msm", "msm_precompute_bases", "hip_generate_affine_points", "hip_projective_sum")]
@@ -337,6 +339,8 @@ API_SYMBOLS = (
        for op in ("vector_add", "vector_sub", "vector_mul", "scalar_mul_vec", "scalar_add_vec", "scalar_sub_vec", "bit_reverse")]
     + [f"{f}_{op}" for f in NTT_FIELDS + BIG_VEC_FIELDS + [GOLD] for op in ("vector_inv", "vector_div", "vector_sum", "vector_product")]
     + ["icicle_hip_vector_inv_tile"]
+    + [f"{f}_{op}" for f in NTT_FIELDS + BIG_VEC_FIELDS + [GOLD] for op in POLY_OPS]
+    + ["icicle_hip_poly_division_tile"]
     + [f"{f}_extension_{op}" for f in NTT_FIELDS + [GOLD] for op in EXT_VEC_OPS_2 + EXT_VEC_OPS_1] + ["icicle_hip_extension_vector_inv_tile"]
     + [f"{pre}{f}_matrix_transpose" for pre in ("", "icicle_hip_") for f in NTT_FIELDS + BIG_VEC_FIELDS + [GOLD]]
     + [f"{pre}{f}_extension_matrix_transpose" for pre in ("", "icicle_hip_") for f in NTT_FIELDS + [GOLD]]
@@ -468,6 +472,14 @@ for _f in NTT_FIELDS + BIG_VEC_FIELDS + [GOLD]:
         getattr(lib, f"{_f}_{_op}").argtypes = [ctypes.c_void_p, ctypes.c_uint64, ctypes.POINTER(VecOpsConfig), ctypes.c_void_p]
     getattr(lib, f"{_f}_vector_div").argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64, ctypes.POINTER(VecOpsConfig), ctypes.c_void_p]
 lib.icicle_hip_vector_inv_tile.argtypes = [ctypes.c_int]
+_slice_args = [ctypes.c_void_p, ctypes.c_uint64, ctypes.c_uint64, ctypes.c_uint64, ctypes.c_uint64, ctypes.POINTER(VecOpsConfig), ctypes.c_void_p]
+for _f in NTT_FIELDS + BIG_VEC_FIELDS + [GOLD]:
+    getattr(lib, f"{_f}_slice").argtypes = _slice_args
+    getattr(lib, f"{_f}_highest_non_zero_idx").argtypes = [ctypes.c_void_p, ctypes.c_uint64, ctypes.POINTER(VecOpsConfig), ctypes.c_void_p]
+    getattr(lib, f"{_f}_poly_eval").argtypes = [ctypes.c_void_p, ctypes.c_uint64, ctypes.c_void_p, ctypes.c_uint64, ctypes.POINTER(VecOpsConfig), ctypes.c_void_p]
+    getattr(lib, f"{_f}_poly_division").argtypes = [ctypes.c_void_p, ctypes.c_uint64, ctypes.c_void_p, ctypes.c_int64, ctypes.POINTER(VecOpsConfig), ctypes.c_void_p,
+                                                    ctypes.c_uint64, ctypes.c_void_p, ctypes.c_uint64]
+lib.icicle_hip_poly_division_tile.argtypes = [ctypes.c_int]
 for _f in NTT_FIELDS + [GOLD]:
     for _op in EXT_VEC_OPS_2:
         getattr(lib, f"{_f}_extension_{_op}").argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64, ctypes.POINTER(VecOpsConfig), ctypes.c_void_p]

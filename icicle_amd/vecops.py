@@ -202,3 +202,110 @@ def execute_program(field, data, program, cfg=None, size=None):
     table = (ctypes.c_void_p * len(ptrs))(*[p for p, _ in ptrs])
     check(getattr(lib, f"{field}_execute_program")(table, len(ptrs), program.handle, size, ctypes.byref(cfg)), f"{field}_execute_program")
     return data
+
+
+# ---- slice, highest_non_zero_idx, poly_eval, poly_division (src/vec_ops.cpp:472-677): what the reference's polynomial API is built from ----
+def _elements(x, words, what):
+    assert not isinstance(x, int), f"a raw device address has no size: pass {what}"
+    return x.nbytes // (4 * words)
+
+
+def slice(field, inp, offset, stride, size_out, cfg=None, out=None, size_in=None):
+    """out[k][i] = inp[k][offset + i * stride], i < size_out, per batch entry of `size_in` elements; inp and out must not overlap"""
+    sym = f"{field}_slice"
+    words = _WORDS[field]
+    cfg = cfg or VecOpsConfig.default()
+    ip, cfg.is_a_on_device = _ptr(inp)
+    batch = max(1, cfg.batch_size)
+    if size_in is None:
+        size_in = _elements(inp, words, "size_in") // batch
+    if out is None:
+        out = np.zeros((size_out * batch, words), np.uint32)
+    op_, cfg.is_result_on_device = _ptr(out)
+    check(getattr(lib, sym)(ip, offset, stride, size_in, size_out, ctypes.byref(cfg), op_), sym)
+    return out
+
+
+def highest_non_zero_idx(field, a, cfg=None, size=None, out=None):
+    """per batch entry the largest index of a non-zero element, -1 for a zero vector: an int64 array of batch_size values
+    (`out`: a DeviceVec or device address of batch_size int64 to keep the result on the device)"""
+    sym = f"{field}_highest_non_zero_idx"
+    cfg = cfg or VecOpsConfig.default()
+    ap, cfg.is_a_on_device = _ptr(a)
+    batch = max(1, cfg.batch_size)
+    if size is None:
+        size = _elements(a, _WORDS[field], "size") // batch
+    if out is None:
+        out = np.full(batch, -2, np.int64)
+    if isinstance(out, np.ndarray):
+        assert out.dtype == np.int64 and out.flags["C_CONTIGUOUS"]
+        op_, cfg.is_result_on_device = out.ctypes.data, False
+    else:
+        op_, cfg.is_result_on_device = _ptr(out)
+    check(getattr(lib, sym)(ap, size, ctypes.byref(cfg), op_), sym)
+    return out
+
+
+def poly_eval(field, coeffs, domain, cfg=None, out=None, coeffs_size=None, chunk=0, domain_size=None):
+    """out[k][e] = P_k(domain[e]): coefficients per batch entry (constant term first), one domain shared by the entries.
+    chunk: 0 = the library picks the route, > 0 = the chunk route with that chunk length, -1 = one lane per (entry, point)"""
+    sym = f"{field}_poly_eval"
+    words = _WORDS[field]
+    cfg = cfg or VecOpsConfig.default()
+    cp, cfg.is_a_on_device = _ptr(coeffs)
+    dp, cfg.is_b_on_device = _ptr(domain)
+    batch = max(1, cfg.batch_size)
+    if coeffs_size is None:
+        coeffs_size = _elements(coeffs, words, "coeffs_size") // batch
+    if domain_size is None:
+        domain_size = _elements(domain, words, "domain_size")
+    if out is None:
+        out = np.zeros((domain_size * batch, words), np.uint32)
+    op_, cfg.is_result_on_device = _ptr(out)
+    ext, saved = None, cfg.ext
+    if chunk:
+        ext = lib.clone_config_extension(saved) if saved else lib.create_config_extension()
+        lib.config_extension_set_int(ext, b"hip_poly_eval_chunk", chunk)
+        cfg.ext = ext
+    try:
+        check(getattr(lib, sym)(cp, coeffs_size, dp, domain_size, ctypes.byref(cfg), op_), sym)
+    finally:
+        if ext:
+            cfg.ext = saved
+            lib.destroy_config_extension(ext)
+    return out
+
+
+def poly_division(field, num, den, cfg=None, q_size=None, r_size=None, q_out=None, r_out=None, num_size=None, den_size=None):
+    """(q, r) with num = q * den + r per batch entry; q has q_size and r has r_size elements per entry, zero above their degrees.
+    Defaults: r_size = the numerator's size, q_size = max(1, numerator size - denominator size + 1) -- enough when the
+    denominator's buffer has no trailing zeros; pass q_size otherwise. The outputs may not overlap the inputs."""
+    sym = f"{field}_poly_division"
+    words = _WORDS[field]
+    cfg = cfg or VecOpsConfig.default()
+    np_, cfg.is_a_on_device = _ptr(num)
+    dp, cfg.is_b_on_device = _ptr(den)
+    batch = max(1, cfg.batch_size)
+    if num_size is None:
+        num_size = _elements(num, words, "num_size") // batch
+    if den_size is None:
+        den_size = _elements(den, words, "den_size") // batch
+    if r_size is None:
+        r_size = num_size
+    if q_size is None:
+        q_size = max(1, num_size - den_size + 1)
+    if q_out is None:
+        q_out = np.zeros((q_size * batch, words), np.uint32)
+    if r_out is None:
+        r_out = np.zeros((r_size * batch, words), np.uint32)
+    qp, q_dev = _ptr(q_out)
+    rp, r_dev = _ptr(r_out)
+    assert q_dev == r_dev, "q_out and r_out must both be on the host or both on the device"
+    cfg.is_result_on_device = q_dev
+    check(getattr(lib, sym)(np_, num_size, dp, den_size, ctypes.byref(cfg), qp, q_size, rp, r_size), sym)
+    return q_out, r_out
+
+
+def poly_division_tile(field) -> int:
+    """how many quotient coefficients of `field` poly_division produces per pair of launches"""
+    return lib.icicle_hip_poly_division_tile(_WORDS[field])

@@ -329,6 +329,48 @@ ICICLE_HIP_DECLARE_VEC_EXT(goldilocks)
 /* elements whose norms share one inversion, by the words of a BASE-field element (1 or 2); 0 for anything else. Needs no device. */
 int icicle_hip_extension_vector_inv_tile(int base_words_per_element);
 
+/* slice, highest_non_zero_idx, poly_eval and poly_division: what the reference's polynomial API is built from, for the eight fields
+ * above (src/vec_ops.cpp:472 slice, :549 highest_non_zero_idx, :621 poly_eval, :648 poly_division; CPU backend
+ * backend/cpu/src/field/cpu_vec_ops.cpp:566-624, 682-780). Elements are canonical words in and out. Every size is per batch entry:
+ * entry k holds its element j at k * size + j, or at j * batch_size + k with columns_batch. stream, is_async and the three
+ * is_*_on_device flags are honoured as vector_div honours them. Arguments are checked before the device is touched, in vector_inv's
+ * order: NULL config gives ICICLE_INVALID_POINTER, then the empty call named below ICICLE_SUCCESS, then a NULL vector
+ * ICICLE_INVALID_POINTER, then everything else ICICLE_INVALID_ARGUMENT.
+ *  - slice: output[k][i] = input[k][offset + i * stride], i < size_out. size_out == 0 is the empty call.
+ *    offset + (size_out - 1) * stride >= size_in is an error (where the reference asserts), also with stride == 0. Input and output
+ *    must not overlap: an overlap of two buffers on the same side (host or device) is an error, nothing is written.
+ *  - highest_non_zero_idx: out_idx[k] = the largest j whose element has a non-zero word, -1 for a zero vector; batch_size int64_t
+ *    values, on the device with is_result_on_device. size == 0 is an error. A maximum of integers: the same on every run.
+ *  - poly_eval: evals[k][e] = P_k(domain[e]). The domain is shared by the entries and contiguous; coeffs (is_a_on_device) and evals
+ *    (is_result_on_device) follow columns_batch; is_b_on_device is the domain's. coeffs_size == 0 or domain_size == 0 is an error.
+ *    evals must overlap neither input. Two routes with the same bytes out: one lane per (entry, point), or -- few points, many
+ *    coefficients -- one wave per chunk of coefficients and further launches over the chunk values. config.ext int
+ *    "hip_poly_eval_chunk": absent or 0 the plan decides (csrc/poly_plan.h), positive the chunk route with that chunk length (1 is
+ *    taken as 2), -1 the point route, any other negative value is an error.
+ *  - poly_division: numerator = q * denominator + r per entry. q_out gets q_size elements per entry and r_out r_size, both written in
+ *    full, zero above the quotient's and the remainder's degree. With deg = highest_non_zero_idx: a zero denominator in any entry,
+ *    r_size < deg_n + 1, and q_size < deg_n - deg_b + 1 where that is positive are errors, and nothing is written. deg_n < deg_b gives
+ *    q = 0 and r = numerator; a zero numerator gives zeros. The outputs may overlap neither the inputs nor each other.
+ *    is_a_on_device is the numerator's, is_b_on_device the denominator's, is_result_on_device covers q_out and r_out. The call
+ *    synchronises the stream once, to read the degrees. The quotient is produced from the top in tiles of
+ *    icicle_hip_poly_division_tile(words) coefficients, two launches per tile. */
+#define ICICLE_HIP_DECLARE_VEC_POLY(F)                                                                                 \
+  icicle_error_t F##_slice(const void* input, uint64_t offset, uint64_t stride, uint64_t size_in, uint64_t size_out, const icicle_vec_ops_config_t* config, void* output); \
+  icicle_error_t F##_highest_non_zero_idx(const void* input, uint64_t size, const icicle_vec_ops_config_t* config, int64_t* out_idx); \
+  icicle_error_t F##_poly_eval(const void* coeffs, uint64_t coeffs_size, const void* domain, uint64_t domain_size, const icicle_vec_ops_config_t* config, void* evals); \
+  icicle_error_t F##_poly_division(const void* numerator, uint64_t numerator_size, const void* denominator, int64_t denominator_size, const icicle_vec_ops_config_t* config, \
+                                   void* q_out, uint64_t q_size, void* r_out, uint64_t r_size);
+ICICLE_HIP_DECLARE_VEC_POLY(babybear)
+ICICLE_HIP_DECLARE_VEC_POLY(koalabear)
+ICICLE_HIP_DECLARE_VEC_POLY(goldilocks)
+ICICLE_HIP_DECLARE_VEC_POLY(bn254)
+ICICLE_HIP_DECLARE_VEC_POLY(bls12_381)
+ICICLE_HIP_DECLARE_VEC_POLY(bls12_377)
+ICICLE_HIP_DECLARE_VEC_POLY(stark252)
+ICICLE_HIP_DECLARE_VEC_POLY(grumpkin)
+/* quotient coefficients per tile of poly_division, for elements of 1, 2 or 8 words; 0 for any other width. Needs no device. */
+int icicle_hip_poly_division_tile(int words_per_element);
+
 /* Matrix transpose of batch_size row-major nof_rows x nof_cols matrices (icicle/src/matrix_ops.cpp:75-102,
  * include/icicle/vec_ops.h:319; CPU: backend/cpu/src/field/cpu_matrix_ops.cpp:333-362): in place allowed, columns_batch
  * rejected. The Rust NTT suite calls it on the main device around every columns_batch transform
