@@ -1,5 +1,5 @@
 // The FRI protocol over any field kind: the proof object, the prover and the verifier of the reference's C ABI
-// (src/fri/fri_c_api.cpp), composed from what hash.hip provides -- the query phase and the verifier on its batched openings and
+// (src/fri/fri_c_api.cpp), composed from what hash.hip and merkle.hip provide -- the query phase and the verifier on its batched openings and
 // verification, one call per round --, and the macro that defines a prefix's entry points. Included by
 // fri.hip (the 31-bit fields) and fri_wide.hip (Goldilocks, the 256-bit fields), which supply the field kind K:
 //
@@ -53,7 +53,7 @@ namespace icicle_hip {
   }
 
   // ---- the proof object -----------------------------------------------------------------------------------------------------------
-  // slots[q][r]: Merkle proofs owned by the FRI proof (handles of hash.hip's proof type, so icicle_merkle_proof_get_* read them)
+  // slots[q][r]: Merkle proofs owned by the FRI proof (handles of merkle.hip's proof type, so icicle_merkle_proof_get_* read them)
   struct FriProofObj {
     std::vector<std::vector<icicle_merkle_proof_handle_t>> slots;
     std::vector<uint32_t> final_poly; // the elements' words back to back (K::WORDS per element)

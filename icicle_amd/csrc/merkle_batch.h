@@ -1,8 +1,10 @@
-// Index arithmetic of batched Merkle openings (icicle_hip_merkle_tree_get_proofs, hash.hip): leaf index -> per layer the on-path
-// node, the group's offset in the layer, the on-path digest's offset in the group, the group's place in the path (pruned or not) and
-// its offset inside a re-hashed sub-tree; and the layout of the staging record one proof's pieces are gathered into. Written once
-// for the host and the device: the gather kernel, the host's unpacking and tests/merkle_batch_harness.cpp call this code, and the
-// harness holds it against merkle_proof_plan (merkle_plan.h) for every index. No HIP in here beyond the function qualifier.
+// Index arithmetic of Merkle openings (icicle_merkle_tree_get_proof, icicle_hip_merkle_tree_get_proofs, merkle.hip), the only one in
+// the product: leaf index -> per layer the on-path node, the group's offset in the layer, the on-path digest's offset in the group,
+// the group's place in the path (pruned or not) and its offset inside a re-hashed sub-tree; and the layout of the staging record one
+// proof's pieces are gathered into. Written once for the host and the device: the gather kernel, the host's unpacking and the CPU
+// harnesses call this code. tests/merkle_batch_harness.cpp holds it against the plain loop form of the walk, which it carries as
+// test-only reference code, for every index; tests/merkle_plan_harness.cpp hands it to the Python model (tests/merkle_model.py).
+// No HIP in here beyond the function qualifier.
 #pragma once
 #include "merkle_plan.h"
 
@@ -51,7 +53,8 @@ namespace icicle_hip {
     s->stride = s->last_at + merkle_batch_pad16(s->es);
   }
 
-  // the layer-0 chunk that holds element leaf_idx; false: the index lies at or beyond the capacity (merkle_proof_plan's rule)
+  // the layer-0 chunk that holds element leaf_idx (the proof's leaf is this whole chunk); false: leaf_idx * leaf_element_size lies
+  // at or beyond the capacity
   MERKLE_HD bool merkle_batch_chunk0(const MerkleBatchShape& s, uint64_t leaf_idx, uint64_t* chunk0)
   {
     if (leaf_idx >= s.capacity / s.es + 1) return false;
@@ -61,8 +64,14 @@ namespace icicle_hip {
     return true;
   }
 
+  // One layer's share of a proof's path (cpu_merkle_tree.cpp:546-573): the a_{i+1} digests of layer i that form the one input of
+  // layer i + 1 on the way from the leaf to the root. Pruned, the digest ON the way is left out (verify recomputes it).
   struct MerkleBatchStep {
-    uint64_t node = 0, src_off = 0, len = 0, skip_off = 0, dst_off = 0; // as MerkleProofStep
+    uint64_t node = 0;     // index of the on-path digest in layer i
+    uint64_t src_off = 0;  // byte offset of the group in layer i's digests
+    uint64_t len = 0;      // c_{i+1}
+    uint64_t skip_off = 0; // byte offset of the on-path digest inside the group
+    uint64_t dst_off = 0;  // where the group starts in the path
     // a layer below store_min: the group's offset among the nodes of this layer under the on-path node of layer store_min, which
     // is where it lies in the re-hashed sub-tree; src_off for the stored layers
     uint64_t sub_off = 0;

@@ -1,6 +1,7 @@
-// Host-only arithmetic of the Merkle tree (hash.hip): layer counts, padding extents, the sub-tree a proof recomputes and the
-// byte offsets of a proof's path. No HIP in here, so tests/merkle_plan_harness.cpp compiles it with g++ and compares it with
-// the Python model (tests/merkle_model.py). The same arithmetic for batched openings, as one host-and-device function, is merkle_batch.h.
+// Host-only arithmetic of the Merkle tree (merkle.hip): layer counts, padding extents and the offsets verify() walks. No HIP in
+// here, so tests/merkle_plan_harness.cpp compiles it with g++ and compares it with the Python model (tests/merkle_model.py).
+// The leaf-index arithmetic of an opening -- the byte offsets of a proof's path, the sub-tree a proof recomputes --, as one
+// host-and-device function, is merkle_batch.h.
 //
 // Notation (reference: icicle/backend/cpu/src/hash/cpu_merkle_tree.cpp:18-51): layer i hashes n_i chunks of c_i bytes into
 // digests of o_i bytes; c_{i+1} % o_i == 0 ("each layer output size must divide the next layer input size"), the arity of
@@ -86,53 +87,6 @@ namespace icicle_hip {
     }
     out->full_chunks = leaves_size / p.layers[0].chunk;
     out->pad_bytes = p.capacity - leaves_size;
-    return 0;
-  }
-
-  // One layer's share of a proof's path (cpu_merkle_tree.cpp:546-573): the a_{i+1} digests of layer i that form the one input
-  // of layer i + 1 on the way from the leaf to the root. Pruned, the digest ON the way is left out (verify recomputes it).
-  struct MerkleProofStep {
-    uint64_t node = 0;     // index of the on-path digest in layer i
-    uint64_t src_off = 0;  // byte offset of the group in layer i's digests
-    uint64_t len = 0;      // c_{i+1}
-    uint64_t skip_off = 0; // byte offset of the on-path digest inside the group
-    uint64_t dst_off = 0;  // where the group starts in the path
-  };
-  struct MerkleProofPlan {
-    uint64_t chunk0 = 0;           // the layer-0 chunk that holds the element; the proof's leaf is this whole chunk
-    std::vector<MerkleProofStep> steps; // layers 0 .. L-2
-    uint64_t path_size = 0;
-    // layers below output_store_min_layer are not kept: the proof re-hashes the sub-tree under the on-path node of layer
-    // store_min -- layer-0 chunks [sub_first, sub_first + sub_count), and n_i / n_store_min nodes of every layer i below it,
-    // the first of them node sub_first * n_i / n_0
-    uint64_t sub_first = 0, sub_count = 0;
-  };
-  // 0 = fine, 1 = leaf_idx * leaf_element_size lies at or beyond the capacity
-  inline int merkle_proof_plan(const MerklePlan& p, uint64_t leaf_idx, bool pruned, int store_min, MerkleProofPlan* out)
-  {
-    const int L = p.L();
-    if (leaf_idx >= p.capacity / p.leaf_element_size + 1) return 1;
-    const uint64_t byte0 = leaf_idx * p.leaf_element_size;
-    if (byte0 >= p.capacity) return 1;
-    out->chunk0 = byte0 / p.layers[0].chunk;
-    out->steps.assign(L > 0 ? L - 1 : 0, MerkleProofStep{});
-    uint64_t node = out->chunk0, dst = 0;
-    for (int i = 0; i + 1 < L; i++) {
-      const uint64_t a = p.arity(i + 1), o = p.layers[i].out;
-      MerkleProofStep& s = out->steps[i];
-      s.node = node;
-      s.src_off = (node / a) * a * o;
-      s.len = p.layers[i + 1].chunk;
-      s.skip_off = (node % a) * o;
-      s.dst_off = dst;
-      dst += pruned ? s.len - o : s.len;
-      node /= a;
-    }
-    out->path_size = dst;
-    if (store_min < 0) store_min = 0;
-    if (store_min > L - 1) store_min = L - 1;
-    out->sub_count = p.layers[0].count / p.layers[store_min].count;
-    out->sub_first = (out->chunk0 / out->sub_count) * out->sub_count;
     return 0;
   }
 

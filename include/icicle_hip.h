@@ -473,7 +473,7 @@ icicle_error_t icicle_hasher_delete(icicle_hasher_handle_t h); /* :52 */
 /* Layer i hashes n_i inputs of c_i bytes (its hasher's chunk size) into digests of o_i bytes: c_{i+1} % o_i == 0 is required
  * (NULL otherwise), n_{L-1} = 1, n_{i-1} = n_i * c_i / o_{i-1}, the tree takes n_0 * c_0 bytes of leaves. The tree copies the
  * hashers. Layers >= output_store_min_layer are kept (device or pinned host memory per is_tree_on_device), lower ones are
- * freed after the build and re-hashed, one sub-tree, by get_proof from the caller's leaves. */
+ * freed after the build and re-hashed, one sub-tree per opening (get_proofs: per distinct sub-tree), from the caller's leaves. */
 icicle_merkle_tree_handle_t icicle_merkle_tree_create(const icicle_hasher_handle_t* layer_hashes, size_t layer_hashes_len, uint64_t leaf_element_size,
                                                       uint64_t output_store_min_layer); /* merkle_c_api.cpp:75 */
 icicle_error_t icicle_merkle_tree_delete(icicle_merkle_tree_handle_t tree);             /* :103 */
@@ -487,10 +487,11 @@ const uint8_t* icicle_merkle_tree_get_root(icicle_merkle_tree_handle_t tree, siz
 /* Proof for element leaf_idx (cpu_merkle_tree.cpp:143-211,546-573): leaf = the whole layer-0 chunk around the element, padded per
  * policy; path = for layers 0 .. L-2 the c_{i+1} bytes of layer-i digests that form the on-path input of layer i+1 (pruned: without
  * the on-path digest itself). leaf_idx * leaf_element_size beyond the capacity, or a tree not built: INVALID_ARGUMENT. Synchronises
- * config->stream once. */
+ * config->stream once. This is icicle_hip_merkle_tree_get_proofs (below) with count == 1: the same code, refusals and bytes. */
 icicle_error_t icicle_merkle_tree_get_proof(icicle_merkle_tree_handle_t tree, const uint8_t* leaves, uint64_t leaves_size, uint64_t leaf_idx, bool is_pruned,
                                             const icicle_merkle_tree_config_t* config, icicle_merkle_proof_handle_t merkle_proof); /* :138 */
-/* include/icicle/merkle/merkle_tree.h:148-203, one hash per layer on the device */
+/* include/icicle/merkle/merkle_tree.h:148-203, one hash per layer on the device: icicle_hip_merkle_tree_verify_batch (below) with
+ * count == 1, the same code, refusals and verdict */
 icicle_error_t icicle_merkle_tree_verify(icicle_merkle_tree_handle_t tree, icicle_merkle_proof_handle_t merkle_proof, bool* valid); /* :157 */
 icicle_merkle_proof_handle_t icicle_merkle_proof_create(void); /* :12 */
 icicle_merkle_proof_handle_t icicle_merkle_proof_create_with_data(bool pruned_path, int64_t leaf_idx, const uint8_t* leaf, size_t leaf_size, const uint8_t* root,
@@ -501,7 +502,8 @@ const uint8_t* icicle_merkle_proof_get_path(icicle_merkle_proof_handle_t proof, 
 const uint8_t* icicle_merkle_proof_get_leaf(icicle_merkle_proof_handle_t proof, size_t* out_size, uint64_t* out_leaf_idx); /* :56 */
 const uint8_t* icicle_merkle_proof_get_root(icicle_merkle_proof_handle_t proof, size_t* out_size); /* :66 */
 
-/* ---- this backend's own: many openings, many verifications per call (the reference has no such call) ----
+/* ---- this backend's own: many openings, many verifications per call (the reference has no such call). The single calls above are
+ * these two with count == 1; there is one implementation of each. ----
  * get_proofs: proofs[i] comes out byte for byte as icicle_merkle_tree_get_proof(tree, leaves, leaves_size, leaf_indices[i], is_pruned,
  * config, proofs[i]) leaves it, for every configuration that call accepts. leaf_indices is a host array, in any order, repeats
  * allowed; proofs are `count` handles of icicle_merkle_proof_create. With the stored layers in device memory ONE kernel gathers the
@@ -516,9 +518,9 @@ icicle_error_t icicle_hip_merkle_tree_get_proofs(icicle_merkle_tree_handle_t tre
                                                  bool is_pruned, const icicle_merkle_tree_config_t* config, icicle_merkle_proof_handle_t* proofs);
 /* valid[i] = what icicle_merkle_tree_verify(tree, proofs[i], &v) would set. One upload of all proofs' layer inputs, one hash launch
  * per layer over all proofs (layer 0: one per distinct leaf size), pruned proofs' digests scattered into the next layer's inputs by
- * one launch per layer, one copy back, one synchronisation (the null stream, as the single call); the comparisons run on the host.
- * All proofs share one pruned flag: a mix is INVALID_ARGUMENT. Where the single call returns an error for some proof (an empty leaf,
- * a path of the wrong size, leaf_idx * leaf_element_size beyond 64 bits) the batch returns the first such error in index order and
+ * one launch per layer, one copy back, one synchronisation (the null stream); the comparisons run on the host.
+ * All proofs share one pruned flag: a mix is INVALID_ARGUMENT. Where some proof is refused (an empty leaf, a path of the wrong
+ * size, leaf_idx * leaf_element_size beyond 64 bits: INVALID_ARGUMENT) the call returns the first such error in index order and
  * every valid[i] is false. A root of the wrong size makes that one proof invalid. NULL tree, proofs, valid or proofs[i]:
  * INVALID_POINTER. count == 0: SUCCESS. The tree need not be built. */
 icicle_error_t icicle_hip_merkle_tree_verify_batch(icicle_merkle_tree_handle_t tree, const icicle_merkle_proof_handle_t* proofs, uint64_t count, bool* valid);

@@ -1,12 +1,61 @@
 // Test infrastructure: a stand-alone program over icicle_amd/csrc/merkle_batch.h (no HIP), compiled with g++ by
 // tests/test_merkle_batch_cpu.py -- once plainly and once with -fsanitize=address,undefined. It holds the index function the gather
-// kernel and the host's unpacking share against merkle_proof_plan (merkle_plan.h) for EVERY leaf index of small trees, pruned and
-// full, for every choice of the first stored layer, and checks the staging record: pieces in order, 16-aligned, without overlap,
-// covering the stride, and found again by merkle_batch_piece from every byte offset. Prints one line per tree and "ok <trees>".
+// kernel and the host's unpacking share -- the product's only leaf-index arithmetic -- against the straightforward loop form of
+// the same walk (ref_proof_plan below, test-only reference code) for EVERY leaf index of small trees, pruned and full, for every
+// choice of the first stored layer, and checks the staging record: pieces in order, 16-aligned, without overlap, covering the
+// stride, and found again by merkle_batch_piece from every byte offset. Prints one line per tree and "ok <trees>".
 #include "../icicle_amd/csrc/merkle_batch.h"
 #include <cstdio>
 #include <cstdlib>
 using namespace icicle_hip;
+
+// ---- the reference: one walk from the leaf to the root over the MerklePlan, all layers at once --------------------------------------
+// One layer's share of a proof's path (reference: icicle/backend/cpu/src/hash/cpu_merkle_tree.cpp:546-573): the a_{i+1} digests of
+// layer i that form the one input of layer i + 1 on the way from the leaf to the root. Pruned, the digest ON the way is left out.
+struct RefProofStep {
+  uint64_t node = 0;     // index of the on-path digest in layer i
+  uint64_t src_off = 0;  // byte offset of the group in layer i's digests
+  uint64_t len = 0;      // c_{i+1}
+  uint64_t skip_off = 0; // byte offset of the on-path digest inside the group
+  uint64_t dst_off = 0;  // where the group starts in the path
+};
+struct RefProofPlan {
+  uint64_t chunk0 = 0;             // the layer-0 chunk that holds the element; the proof's leaf is this whole chunk
+  std::vector<RefProofStep> steps; // layers 0 .. L-2
+  uint64_t path_size = 0;
+  // layers below output_store_min_layer are not kept: the proof re-hashes the sub-tree under the on-path node of layer
+  // store_min -- layer-0 chunks [sub_first, sub_first + sub_count), and n_i / n_store_min nodes of every layer i below it,
+  // the first of them node sub_first * n_i / n_0
+  uint64_t sub_first = 0, sub_count = 0;
+};
+// 0 = fine, 1 = leaf_idx * leaf_element_size lies at or beyond the capacity
+static int ref_proof_plan(const MerklePlan& p, uint64_t leaf_idx, bool pruned, int store_min, RefProofPlan* out)
+{
+  const int L = p.L();
+  if (leaf_idx >= p.capacity / p.leaf_element_size + 1) return 1;
+  const uint64_t byte0 = leaf_idx * p.leaf_element_size;
+  if (byte0 >= p.capacity) return 1;
+  out->chunk0 = byte0 / p.layers[0].chunk;
+  out->steps.assign(L > 0 ? L - 1 : 0, RefProofStep{});
+  uint64_t node = out->chunk0, dst = 0;
+  for (int i = 0; i + 1 < L; i++) {
+    const uint64_t a = p.arity(i + 1), o = p.layers[i].out;
+    RefProofStep& s = out->steps[i];
+    s.node = node;
+    s.src_off = (node / a) * a * o;
+    s.len = p.layers[i + 1].chunk;
+    s.skip_off = (node % a) * o;
+    s.dst_off = dst;
+    dst += pruned ? s.len - o : s.len;
+    node /= a;
+  }
+  out->path_size = dst;
+  if (store_min < 0) store_min = 0;
+  if (store_min > L - 1) store_min = L - 1;
+  out->sub_count = p.layers[0].count / p.layers[store_min].count;
+  out->sub_first = (out->chunk0 / out->sub_count) * out->sub_count;
+  return 0;
+}
 
 static int g_failures = 0;
 #define CHECK(cond, ...)                                                                                               \
@@ -70,8 +119,8 @@ static uint64_t check_tree(const std::vector<uint64_t>& chunk, const std::vector
       CHECK(merkle_batch_path_size(s) == (pruned ? p.pruned_path : p.full_path), "path size");
       // every index the tree has, and a few it has not
       for (uint64_t idx = 0; idx <= p.capacity / es + 2; idx++) {
-        MerkleProofPlan pp;
-        const int refused = merkle_proof_plan(p, idx, pruned != 0, store_min, &pp);
+        RefProofPlan pp;
+        const int refused = ref_proof_plan(p, idx, pruned != 0, store_min, &pp);
         uint64_t chunk0 = ~0ull;
         const bool ok = merkle_batch_chunk0(s, idx, &chunk0);
         CHECK(ok == !refused, "index %llu: accepted %d, plan refuses %d", (unsigned long long)idx, ok, refused);
@@ -85,11 +134,11 @@ static uint64_t check_tree(const std::vector<uint64_t>& chunk, const std::vector
         for (int l = 0; l + 1 < L; l++) {
           MerkleBatchStep st;
           merkle_batch_step(s, chunk0, l, &st);
-          const MerkleProofStep& w = pp.steps[l];
+          const RefProofStep& w = pp.steps[l];
           CHECK(st.node == w.node && st.src_off == w.src_off && st.len == w.len && st.skip_off == w.skip_off && st.dst_off == w.dst_off, "index %llu layer %d pruned %d",
                 (unsigned long long)idx, l, pruned);
-          // where the group lies in the re-hashed sub-tree: relative to the layer's first node under the sub-tree's root, as tree_proof
-          // computes it (sub_first / (layer-0 chunks per node of the layer)); the whole group inside the sub-tree's share of the layer
+          // where the group lies in the re-hashed sub-tree: relative to the layer's first node under the sub-tree's root, i.e.
+          // node sub_first / (layer-0 chunks per node of the layer); the whole group inside the sub-tree's share of the layer
           const int m = s.store_min;
           if (l < m) {
             const uint64_t ratio = p.layers[0].count / p.layers[l].count, node0 = pp.sub_first / ratio, nodes = pp.sub_count / ratio;

@@ -1,6 +1,7 @@
-// Host check of the Merkle tree arithmetic (icicle_amd/csrc/merkle_plan.h): a flat C surface that tests/test_hash_cpu.py compares
-// with the Python model (tests/merkle_model.py). With -DMERKLE_PLAN_MAIN it is a stand-alone program that walks a few shapes.
-#include "../icicle_amd/csrc/merkle_plan.h"
+// Host check of the Merkle tree arithmetic (icicle_amd/csrc/merkle_plan.h, and the leaf-index arithmetic of merkle_batch.h): a flat
+// C surface that tests/test_hash_cpu.py compares with the Python model (tests/merkle_model.py). With -DMERKLE_PLAN_MAIN it is a
+// stand-alone program that walks a few shapes.
+#include "../icicle_amd/csrc/merkle_batch.h"
 #include <cstdio>
 using namespace icicle_hip;
 
@@ -32,12 +33,17 @@ extern "C" int mp_proof(const uint64_t* chunk, const uint64_t* outsz, int L, uin
 {
   MerklePlan p;
   if (!merkle_make_plan(chunk, outsz, L, es, &p)) return 2;
-  MerkleProofPlan pp;
-  if (merkle_proof_plan(p, leaf_idx, pruned != 0, store_min, &pp)) return 1;
-  out[0] = pp.chunk0, out[1] = pp.path_size, out[2] = pp.sub_first, out[3] = pp.sub_count;
+  MerkleBatchShape sh;
+  merkle_batch_shape(p, pruned != 0, store_min, &sh);
+  if (!merkle_batch_chunk0(sh, leaf_idx, &out[0])) return 1;
+  out[1] = merkle_batch_path_size(sh);
+  merkle_batch_subtree(sh, out[0], &out[2], &out[3]);
   uint64_t* o = out + 4;
-  for (const MerkleProofStep& s : pp.steps)
+  for (int l = 0; l < sh.steps; l++) {
+    MerkleBatchStep s;
+    merkle_batch_step(sh, out[0], l, &s);
     *o++ = s.node, *o++ = s.src_off, *o++ = s.len, *o++ = s.skip_off, *o++ = s.dst_off;
+  }
   std::vector<uint64_t> offs;
   merkle_verify_offsets(p, leaf_idx, p.layers[0].chunk, &offs);
   for (uint64_t v : offs)

@@ -1,7 +1,8 @@
-"""GPU: batched Merkle openings and verification (icicle_hip_merkle_tree_get_proofs / _verify_batch) against the single calls field by
-field (leaf, leaf_idx, path, root, pruned) and, for the Keccak trees, against the model (tests/merkle_model.py): chunks of one and of
-four elements, an arity-4 layer, Keccak-512 and Blake2s layers in one tree; one layer (an empty path), two layers, 2^6 and 2^10
-leaf chunks; single indices, every index, 300 unsorted indices with repeats; the padded tail under both policies; host and device
+"""GPU: batched Merkle openings and verification (icicle_hip_merkle_tree_get_proofs / _verify_batch) against the model of all six
+hashers (tests/blake_model.py) field by field (leaf, leaf_idx, path, root, pruned) for every index opened and every verdict -- the
+single calls are the same code with count == 1, so they are no oracle --, and the single calls against the batch of one at the C ABI
+on the smallest shapes that reach each branch: chunks of one and of four elements, an arity-4 layer, Keccak-512 and Blake2s layers
+in one tree; one layer (an empty path), two layers, 2^6 and 2^10 leaf chunks; single indices, every index, 300 unsorted indices with repeats; the padded tail under both policies; host and device
 leaves, leaves off a 16-byte boundary, a tree in pinned memory, layers below the first stored one re-hashed for 1, 2 and many
 sub-trees; refusals that leave the proofs empty; a stream of its own; and verify_batch for all six hashers with one bit flipped
 in one proof at a time."""
@@ -10,6 +11,7 @@ import ctypes
 import numpy as np
 import pytest
 
+from tests import blake_model as bm
 from tests import merkle_model as mm
 
 pytestmark = pytest.mark.gpu
@@ -74,22 +76,29 @@ def fields(p):
     return p.leaf, p.leaf_idx, p.path, p.root, p.pruned
 
 
-def check_against_single_calls(tree, arg, size, indices, pruned, cfg, model=None):
-    """the batch equals one single call per index; model: (shape, leaves bytes, policy) of a Keccak tree"""
+def model_of(layers, leaves, policy=mm.PAD_NONE, es=ES):
+    """(shape, leaves bytes, policy) as check_against_model takes it; the model's build of the tree is cached"""
+    return bm.TreeShape(layers, es), leaves.tobytes(), policy
+
+
+def check_against_model(tree, arg, size, indices, pruned, cfg, model):
+    """every proof of the batch equals the model's proof for its index; model: (shape, leaves bytes, policy)"""
     got = tree.proofs(arg, indices, pruned, cfg, size=size)
     assert len(got) == len(indices)
-    single = {}
+    shape, leaves, policy = model
+    want = {}
     for i, pr in zip(indices, got):
-        if i not in single:
-            single[i] = fields(tree.proof(arg, i, pruned, cfg, size=size))
-        assert fields(pr) == single[i], (i, pruned)
-        assert pr.leaf_idx == i and pr.pruned == pruned
-    if model is not None:
-        shape, leaves, policy = model
-        for i in list(single)[:40]:
-            leaf, path, root = mm.proof(shape, leaves, i, pruned, policy)
-            assert single[i] == (leaf, i, path, root, pruned), ("model", i)
+        if i not in want:
+            leaf, path, root = bm.proof(shape, leaves, i, pruned, policy)
+            want[i] = (leaf, i, path, root, pruned)
+        assert fields(pr) == want[i], (i, pruned)
     return got
+
+
+def verdict(shape, pr):
+    """the model's verdict on a proof (MerkleProof or its fields)"""
+    leaf, idx, path, root, pruned = pr if isinstance(pr, tuple) else fields(pr)
+    return bm.verify(shape, leaf, idx, path, root, pruned)
 
 
 def random_leaves(size, seed):
@@ -100,6 +109,7 @@ def random_leaves(size, seed):
 @pytest.mark.parametrize("pruned", [False, True], ids=["full", "pruned"])
 @pytest.mark.parametrize("kind", ["k1", "k4", "arity4", "mixed"])
 def test_batch_equals_single_calls(hip, kind, pruned, on_device):
+    """every proof of every batch against the model (the single calls run the batch's code: test_single_calls_are_batches_of_one)"""
     from icicle_amd.runtime import DeviceVec
 
     rng = np.random.default_rng(17)
@@ -111,7 +121,7 @@ def test_batch_equals_single_calls(hip, kind, pruned, on_device):
         cfg = config()
         tree = make_tree(layers).build(arg, cfg=cfg)
         n = shape.elements
-        model = (mm.TreeShape(layers, ES), leaves.tobytes(), mm.PAD_NONE) if kind != "mixed" and L <= 7 else None
+        model = model_of(layers, leaves)
         sets = [[0], [n - 1], [n // 2, n // 2]]
         if L == 7:
             sets.append(list(range(n)))  # every index of the 2^6 tree
@@ -119,7 +129,7 @@ def test_batch_equals_single_calls(hip, kind, pruned, on_device):
             sets.append([int(v) for v in rng.integers(0, n, 300)])  # unsorted, with repeats, several blocks of the gather
             assert len(set(sets[-1])) < 300
         for indices in sets:
-            got = check_against_single_calls(tree, arg, leaves.nbytes, indices, pruned, cfg, model)
+            got = check_against_model(tree, arg, leaves.nbytes, indices, pruned, cfg, model)
             assert all(len(p.path) == (0 if L == 1 else sum(shape.chunk[1:]) - (sum(shape.out[:-1]) if pruned else 0)) for p in got)
             assert tree.verify_batch(got[:70]) == [True] * len(got[:70])
         tree.close()
@@ -141,7 +151,7 @@ def test_padded_tail(hip, policy, size, on_device):
         last = (size - 1) // ES
         indices = [shape.elements - 1, last, 0, min(last + 1, shape.elements - 1), min(last + 9, shape.elements - 1), shape.elements // 2, last]
         for pruned in (False, True):
-            got = check_against_single_calls(tree, arg, size, indices, pruned, cfg, (mm.TreeShape(layers, ES), leaves.tobytes(), policy))
+            got = check_against_model(tree, arg, size, indices, pruned, cfg, model_of(layers, leaves, policy))
             assert tree.verify_batch(got) == [True] * len(got)
         tree.close()
 
@@ -165,7 +175,7 @@ def test_stored_layers(hip, tree_on_device, on_device):
         tree = make_tree(layers, store_min).build(arg, size=size, cfg=cfg)
         for indices in sets:
             for pruned in (False, True):
-                check_against_single_calls(tree, arg, size, indices, pruned, cfg, (mm.TreeShape(layers, ES), leaves.tobytes(), mm.PAD_LAST))
+                check_against_model(tree, arg, size, indices, pruned, cfg, model_of(layers, leaves, mm.PAD_LAST))
         tree.close()
     # the mixed tree, whose layers below the first stored one have digests of both sizes
     layers = tree_layers("mixed", 6)
@@ -175,7 +185,7 @@ def test_stored_layers(hip, tree_on_device, on_device):
     cfg = config(tree_on_device=tree_on_device)
     tree = make_tree(layers, 3).build(arg, cfg=cfg)
     for pruned in (False, True):
-        check_against_single_calls(tree, arg, leaves.nbytes, [int(v) for v in rng.integers(0, shape.elements, 40)], pruned, cfg)
+        check_against_model(tree, arg, leaves.nbytes, [int(v) for v in rng.integers(0, shape.elements, 40)], pruned, cfg, model_of(layers, leaves))
     tree.close()
 
 
@@ -192,13 +202,13 @@ def test_leaves_off_a_16_byte_boundary(hip, shift):
         leaves = host[shift:]  # a host pointer off the boundary as well
         d = DeviceVec(size + 32)
         check(lib.icicle_copy_to_device(d.ptr + shift, leaves.ctypes.data, size))
-        model = (mm.TreeShape(layers, ES), leaves.tobytes(), policy)
+        model = model_of(layers, leaves, policy)
         for arg in (leaves, d.ptr + shift):
             for store_min in (0, 2):
                 cfg = config(policy)
                 tree = make_tree(layers, store_min).build(arg, size=size, cfg=cfg)
                 for pruned in (False, True):
-                    check_against_single_calls(tree, arg, size, [0, 1, 5, shape.elements - 1, shape.elements - 4, 77 % shape.elements], pruned, cfg, model)
+                    check_against_model(tree, arg, size, [0, 1, 5, shape.elements - 1, shape.elements - 4, 77 % shape.elements], pruned, cfg, model)
                 tree.close()
 
 
@@ -316,7 +326,7 @@ def test_verify_batch_finds_exactly_the_corrupted_proof(hip, name, pruned):
         if bad is None:
             continue
         batch = good[:at] + [bad] + good[at + 1:]
-        assert tree.verify(bad) is False, what  # what the single call says
+        assert verdict(bm.TreeShape(layers, ES), bad) is False, what  # what the model says
         assert tree.verify_batch(batch) == [i != at for i in range(64)], what
     tree.close()
 
@@ -340,15 +350,16 @@ def test_verify_batch_wrong_sizes_and_more_than_one_block(hip):
         wrong = {0: "leaf", 255: "top", 256: "root", 131: "lowest"}
         for at, what in wrong.items():
             batch[at] = corrupt(shape, plain[at], what)
+            assert verdict(bm.TreeShape(layers, ES), batch[at]) is False, what
         # a root of another length: that entry is false, and no error
         leaf, idx, path, root, _ = plain[77]
         batch[77] = MerkleProof.with_data(pruned, idx, leaf, root[:-1], path)
-        # leaves of other sizes in the same batch: whatever the single call says of each
+        # leaves of other sizes in the same batch (a 4-byte leaf, a 32-byte leaf in a tree of 16-byte chunks): whatever the model says of each
         batch[40] = MerkleProof.with_data(pruned, plain[40][1], plain[40][0][:4], plain[40][3], plain[40][2])
         batch[41] = MerkleProof.with_data(pruned, plain[41][1], plain[41][0] + b"\0" * 16, plain[41][3], plain[41][2])
-        single = {at: tree.verify(batch[at]) for at in (40, 41, 77)}
-        assert single[77] is False
-        want = [single.get(i, i not in wrong) for i in range(257)]
+        model = {at: verdict(bm.TreeShape(layers, ES), batch[at]) for at in (40, 41, 77)}
+        assert model[77] is False
+        want = [model.get(i, i not in wrong) for i in range(257)]
         assert tree.verify_batch(batch) == want
         # a path of the wrong length: the error, and every verdict false
         batch[200] = MerkleProof.with_data(pruned, plain[200][1], plain[200][0], plain[200][3], plain[200][2][:-1])
@@ -362,4 +373,41 @@ def test_verify_batch_wrong_sizes_and_more_than_one_block(hip):
     fresh = make_tree(layers)
     assert fresh.verify_batch(good[:5]) == [True] * 5
     fresh.close()
+    tree.close()
+
+
+# ---- the single calls are batches of one ---------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("pruned", [False, True], ids=["full", "pruned"])
+@pytest.mark.parametrize("case", ["one_layer", "two_layers", "rehashed_subtree", "host_leaves_pinned_tree", "index_in_the_padding"])
+def test_single_calls_are_batches_of_one(hip, case, pruned):
+    """include/icicle_hip.h: get_proofs gives proofs[i] "byte for byte as icicle_merkle_tree_get_proof", verify_batch sets valid[i] to
+    "what icicle_merkle_tree_verify would set" -- held at the C ABI on the smallest trees that reach each branch of the one path: an
+    empty path, one group, one re-hashed sub-tree, a call that touches no device memory, and a leaf chunk made of padding alone. The
+    model says what both must give."""
+    from icicle_amd.merkle import MerkleProof
+    from icicle_amd.runtime import DeviceVec
+
+    # (layers, store_min, leaves on the device, tree on the device, policy, bytes of leaves or None for the capacity, indices)
+    L, store_min, dev_leaves, dev_tree, policy, size, indices = {
+        "one_layer": (1, 0, True, True, mm.PAD_NONE, None, [0, 3]),
+        "two_layers": (2, 0, True, True, mm.PAD_NONE, None, [0, 7]),
+        "rehashed_subtree": (3, 1, True, True, mm.PAD_NONE, None, [0, 9, 15]),
+        "host_leaves_pinned_tree": (3, 0, False, False, mm.PAD_NONE, None, [0, 6, 15]),
+        "index_in_the_padding": (3, 0, True, True, mm.PAD_LAST, 20, [4, 5, 15]),  # 20 of 64 bytes: chunk 1 half padding, chunks 2 and 3 all of it
+    }[case]
+    layers = tree_layers("k4", L)  # at most 4 chunks of 16 bytes
+    shape = Shape(layers)
+    leaves = random_leaves(size or shape.capacity, L)
+    arg = DeviceVec.from_host(leaves) if dev_leaves else leaves
+    cfg = config(policy, dev_tree)
+    tree = make_tree(layers, store_min).build(arg, size=leaves.nbytes, cfg=cfg)
+    model = bm.TreeShape(layers, ES)
+    for i in indices:
+        single, batch = tree.proof(arg, i, pruned, cfg, size=leaves.nbytes), tree.proofs(arg, [i], pruned, cfg, size=leaves.nbytes)[0]
+        leaf, path, root = bm.proof(model, leaves.tobytes(), i, pruned, policy)
+        assert fields(single) == fields(batch) == (leaf, i, path, root, pruned), i
+        bad = MerkleProof.with_data(pruned, i, flip(leaf, 0), root, path)
+        for pr, want in ((single, True), (bad, False)):
+            assert verdict(model, pr) is want
+            assert tree.verify(pr) is tree.verify_batch([pr])[0] is want, i
     tree.close()

@@ -1,6 +1,7 @@
 """CPU: the hash / Merkle part of the C ABI without a GPU -- the test model against hashlib, struct layouts, exported and bound
 symbols, handle life cycle, loud failure of the compute entry points, and the host-only tree arithmetic
-(icicle_amd/csrc/merkle_plan.h, compiled with g++) against the model (tests/merkle_model.py)."""
+(icicle_amd/csrc/merkle_plan.h and the leaf-index arithmetic of merkle_batch.h, compiled with g++) against the model
+(tests/merkle_model.py)."""
 import ctypes
 import hashlib
 import os
@@ -157,13 +158,13 @@ def test_no_gpu_means_loud_failure():
         MerkleTree([Hasher.keccak256(64)] * 2, 32).build(np.zeros(128, np.uint8))
 
 
-# ---- merkle_plan.h against the model ------------------------------------------------------------------------------------------
+# ---- merkle_plan.h and merkle_batch.h against the model -------------------------------------------------------------------------
 def _plan_lib():
     so = os.path.join(HERE, "_build", "libmerkle_plan.so")
     os.makedirs(os.path.dirname(so), exist_ok=True)
     src = os.path.join(HERE, "merkle_plan_harness.cpp")
-    hdr = os.path.join(ROOT, "icicle_amd", "csrc", "merkle_plan.h")
-    if not os.path.exists(so) or max(os.path.getmtime(src), os.path.getmtime(hdr)) > os.path.getmtime(so):
+    hdrs = [os.path.join(ROOT, "icicle_amd", "csrc", h) for h in ("merkle_plan.h", "merkle_batch.h")]  # mp_proof walks merkle_batch.h
+    if not os.path.exists(so) or max(os.path.getmtime(f) for f in [src] + hdrs) > os.path.getmtime(so):
         subprocess.check_call(["g++", "-std=c++17", "-O2", "-fPIC", "-shared", src, "-o", so])
     lib = ctypes.CDLL(so)
     u64p = ctypes.POINTER(ctypes.c_uint64)

@@ -1,7 +1,8 @@
 """CPU: batched Merkle openings and verification without a GPU -- the index function the gather kernel and the host share
 (icicle_amd/csrc/merkle_batch.h, compiled with g++ plainly and with -fsanitize=address,undefined as a program of its own:
-tests/merkle_batch_harness.cpp) against merkle_proof_plan for every leaf index of small trees, the staging record's layout, the two
-entry points in header, library and binding, and the refusals that precede the device."""
+tests/merkle_batch_harness.cpp) against the loop form of the proof plan, which the harness carries as reference code, for every leaf
+index of small trees, the staging record's layout, the two entry points in header, library and binding, and the refusals that precede
+the device."""
 import ctypes
 import os
 import re
