@@ -49,6 +49,19 @@ namespace icicle_hip {
     if (_ie != ICICLE_SUCCESS) return _ie;                                                                             \
   } while (0)
 
+// the body of an extern "C" entry point: no exception crosses the C ABI
+#define GUARDED(expr)                                                                                                  \
+  try {                                                                                                                \
+    return (expr);                                                                                                     \
+  } catch (...) {                                                                                                      \
+    return ICICLE_INVALID_ARGUMENT;                                                                                    \
+  }
+
+// an entry point under the reference's name and under its icicle_hip_ twin, from one body; ARGS in parentheses
+#define EXPORT_TWIN(NAME, ARGS, ...)                                                                                   \
+  extern "C" icicle_error_t NAME ARGS { GUARDED((__VA_ARGS__)); }                                                      \
+  extern "C" icicle_error_t icicle_hip_##NAME ARGS { GUARDED((__VA_ARGS__)); }
+
   bool verbose();
   bool sync_debug(); // ICICLE_HIP_SYNC_DEBUG=1: synchronise + check after every kernel launch
 

@@ -463,13 +463,6 @@ namespace icicle_hip {
 
 using namespace icicle_hip;
 
-#define GUARDED(expr)                                                                                                  \
-  try {                                                                                                                \
-    return (expr);                                                                                                     \
-  } catch (...) {                                                                                                      \
-    return ICICLE_INVALID_ARGUMENT;                                                                                    \
-  }
-
 #define DEFINE_ECNTT(C)                                                                                                \
   extern "C" icicle_error_t C##_ecntt(const void* input, int size, int dir, const icicle_ntt_config_u256_t* config, void* output) \
   {                                                                                                                    \

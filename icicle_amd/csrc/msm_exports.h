@@ -1,14 +1,7 @@
 // C-ABI export macros of the MSM translation units (msm.hip, msm_curves2.hip, msm_g2.hip, msm_g2_curves2.hip): the
 // curves are spread over several files so that they compile in parallel.
 #pragma once
-
-// exceptions must never cross the C boundary (Rust/Go callers are extern "C" frames)
-#define GUARDED(expr)                                                                                                  \
-  try {                                                                                                                \
-    return (expr);                                                                                                     \
-  } catch (...) {                                                                                                      \
-    return ICICLE_INVALID_ARGUMENT;                                                                                    \
-  }
+#include "common.h" // GUARDED: exceptions must never cross the C boundary (Rust/Go callers are extern "C" frames)
 
 // G: bn254 -> group bn254_g1, symbols bn254_msm ...; G2: bn254 -> group bn254_g2, symbols bn254_g2_msm ...
 #define DEFINE_MSM_EXPORTS(SYM, GROUP)                                                                                 \

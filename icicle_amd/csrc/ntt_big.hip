@@ -523,13 +523,6 @@ namespace icicle_hip {
 
 using namespace icicle_hip;
 
-#define GUARDED(expr)                                                                                                  \
-  try {                                                                                                                \
-    return (expr);                                                                                                     \
-  } catch (...) {                                                                                                      \
-    return ICICLE_INVALID_ARGUMENT;                                                                                    \
-  }
-
 // domain / root-of-unity entry points (src/ntt.cpp:26,41,55,75) + collision-free aliases for the plugin
 #define DEFINE_NTT_DOMAIN_API(F, PRM)                                                                                  \
   extern "C" icicle_error_t F##_ntt_init_domain(const uint32_t* primitive_root, const icicle_ntt_init_domain_config_t* config) \

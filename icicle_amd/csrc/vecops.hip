@@ -6,16 +6,17 @@
 // icicle/backend/cpu/src/field/cpu_vec_ops.cpp convert_montgomery, backend/cpu/src/curve/cpu_mont_conversion.cpp:12-27;
 // C ABI icicle/src/vec_ops.cpp:402-415, icicle/src/curves/montgomery_conversion.cpp:10-58).
 // One field multiplication per element: HBM-bound (read + write of the data).
-#include "common.h"
+#include "vecops_host.hpp"
 #include "bigfield.hpp"
 #include "smallfield.hpp"
 #include "goldfield.hpp"
 
 namespace icicle_hip {
 
+  // The three kernels are element-wise under the contract stated at k_vec2 (vecops_tile.hpp): out may be in, and convert_run uses that.
   // n field elements of PR::NL32 words each
   template <class PR>
-  __global__ __launch_bounds__(256) void k_convert_big(const uint32_t* __restrict__ in, uint32_t* __restrict__ out, size_t n, bool to_mont)
+  __global__ __launch_bounds__(256) void k_convert_big(const uint32_t* in, uint32_t* out, size_t n, bool to_mont)
   {
     using F = FieldOps<PR>;
     const size_t t = blockIdx.x * (size_t)blockDim.x + threadIdx.x;
@@ -36,7 +37,7 @@ namespace icicle_hip {
   }
 
   // goldilocks: x -> x * 2^64 or x * 2^-64 mod p (goldilocks.h:179-184), n elements of 2 words
-  __global__ __launch_bounds__(256) void k_convert_gold(const uint32_t* __restrict__ in, uint32_t* __restrict__ out, size_t n, bool to_mont)
+  __global__ __launch_bounds__(256) void k_convert_gold(const uint32_t* in, uint32_t* out, size_t n, bool to_mont)
   {
     using F = FieldOps<goldilocks_params>;
     size_t t = blockIdx.x * (size_t)blockDim.x + threadIdx.x;
@@ -50,7 +51,7 @@ namespace icicle_hip {
   }
 
   template <class PR>
-  __global__ __launch_bounds__(256) void k_convert_small(const uint32_t* __restrict__ in, uint32_t* __restrict__ out, size_t n, bool to_mont)
+  __global__ __launch_bounds__(256) void k_convert_small(const uint32_t* in, uint32_t* out, size_t n, bool to_mont)
   {
     using S = SmallField<PR>;
     size_t t = blockIdx.x * (size_t)blockDim.x + threadIdx.x;
@@ -69,31 +70,16 @@ namespace icicle_hip {
     ICICLE_TRY(bind_current_device());
     hipStream_t st = (hipStream_t)cfg->stream;
     const size_t bytes = (size_t)nelem * words * 4;
-    TempBuf d_in_tmp, d_out_tmp;
-    const uint32_t* d_in = (const uint32_t*)input;
-    uint32_t* d_out = (uint32_t*)output;
-    if (!cfg->is_a_on_device) {
-      HIP_TRY(d_in_tmp.alloc(bytes, st), ICICLE_ALLOCATION_FAILED);
-      HIP_TRY(hipMemcpyAsync(d_in_tmp.ptr(), input, bytes, hipMemcpyHostToDevice, st), ICICLE_COPY_FAILED);
-      d_in = d_in_tmp.as<uint32_t>();
-    }
-    if (!cfg->is_result_on_device) {
-      if (!cfg->is_a_on_device) {
-        d_out = d_in_tmp.as<uint32_t>(); // in place in the staging buffer
-      } else {
-        HIP_TRY(d_out_tmp.alloc(bytes, st), ICICLE_ALLOCATION_FAILED);
-        d_out = d_out_tmp.as<uint32_t>();
-      }
-    }
-    launch(d_in, d_out, (size_t)nelem, st);
+    Staged si;
+    StagedOut so;
+    ICICLE_TRY(si.in(input, cfg->is_a_on_device, bytes, st));
+    if (!cfg->is_a_on_device && !cfg->is_result_on_device)
+      so.adopt(output, false, bytes, st, si.buf.as<uint32_t>()); // in place in the staging buffer
+    else
+      ICICLE_TRY(so.out(output, cfg->is_result_on_device, bytes, st));
+    launch(si.dev, so.dev, (size_t)nelem, st);
     LAUNCH_CHECK("k_convert", st);
-    if (!cfg->is_result_on_device) {
-      HIP_TRY(hipMemcpyAsync(output, d_out, bytes, hipMemcpyDeviceToHost, st), ICICLE_COPY_FAILED);
-      HIP_TRY(hipStreamSynchronize(st), ICICLE_SYNCHRONIZATION_FAILED);
-    } else if (!cfg->is_async) {
-      HIP_TRY(hipStreamSynchronize(st), ICICLE_SYNCHRONIZATION_FAILED);
-    }
-    return ICICLE_SUCCESS;
+    return so.finish(cfg->is_async);
   }
 
   template <class PR>
@@ -122,36 +108,21 @@ namespace icicle_hip {
 
 using namespace icicle_hip;
 
-#define GUARDED(expr)                                                                                                  \
-  try {                                                                                                                \
-    return (expr);                                                                                                     \
-  } catch (...) {                                                                                                      \
-    return ICICLE_INVALID_ARGUMENT;                                                                                    \
-  }
-
+#define CONVERT_ARGS (const void* i, uint64_t n, bool to, const icicle_vec_ops_config_t* c, void* o)
 // scalar_convert_montgomery: `size` elements per batch entry (icicle/src/vec_ops.cpp:404-408)
-#define DEFINE_SCALAR_CONVERT_BIG(NAME, PR)                                                                            \
-  extern "C" icicle_error_t NAME##_scalar_convert_montgomery(const void* i, uint64_t n, bool to, const icicle_vec_ops_config_t* c, void* o) { GUARDED(convert_big<PR>(i, n * batch_of(c), to, c, o)); } \
-  extern "C" icicle_error_t icicle_hip_##NAME##_scalar_convert_montgomery(const void* i, uint64_t n, bool to, const icicle_vec_ops_config_t* c, void* o) { GUARDED(convert_big<PR>(i, n * batch_of(c), to, c, o)); }
+#define DEFINE_SCALAR_CONVERT_BIG(NAME, PR) EXPORT_TWIN(NAME##_scalar_convert_montgomery, CONVERT_ARGS, convert_big<PR>(i, n * batch_of(c), to, c, o))
 #define DEFINE_SCALAR_CONVERT_SMALL(NAME, PR)                                                                          \
-  extern "C" icicle_error_t NAME##_scalar_convert_montgomery(const void* i, uint64_t n, bool to, const icicle_vec_ops_config_t* c, void* o) { GUARDED(convert_small<PR>(i, n * batch_of(c), to, c, o)); } \
-  extern "C" icicle_error_t NAME##_extension_scalar_convert_montgomery(const void* i, uint64_t n, bool to, const icicle_vec_ops_config_t* c, void* o) { GUARDED(convert_small<PR>(i, 4 * n * batch_of(c), to, c, o)); } \
-  extern "C" icicle_error_t icicle_hip_##NAME##_scalar_convert_montgomery(const void* i, uint64_t n, bool to, const icicle_vec_ops_config_t* c, void* o) { GUARDED(convert_small<PR>(i, n * batch_of(c), to, c, o)); } \
-  extern "C" icicle_error_t icicle_hip_##NAME##_extension_scalar_convert_montgomery(const void* i, uint64_t n, bool to, const icicle_vec_ops_config_t* c, void* o) { GUARDED(convert_small<PR>(i, 4 * n * batch_of(c), to, c, o)); }
+  EXPORT_TWIN(NAME##_scalar_convert_montgomery, CONVERT_ARGS, convert_small<PR>(i, n * batch_of(c), to, c, o))         \
+  EXPORT_TWIN(NAME##_extension_scalar_convert_montgomery, CONVERT_ARGS, convert_small<PR>(i, 4 * n * batch_of(c), to, c, o))
 // points: n points of 2 (affine) or 3 (projective) base-field coordinates (icicle/src/curves/montgomery_conversion.cpp:12-16,46-50)
 #define DEFINE_POINT_CONVERT(NAME, PR)                                                                                 \
-  extern "C" icicle_error_t NAME##_affine_convert_montgomery(const void* i, uint64_t n, bool to, const icicle_vec_ops_config_t* c, void* o) { GUARDED(convert_big<PR>(i, 2 * n, to, c, o)); } \
-  extern "C" icicle_error_t NAME##_projective_convert_montgomery(const void* i, uint64_t n, bool to, const icicle_vec_ops_config_t* c, void* o) { GUARDED(convert_big<PR>(i, 3 * n, to, c, o)); } \
-  extern "C" icicle_error_t icicle_hip_##NAME##_affine_convert_montgomery(const void* i, uint64_t n, bool to, const icicle_vec_ops_config_t* c, void* o) { GUARDED(convert_big<PR>(i, 2 * n, to, c, o)); } \
-  extern "C" icicle_error_t icicle_hip_##NAME##_projective_convert_montgomery(const void* i, uint64_t n, bool to, const icicle_vec_ops_config_t* c, void* o) { GUARDED(convert_big<PR>(i, 3 * n, to, c, o)); }
-
+  EXPORT_TWIN(NAME##_affine_convert_montgomery, CONVERT_ARGS, convert_big<PR>(i, 2 * n, to, c, o))                     \
+  EXPORT_TWIN(NAME##_projective_convert_montgomery, CONVERT_ARGS, convert_big<PR>(i, 3 * n, to, c, o))
 // G2 points: coordinates are Fq2 = two base-field components each, converted component-wise
 // (fields/complex_extension.h:88-96; src/curves/montgomery_conversion.cpp:26-44,60-78)
 #define DEFINE_G2_POINT_CONVERT(NAME, PR)                                                                              \
-  extern "C" icicle_error_t NAME##_g2_affine_convert_montgomery(const void* i, uint64_t n, bool to, const icicle_vec_ops_config_t* c, void* o) { GUARDED(convert_big<PR>(i, 4 * n, to, c, o)); } \
-  extern "C" icicle_error_t NAME##_g2_projective_convert_montgomery(const void* i, uint64_t n, bool to, const icicle_vec_ops_config_t* c, void* o) { GUARDED(convert_big<PR>(i, 6 * n, to, c, o)); } \
-  extern "C" icicle_error_t icicle_hip_##NAME##_g2_affine_convert_montgomery(const void* i, uint64_t n, bool to, const icicle_vec_ops_config_t* c, void* o) { GUARDED(convert_big<PR>(i, 4 * n, to, c, o)); } \
-  extern "C" icicle_error_t icicle_hip_##NAME##_g2_projective_convert_montgomery(const void* i, uint64_t n, bool to, const icicle_vec_ops_config_t* c, void* o) { GUARDED(convert_big<PR>(i, 6 * n, to, c, o)); }
+  EXPORT_TWIN(NAME##_g2_affine_convert_montgomery, CONVERT_ARGS, convert_big<PR>(i, 4 * n, to, c, o))                  \
+  EXPORT_TWIN(NAME##_g2_projective_convert_montgomery, CONVERT_ARGS, convert_big<PR>(i, 6 * n, to, c, o))
 
 DEFINE_SCALAR_CONVERT_BIG(bn254, bn254_fr_params)
 DEFINE_SCALAR_CONVERT_BIG(bls12_381, bls12_381_fr_params)
@@ -168,7 +139,6 @@ DEFINE_G2_POINT_CONVERT(bn254, bn254_fq_params)
 DEFINE_G2_POINT_CONVERT(bls12_381, bls12_381_fq_params)
 DEFINE_G2_POINT_CONVERT(bls12_377, bls12_377_fq_params)
 // goldilocks and its quadratic extension (two components per element)
-extern "C" icicle_error_t goldilocks_scalar_convert_montgomery(const void* i, uint64_t n, bool to, const icicle_vec_ops_config_t* c, void* o) { GUARDED(convert_gold(i, n * batch_of(c), to, c, o)); }
-extern "C" icicle_error_t goldilocks_extension_scalar_convert_montgomery(const void* i, uint64_t n, bool to, const icicle_vec_ops_config_t* c, void* o) { GUARDED(convert_gold(i, 2 * n * batch_of(c), to, c, o)); }
-extern "C" icicle_error_t icicle_hip_goldilocks_scalar_convert_montgomery(const void* i, uint64_t n, bool to, const icicle_vec_ops_config_t* c, void* o) { GUARDED(convert_gold(i, n * batch_of(c), to, c, o)); }
-extern "C" icicle_error_t icicle_hip_goldilocks_extension_scalar_convert_montgomery(const void* i, uint64_t n, bool to, const icicle_vec_ops_config_t* c, void* o) { GUARDED(convert_gold(i, 2 * n * batch_of(c), to, c, o)); }
+EXPORT_TWIN(goldilocks_scalar_convert_montgomery, CONVERT_ARGS, convert_gold(i, n * batch_of(c), to, c, o))
+EXPORT_TWIN(goldilocks_extension_scalar_convert_montgomery, CONVERT_ARGS, convert_gold(i, 2 * n * batch_of(c), to, c, o))
+

@@ -10,21 +10,9 @@
 // columns_batch), :536-560 (bit reverse per batch entry). Values are plain (non-Montgomery) residues and
 // stay so: products are computed as montmul(montmul(a, b), R^2).
 // All of these are HBM-bound streams (2 reads + 1 write per element, or 1 + 1 for bit_reverse).
-#include "vecops_elem.hpp" // SmallElem / BigElem / GoldElem, Staged, finish_out
+#include "vecops_tile.hpp" // SmallElem / BigElem / GoldElem, k_vec2 and vec2_run; Staged and StagedOut (vecops_host.hpp)
 
 namespace icicle_hip {
-
-  // out[i] = a[ai(i)] op b[i]; a_scalar: a holds one scalar per batch entry
-  template <class EL>
-  __global__ __launch_bounds__(256) void k_vec2(const uint32_t* __restrict__ a, const uint32_t* __restrict__ b, uint32_t* __restrict__ out, uint64_t total, int op, bool a_scalar, uint64_t size, uint32_t batch, bool columns)
-  {
-    uint64_t i = blockIdx.x * (uint64_t)blockDim.x + threadIdx.x;
-    const uint64_t stride = (uint64_t)gridDim.x * blockDim.x;
-    for (; i < total; i += stride) {
-      const uint64_t ai = !a_scalar ? i : (columns ? i % batch : i / size);
-      EL::store(out + i * EL::W, EL::apply(op, EL::load(a + ai * EL::W), EL::load(b + i * EL::W)));
-    }
-  }
 
   // out[b][bitrev(j)] = in[b][j]; element j of entry b at (columns ? j*batch + b : b*size + j)
   template <int W>
@@ -45,32 +33,6 @@ namespace icicle_hip {
       out[dst * W + i] = w[i];
   }
 
-  template <class EL>
-  static icicle_error_t vec2_run(const void* a, const void* b, uint64_t size, const icicle_vec_ops_config_t* cfg, void* out, int op, bool a_scalar)
-  {
-    if (!cfg) return ICICLE_INVALID_POINTER;
-    if (size == 0) return ICICLE_SUCCESS;
-    if (!a || !b || !out) return ICICLE_INVALID_POINTER;
-    ICICLE_TRY(bind_current_device());
-    hipStream_t st = (hipStream_t)cfg->stream;
-    const uint32_t batch = (uint32_t)std::max(1, cfg->batch_size);
-    const uint64_t total = size * batch;
-    const size_t ebytes = (size_t)EL::W * 4, bytes = (size_t)total * ebytes;
-    Staged sa, sb;
-    ICICLE_TRY(sa.in(a, cfg->is_a_on_device, a_scalar ? (size_t)batch * ebytes : bytes, st));
-    ICICLE_TRY(sb.in(b, cfg->is_b_on_device, bytes, st));
-    TempBuf d_out_tmp;
-    uint32_t* d_out = (uint32_t*)out;
-    if (!cfg->is_result_on_device) {
-      HIP_TRY(d_out_tmp.alloc(bytes, st), ICICLE_ALLOCATION_FAILED);
-      d_out = d_out_tmp.as<uint32_t>();
-    }
-    const unsigned grid = (unsigned)std::min<uint64_t>((total + 255) / 256, 1u << 20);
-    k_vec2<EL><<<grid, 256, 0, st>>>(sa.dev, sb.dev, d_out, total, op, a_scalar, size, batch, cfg->columns_batch);
-    LAUNCH_CHECK("k_vec2", st);
-    return finish_out(out, d_out, cfg->is_result_on_device, cfg->is_async, bytes, st);
-  }
-
   template <int W>
   static icicle_error_t bitrev_run(const void* in, uint64_t size, const icicle_vec_ops_config_t* cfg, void* out)
   {
@@ -85,23 +47,13 @@ namespace icicle_hip {
       logn++;
     const size_t bytes = (size_t)size * batch * W * 4;
     Staged si;
+    StagedOut so;
     ICICLE_TRY(si.in(in, cfg->is_a_on_device, bytes, st));
-    TempBuf d_out_tmp;
-    uint32_t* d_out = (uint32_t*)out;
-    // out of place on the device; an in-place call (same device pointer) goes through a temporary
-    const bool need_tmp = !cfg->is_result_on_device || (const void*)si.dev == (const void*)out;
-    if (need_tmp) {
-      HIP_TRY(d_out_tmp.alloc(bytes, st), ICICLE_ALLOCATION_FAILED);
-      d_out = d_out_tmp.as<uint32_t>();
-    }
+    ICICLE_TRY(so.out(out, cfg->is_result_on_device, bytes, st, si.dev)); // out of place on the device: an in-place call goes through a temporary
     const uint64_t tot = size * batch;
-    k_bitrev_elems<W><<<(unsigned)((tot + 255) / 256), 256, 0, st>>>(si.dev, d_out, logn, batch, cfg->columns_batch);
+    k_bitrev_elems<W><<<(unsigned)((tot + 255) / 256), 256, 0, st>>>(si.dev, so.dev, logn, batch, cfg->columns_batch);
     LAUNCH_CHECK("k_bitrev_elems", st);
-    if (cfg->is_result_on_device && need_tmp) {
-      HIP_TRY(hipMemcpyAsync(out, d_out, bytes, hipMemcpyDeviceToDevice, st), ICICLE_COPY_FAILED);
-      d_out = (uint32_t*)out;
-    }
-    return finish_out(out, d_out, cfg->is_result_on_device, cfg->is_async, bytes, st);
+    return so.finish(cfg->is_async);
   }
 
   // ---- matrix_transpose (icicle/src/matrix_ops.cpp:73-102, backend/cpu/src/field/cpu_matrix_ops.cpp:175-201,333-362) ----------
@@ -146,52 +98,31 @@ namespace icicle_hip {
     const uint32_t batch = (uint32_t)std::max(1, cfg->batch_size);
     const size_t bytes = (size_t)rows * cols * batch * W * 4;
     Staged si;
+    StagedOut so;
     ICICLE_TRY(si.in(in, cfg->is_a_on_device, bytes, st));
-    TempBuf d_out_tmp;
-    uint32_t* d_out = (uint32_t*)out;
-    // out of place on the device; an in-place call (cpu_matrix_ops.cpp:348-359 supports it) goes through a temporary
-    const bool need_tmp = !cfg->is_result_on_device || (const void*)si.dev == (const void*)out;
-    if (need_tmp) {
-      HIP_TRY(d_out_tmp.alloc(bytes, st), ICICLE_ALLOCATION_FAILED);
-      d_out = d_out_tmp.as<uint32_t>();
-    }
+    // out of place on the device: an in-place call (cpu_matrix_ops.cpp:348-359 supports it) goes through a temporary
+    ICICLE_TRY(so.out(out, cfg->is_result_on_device, bytes, st, si.dev));
     const uint64_t tiles_r = ((uint64_t)rows + 31) / 32, tiles_c = ((uint64_t)cols + 31) / 32;
     if (tiles_r * tiles_c > 0x7fffffffull) return ICICLE_INVALID_ARGUMENT;
-    k_transpose<W><<<dim3((unsigned)(tiles_r * tiles_c), std::min(batch, 65535u)), 256, 0, st>>>(si.dev, d_out, rows, cols, (uint32_t)tiles_c, batch);
+    k_transpose<W><<<dim3((unsigned)(tiles_r * tiles_c), std::min(batch, 65535u)), 256, 0, st>>>(si.dev, so.dev, rows, cols, (uint32_t)tiles_c, batch);
     LAUNCH_CHECK("k_transpose", st);
-    if (cfg->is_result_on_device && need_tmp) {
-      HIP_TRY(hipMemcpyAsync(out, d_out, bytes, hipMemcpyDeviceToDevice, st), ICICLE_COPY_FAILED);
-      d_out = (uint32_t*)out;
-    }
-    return finish_out(out, d_out, cfg->is_result_on_device, cfg->is_async, bytes, st);
+    return so.finish(cfg->is_async);
   }
 
 } // namespace icicle_hip
 
 using namespace icicle_hip;
 
-#define GUARDED(expr)                                                                                                  \
-  try {                                                                                                                \
-    return (expr);                                                                                                     \
-  } catch (...) {                                                                                                      \
-    return ICICLE_INVALID_ARGUMENT;                                                                                    \
-  }
-
+#define VEC_ARGS2 (const void* a, const void* b, uint64_t n, const icicle_vec_ops_config_t* c, void* o)
+#define VEC_ARGS1 (const void* a, uint64_t n, const icicle_vec_ops_config_t* c, void* o)
 #define DEFINE_VEC_ARITH(NAME, EL, W)                                                                                  \
-  extern "C" icicle_error_t NAME##_vector_add(const void* a, const void* b, uint64_t n, const icicle_vec_ops_config_t* c, void* o) { GUARDED((vec2_run<EL>(a, b, n, c, o, VOP_ADD, false))); } \
-  extern "C" icicle_error_t NAME##_vector_sub(const void* a, const void* b, uint64_t n, const icicle_vec_ops_config_t* c, void* o) { GUARDED((vec2_run<EL>(a, b, n, c, o, VOP_SUB, false))); } \
-  extern "C" icicle_error_t NAME##_vector_mul(const void* a, const void* b, uint64_t n, const icicle_vec_ops_config_t* c, void* o) { GUARDED((vec2_run<EL>(a, b, n, c, o, VOP_MUL, false))); } \
-  extern "C" icicle_error_t NAME##_scalar_mul_vec(const void* a, const void* b, uint64_t n, const icicle_vec_ops_config_t* c, void* o) { GUARDED((vec2_run<EL>(a, b, n, c, o, VOP_MUL, true))); } \
-  extern "C" icicle_error_t NAME##_scalar_add_vec(const void* a, const void* b, uint64_t n, const icicle_vec_ops_config_t* c, void* o) { GUARDED((vec2_run<EL>(a, b, n, c, o, VOP_ADD, true))); } \
-  extern "C" icicle_error_t NAME##_scalar_sub_vec(const void* a, const void* b, uint64_t n, const icicle_vec_ops_config_t* c, void* o) { GUARDED((vec2_run<EL>(a, b, n, c, o, VOP_SUB, true))); } \
-  extern "C" icicle_error_t icicle_hip_##NAME##_scalar_add_vec(const void* a, const void* b, uint64_t n, const icicle_vec_ops_config_t* c, void* o) { GUARDED((vec2_run<EL>(a, b, n, c, o, VOP_ADD, true))); } \
-  extern "C" icicle_error_t icicle_hip_##NAME##_scalar_sub_vec(const void* a, const void* b, uint64_t n, const icicle_vec_ops_config_t* c, void* o) { GUARDED((vec2_run<EL>(a, b, n, c, o, VOP_SUB, true))); } \
-  extern "C" icicle_error_t NAME##_bit_reverse(const void* i, uint64_t n, const icicle_vec_ops_config_t* c, void* o) { GUARDED((bitrev_run<W>(i, n, c, o))); } \
-  extern "C" icicle_error_t icicle_hip_##NAME##_vector_add(const void* a, const void* b, uint64_t n, const icicle_vec_ops_config_t* c, void* o) { GUARDED((vec2_run<EL>(a, b, n, c, o, VOP_ADD, false))); } \
-  extern "C" icicle_error_t icicle_hip_##NAME##_vector_sub(const void* a, const void* b, uint64_t n, const icicle_vec_ops_config_t* c, void* o) { GUARDED((vec2_run<EL>(a, b, n, c, o, VOP_SUB, false))); } \
-  extern "C" icicle_error_t icicle_hip_##NAME##_vector_mul(const void* a, const void* b, uint64_t n, const icicle_vec_ops_config_t* c, void* o) { GUARDED((vec2_run<EL>(a, b, n, c, o, VOP_MUL, false))); } \
-  extern "C" icicle_error_t icicle_hip_##NAME##_scalar_mul_vec(const void* a, const void* b, uint64_t n, const icicle_vec_ops_config_t* c, void* o) { GUARDED((vec2_run<EL>(a, b, n, c, o, VOP_MUL, true))); } \
-  extern "C" icicle_error_t icicle_hip_##NAME##_bit_reverse(const void* i, uint64_t n, const icicle_vec_ops_config_t* c, void* o) { GUARDED((bitrev_run<W>(i, n, c, o))); }
+  EXPORT_TWIN(NAME##_vector_add, VEC_ARGS2, vec2_run<EL>(a, b, n, c, o, VOP_ADD, false))                               \
+  EXPORT_TWIN(NAME##_vector_sub, VEC_ARGS2, vec2_run<EL>(a, b, n, c, o, VOP_SUB, false))                               \
+  EXPORT_TWIN(NAME##_vector_mul, VEC_ARGS2, vec2_run<EL>(a, b, n, c, o, VOP_MUL, false))                               \
+  EXPORT_TWIN(NAME##_scalar_add_vec, VEC_ARGS2, vec2_run<EL>(a, b, n, c, o, VOP_ADD, true))                            \
+  EXPORT_TWIN(NAME##_scalar_sub_vec, VEC_ARGS2, vec2_run<EL>(a, b, n, c, o, VOP_SUB, true))                            \
+  EXPORT_TWIN(NAME##_scalar_mul_vec, VEC_ARGS2, vec2_run<EL>(a, b, n, c, o, VOP_MUL, true))                            \
+  EXPORT_TWIN(NAME##_bit_reverse, VEC_ARGS1, bitrev_run<W>(a, n, c, o))
 
 DEFINE_VEC_ARITH(babybear, SmallElem<babybear_params>, 1)
 DEFINE_VEC_ARITH(koalabear, SmallElem<koalabear_params>, 1)
@@ -204,15 +135,14 @@ DEFINE_VEC_ARITH(goldilocks, GoldElem, 2)
 
 // extension_bit_reverse (icicle/src/vec_ops.cpp:455-464): the kernel above over the 4-word extension elements of vecops_ext.hip
 #define DEFINE_EXT_BITREV(NAME)                                                                                        \
-  extern "C" icicle_error_t NAME##_extension_bit_reverse(const void* i, uint64_t n, const icicle_vec_ops_config_t* c, void* o) { GUARDED((bitrev_run<4>(i, n, c, o))); }
+  extern "C" icicle_error_t NAME##_extension_bit_reverse VEC_ARGS1 { GUARDED((bitrev_run<4>(a, n, c, o))); }
 DEFINE_EXT_BITREV(babybear)
 DEFINE_EXT_BITREV(koalabear)
 DEFINE_EXT_BITREV(goldilocks)
 
 // matrix_transpose / extension_matrix_transpose (icicle/src/matrix_ops.cpp:75-102): W = u32 words per element
 #define DEFINE_TRANSPOSE(NAME, SUFFIX, W)                                                                              \
-  extern "C" icicle_error_t NAME##_##SUFFIX(const void* i, uint32_t r, uint32_t c, const icicle_vec_ops_config_t* cfg, void* o) { GUARDED((transpose_run<W>(i, r, c, cfg, o))); } \
-  extern "C" icicle_error_t icicle_hip_##NAME##_##SUFFIX(const void* i, uint32_t r, uint32_t c, const icicle_vec_ops_config_t* cfg, void* o) { GUARDED((transpose_run<W>(i, r, c, cfg, o))); }
+  EXPORT_TWIN(NAME##_##SUFFIX, (const void* i, uint32_t r, uint32_t c, const icicle_vec_ops_config_t* cfg, void* o), transpose_run<W>(i, r, c, cfg, o))
 DEFINE_TRANSPOSE(babybear, matrix_transpose, 1)
 DEFINE_TRANSPOSE(koalabear, matrix_transpose, 1)
 DEFINE_TRANSPOSE(babybear, extension_matrix_transpose, 4)
@@ -224,3 +154,4 @@ DEFINE_TRANSPOSE(bls12_381, matrix_transpose, 8)
 DEFINE_TRANSPOSE(bls12_377, matrix_transpose, 8)
 DEFINE_TRANSPOSE(grumpkin, matrix_transpose, 8)
 DEFINE_TRANSPOSE(stark252, matrix_transpose, 8)
+

@@ -1,5 +1,5 @@
-// What vecops_arith.hip and vecops_inv.hip share: the three kinds of element behind one interface (one Montgomery word, nine
-// 29-bit Montgomery limbs, one canonical 64-bit Goldilocks value) and the host <-> device staging of an operand and a result.
+// The three kinds of base-field element behind one interface: one Montgomery word, nine 29-bit Montgomery limbs, one canonical
+// 64-bit Goldilocks value. vecops_ext_elem.hpp holds the extension elements behind the same interface, vecops_tile.hpp the kernels.
 //
 // load / store / apply are the element-wise interface of vector_add / sub / mul. What follows them in each struct is what the
 // inversion and the reductions need. There a loaded value x is never converted: it is read as the Montgomery representative of
@@ -11,13 +11,12 @@
 //   * a product of n loaded values through mul_raw is prod / R^(n-1): scale_pow(x, n) puts R^(n-1) back.
 #pragma once
 #include "common.h"
+#include "vecops_op.h"
 #include "bigfield.hpp"
 #include "smallfield.hpp"
 #include "goldfield.hpp"
 
 namespace icicle_hip {
-
-  enum { VOP_ADD = 0, VOP_SUB = 1, VOP_MUL = 2 };
 
   template <class PR>
   struct SmallElem {
@@ -134,32 +133,5 @@ namespace icicle_hip {
     static __device__ __forceinline__ T unscale(const T& a) { return a; }
     static __device__ __forceinline__ T scale_pow(const T& a, uint64_t) { return a; }
   };
-
-  struct Staged { // host <-> device staging of one operand
-    TempBuf buf;
-    const uint32_t* dev = nullptr;
-    icicle_error_t in(const void* p, bool on_device, size_t bytes, hipStream_t st)
-    {
-      if (on_device) {
-        dev = (const uint32_t*)p;
-        return ICICLE_SUCCESS;
-      }
-      HIP_TRY(buf.alloc(bytes, st), ICICLE_ALLOCATION_FAILED);
-      HIP_TRY(hipMemcpyAsync(buf.ptr(), p, bytes, hipMemcpyHostToDevice, st), ICICLE_COPY_FAILED);
-      dev = buf.as<uint32_t>();
-      return ICICLE_SUCCESS;
-    }
-  };
-
-  static inline icicle_error_t finish_out(void* output, uint32_t* d_out, bool on_device, bool is_async, size_t bytes, hipStream_t st)
-  {
-    if (!on_device) {
-      HIP_TRY(hipMemcpyAsync(output, d_out, bytes, hipMemcpyDeviceToHost, st), ICICLE_COPY_FAILED);
-      HIP_TRY(hipStreamSynchronize(st), ICICLE_SYNCHRONIZATION_FAILED);
-    } else if (!is_async) {
-      HIP_TRY(hipStreamSynchronize(st), ICICLE_SYNCHRONIZATION_FAILED);
-    }
-    return ICICLE_SUCCESS;
-  }
 
 } // namespace icicle_hip

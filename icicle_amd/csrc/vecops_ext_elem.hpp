@@ -10,12 +10,11 @@
 // norm() goes down the tower x^2 = y, y^2 = W to the base field and conj_times() is the numerator of the inverse:
 // a^-1 = conj_times(a) / norm(a). Everything here is host and device code: tests/vecops_ext_host_harness.cpp runs it under g++.
 #pragma once
+#include "vecops_op.h"
 #include "smallfield.hpp"
 #include "goldfield.hpp"
 
 namespace icicle_hip {
-
-  enum { XOP_ADD = 0, XOP_SUB = 1, XOP_MUL = 2 }; // the values of VOP_* in vecops_elem.hpp
 
   struct Ext4 {
     uint32_t c[4];
@@ -78,8 +77,8 @@ namespace icicle_hip {
     // canonical in, canonical out. A product first lifts b to b R and W b R (seven independent reductions), then a * (b R) / R
     static SF_HD T apply(int op, const T& a, const T& b)
     {
-      if (op == XOP_ADD) return sum(a, b);
-      if (op == XOP_SUB) return diff(a, b);
+      if (op == VOP_ADD) return sum(a, b);
+      if (op == VOP_SUB) return diff(a, b);
       const uint32_t r2 = PR::R2, w = wr2();
       const T bm = mul_base_raw(b, r2);
       return mul_core(a, bm, S::mul(b.c[1], w), S::mul(b.c[2], w), S::mul(b.c[3], w));
@@ -153,8 +152,8 @@ namespace icicle_hip {
     static HD T scale_pow(const T& a, uint64_t) { return a; }
     static HD T apply(int op, const T& a, const T& b)
     {
-      if (op == XOP_ADD) return sum(a, b);
-      if (op == XOP_SUB) return diff(a, b);
+      if (op == VOP_ADD) return sum(a, b);
+      if (op == VOP_SUB) return diff(a, b);
       return mul_raw(a, b);
     }
     static HD T apply_mixed(const T& a, const BT& b) { return mul_base_raw(a, b); }
@@ -177,5 +176,35 @@ namespace icicle_hip {
       return num;
     }
   };
+
+#if defined(__HIPCC__)
+  // Vec16<EL> is EL with one 16-byte access per element: what the kernels of vecops_tile.hpp are instantiated with where every
+  // device pointer of a call is 16-byte aligned (aligned16; a staging buffer always is). EL itself goes word by word.
+  template <class EL>
+  struct Vec16 : EL {
+    static __device__ __forceinline__ typename EL::T load(const uint32_t* p)
+    {
+      const uint4 v = *reinterpret_cast<const uint4*>(p);
+      const uint32_t w[4] = {v.x, v.y, v.z, v.w};
+      return EL::load(w);
+    }
+    static __device__ __forceinline__ void store(uint32_t* p, const typename EL::T& x)
+    {
+      uint32_t w[4];
+      EL::store(w, x);
+      *reinterpret_cast<uint4*>(p) = make_uint4(w[0], w[1], w[2], w[3]);
+    }
+    static __device__ __forceinline__ typename EL::BT load_base(const uint32_t* p)
+    {
+      if constexpr (EL::BW == 2) {
+        const uint2 v = *reinterpret_cast<const uint2*>(p);
+        const uint32_t w[2] = {v.x, v.y};
+        return EL::load_base(w);
+      } else {
+        return EL::load_base(p);
+      }
+    }
+  };
+#endif
 
 } // namespace icicle_hip

@@ -106,22 +106,18 @@ namespace icicle_hip {
     const bool columns = cfg->columns_batch && batch > 1;
     const size_t out_bytes = (size_t)size_out * batch * W * 4;
     Staged sa;
+    StagedOut so;
     ICICLE_TRY(sa.in(in, cfg->is_a_on_device, (size_t)size_in * batch * W * 4, st));
-    TempBuf d_out_tmp;
-    uint32_t* d_out = (uint32_t*)out;
-    if (!cfg->is_result_on_device) {
-      HIP_TRY(d_out_tmp.alloc(out_bytes, st), ICICLE_ALLOCATION_FAILED);
-      d_out = d_out_tmp.as<uint32_t>();
-    }
+    ICICLE_TRY(so.out(out, cfg->is_result_on_device, out_bytes, st));
     constexpr uintptr_t ALIGN = W * 4 < 16 ? W * 4 : 16;
-    const bool vec = (((uintptr_t)sa.dev | (uintptr_t)d_out) & (ALIGN - 1)) == 0;
+    const bool vec = (((uintptr_t)sa.dev | (uintptr_t)so.dev) & (ALIGN - 1)) == 0;
     const unsigned grid = (unsigned)std::min<uint64_t>(((uint64_t)size_out * batch + 255) / 256, 1u << 20);
     if (vec)
-      k_slice<W, true><<<grid, 256, 0, st>>>(sa.dev, d_out, offset, stride, size_in, size_out, batch, columns);
+      k_slice<W, true><<<grid, 256, 0, st>>>(sa.dev, so.dev, offset, stride, size_in, size_out, batch, columns);
     else
-      k_slice<W, false><<<grid, 256, 0, st>>>(sa.dev, d_out, offset, stride, size_in, size_out, batch, columns);
+      k_slice<W, false><<<grid, 256, 0, st>>>(sa.dev, so.dev, offset, stride, size_in, size_out, batch, columns);
     LAUNCH_CHECK("k_slice", st);
-    return finish_out(out, d_out, cfg->is_result_on_device, cfg->is_async, out_bytes, st);
+    return so.finish(cfg->is_async);
   }
 
   // ======================================================== highest_non_zero_idx ========================================================
@@ -208,15 +204,12 @@ namespace icicle_hip {
     const bool columns = cfg->columns_batch && batch > 1;
     const size_t out_bytes = (size_t)batch * sizeof(int64_t);
     Staged sa;
+    StagedOut so;
+    TempBuf partials;
     ICICLE_TRY(sa.in(in, cfg->is_a_on_device, (size_t)size * batch * W * 4, st));
-    TempBuf d_out_tmp, partials;
-    int64_t* d_out = out;
-    if (!cfg->is_result_on_device) {
-      HIP_TRY(d_out_tmp.alloc(out_bytes, st), ICICLE_ALLOCATION_FAILED);
-      d_out = d_out_tmp.as<int64_t>();
-    }
-    ICICLE_TRY(hnz_launch<W>(sa.dev, size, batch, columns, d_out, partials, st));
-    return finish_out(out, (uint32_t*)d_out, cfg->is_result_on_device, cfg->is_async, out_bytes, st);
+    ICICLE_TRY(so.out(out, cfg->is_result_on_device, out_bytes, st));
+    ICICLE_TRY(hnz_launch<W>(sa.dev, size, batch, columns, (int64_t*)so.dev, partials, st));
+    return so.finish(cfg->is_async);
   }
 
   // ================================================================ poly_eval ================================================================
@@ -328,21 +321,17 @@ namespace icicle_hip {
     hipStream_t st = (hipStream_t)cfg->stream;
     const bool columns = cfg->columns_batch && batch > 1;
     Staged sa, sb;
+    StagedOut so;
     ICICLE_TRY(sa.in(coeffs, cfg->is_a_on_device, c_bytes, st));
     ICICLE_TRY(sb.in(domain, cfg->is_b_on_device, d_bytes, st));
-    TempBuf d_out_tmp;
-    uint32_t* d_out = (uint32_t*)evals;
-    if (!cfg->is_result_on_device) {
-      HIP_TRY(d_out_tmp.alloc(out_bytes, st), ICICLE_ALLOCATION_FAILED);
-      d_out = d_out_tmp.as<uint32_t>();
-    }
+    ICICLE_TRY(so.out(evals, cfg->is_result_on_device, out_bytes, st));
     const uint64_t pairs = (uint64_t)domain_size * batch;
     const PolyEvalPlan plan = poly_eval_plan(coeffs_size, pairs, key);
     TempBuf vals[2];
     if (!plan.split) {
       const unsigned threads = domain_size <= 64 ? 64 : 256;
       const unsigned gx = (unsigned)std::min<uint64_t>((domain_size + threads - 1) / threads, 1u << 20);
-      k_poly_eval_point<EL><<<dim3(gx, std::min(batch, 65535u)), threads, 0, st>>>(sa.dev, sb.dev, d_out, coeffs_size, domain_size, batch, columns);
+      k_poly_eval_point<EL><<<dim3(gx, std::min(batch, 65535u)), threads, 0, st>>>(sa.dev, sb.dev, so.dev, coeffs_size, domain_size, batch, columns);
       LAUNCH_CHECK("k_poly_eval_point", st);
     } else {
       uint64_t n = coeffs_size;
@@ -359,9 +348,9 @@ namespace icicle_hip {
         }
         const unsigned grid = (unsigned)std::min<uint64_t>((pairs * chunks + 3) / 4, 1u << 20);
         if (level == 0)
-          k_poly_chunk<EL, true><<<grid, 256, 0, st>>>(sa.dev, nullptr, sb.dev, xpow, out_vals, d_out, n, C, chunks, pairs, domain_size, batch, columns);
+          k_poly_chunk<EL, true><<<grid, 256, 0, st>>>(sa.dev, nullptr, sb.dev, xpow, out_vals, so.dev, n, C, chunks, pairs, domain_size, batch, columns);
         else
-          k_poly_chunk<EL, false><<<grid, 256, 0, st>>>(nullptr, in_vals, sb.dev, xpow, out_vals, d_out, n, C, chunks, pairs, domain_size, batch, columns);
+          k_poly_chunk<EL, false><<<grid, 256, 0, st>>>(nullptr, in_vals, sb.dev, xpow, out_vals, so.dev, n, C, chunks, pairs, domain_size, batch, columns);
         LAUNCH_CHECK("k_poly_chunk", st);
         if (chunks == 1) break;
         xpow *= C; // no overflow: another level exists only while about coeffs_size / xpow > 1 values are left
@@ -369,7 +358,7 @@ namespace icicle_hip {
         n = chunks;
       }
     }
-    return finish_out(evals, d_out, cfg->is_result_on_device, cfg->is_async, out_bytes, st);
+    return so.finish(cfg->is_async);
   }
 
   // ============================================================== poly_division ==============================================================
@@ -527,13 +516,11 @@ namespace icicle_hip {
       tiles = std::max(tiles, poly_division_tiles(deg[k], deg[batch + k], POLY_DIV_TILE));
       max_db = std::max(max_db, deg[batch + k]);
     }
-    TempBuf d_q_tmp, d_r_tmp, lci;
-    uint32_t *d_q = (uint32_t*)q_out, *d_r = (uint32_t*)r_out;
-    if (!o_dev) {
-      HIP_TRY(d_q_tmp.alloc(q_bytes, st), ICICLE_ALLOCATION_FAILED);
-      HIP_TRY(d_r_tmp.alloc(r_bytes, st), ICICLE_ALLOCATION_FAILED);
-      d_q = d_q_tmp.as<uint32_t>(), d_r = d_r_tmp.as<uint32_t>();
-    }
+    StagedOut sq, sr;
+    TempBuf lci;
+    ICICLE_TRY(sq.out(q_out, o_dev, q_bytes, st));
+    ICICLE_TRY(sr.out(r_out, o_dev, r_bytes, st));
+    uint32_t *const d_q = sq.dev, *const d_r = sr.dev;
     const uint64_t init_total = ((uint64_t)r_size + q_size) * batch;
     if (init_total) {
       k_poly_div_init<W><<<(unsigned)std::min<uint64_t>((init_total + 255) / 256, 1u << 20), 256, 0, st>>>(sa.dev, d_r, d_q, num_size, r_size, q_size, batch, columns);
@@ -554,26 +541,13 @@ namespace icicle_hip {
         }
       }
     }
-    if (!o_dev) {
-      if (q_bytes) HIP_TRY(hipMemcpyAsync(q_out, d_q, q_bytes, hipMemcpyDeviceToHost, st), ICICLE_COPY_FAILED);
-      if (r_bytes) HIP_TRY(hipMemcpyAsync(r_out, d_r, r_bytes, hipMemcpyDeviceToHost, st), ICICLE_COPY_FAILED);
-      HIP_TRY(hipStreamSynchronize(st), ICICLE_SYNCHRONIZATION_FAILED);
-    } else if (!cfg->is_async) {
-      HIP_TRY(hipStreamSynchronize(st), ICICLE_SYNCHRONIZATION_FAILED);
-    }
-    return ICICLE_SUCCESS;
+    ICICLE_TRY(sq.copy_back());
+    return sr.finish(cfg->is_async); // one synchronisation for both results
   }
 
 } // namespace icicle_hip
 
 using namespace icicle_hip;
-
-#define GUARDED(expr)                                                                                                  \
-  try {                                                                                                                \
-    return (expr);                                                                                                     \
-  } catch (...) {                                                                                                      \
-    return ICICLE_INVALID_ARGUMENT;                                                                                    \
-  }
 
 #define DEFINE_VEC_POLY(NAME, EL)                                                                                      \
   extern "C" icicle_error_t NAME##_slice(const void* in, uint64_t offset, uint64_t stride, uint64_t size_in, uint64_t size_out, const icicle_vec_ops_config_t* c, void* o) \

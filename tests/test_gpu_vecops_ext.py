@@ -18,7 +18,7 @@ pytestmark = pytest.mark.gpu
 HERE = os.path.dirname(os.path.abspath(__file__))
 ALL = list(M.FIELDS)
 REDUCES = ("vector_sum", "vector_product")
-INV_MAX_GRID = 2048  # k_ext_inv launches at most this many blocks of four waves (one tile per wave at a time) and loops beyond
+INV_MAX_GRID = 2048  # k_vec_inv launches at most this many blocks of four waves (one tile per wave at a time) and loops beyond
 
 
 @functools.lru_cache(maxsize=None)

@@ -1,4 +1,5 @@
-// Host harness for icicle_amd/csrc/vecops_ext_elem.hpp: the element code a lane of vecops_ext.hip runs, compiled with plain g++.
+// Host harness for icicle_amd/csrc/vecops_ext_elem.hpp: the element code a lane of the shared kernels (k_vec2, k_vec_inv of
+// vecops_tile.hpp) and of vecops_ext.hip's k_ext_mixed_mul runs for an extension element, compiled with plain g++.
 //
 //   harness cases <file>            every line of <file> is one fixture case, "field op size batch columns a_hex b_hex|- out_hex"
 //                                   (tests/test_vecops_ext_cpu.py writes it from tests/golden/vecops_ext_vectors.json); each is
@@ -59,7 +60,7 @@ static std::vector<uint32_t> unhex(const std::string& s)
   return w;
 }
 
-// what k_ext_inv computes for one element: conj_times(a) / norm(a), times num where DIV
+// what k_vec_inv computes for one extension element (InvTile<> of vecops_ext.hip): conj_times(a) / norm(a), times num where DIV
 template <class EL>
 static typename EL::T inverse(const typename EL::T& den, const typename EL::T* num)
 {
@@ -81,9 +82,9 @@ static bool run_case(const std::string& op, uint64_t size, uint32_t batch, bool 
   auto at = [&](uint64_t j, uint64_t k) { return columns ? j * batch + k : k * size + j; };
   if (op == "vector_add" || op == "vector_sub" || op == "vector_mul" || op.rfind("scalar_", 0) == 0) {
     const bool a_scalar = op[0] == 's';
-    const int o = op.find("add") != std::string::npos ? XOP_ADD : op.find("sub") != std::string::npos ? XOP_SUB : XOP_MUL;
+    const int o = op.find("add") != std::string::npos ? VOP_ADD : op.find("sub") != std::string::npos ? VOP_SUB : VOP_MUL;
     for (uint64_t i = 0; i < total; i++) {
-      const uint64_t ai = !a_scalar ? i : (columns ? i % batch : i / size); // k_ext_vec2
+      const uint64_t ai = !a_scalar ? i : (columns ? i % batch : i / size); // k_vec2
       EL::store(&out[i * 4], EL::apply(o, EL::load(&a[ai * 4]), EL::load(&b[i * 4])));
     }
   } else if (op == "vector_mixed_mul") {
@@ -187,10 +188,10 @@ static int run_random(const char* field, uint64_t seed, int n, int emit)
   uint32_t one_w[4] = {1, 0, 0, 0}; // canonical 1 in either layout
   for (int i = 0; i < n; i++) {
     const T a = random_elem<EL>(), b = random_elem<EL>();
-    const T ab = EL::apply(XOP_MUL, a, b), ia = inverse<EL>(a, nullptr);
+    const T ab = EL::apply(VOP_MUL, a, b), ia = inverse<EL>(a, nullptr);
     uint32_t w[4], v[4];
     // a * inv(a) = 1 (zero has no inverse: inv gives zero)
-    EL::store(w, EL::apply(XOP_MUL, a, ia));
+    EL::store(w, EL::apply(VOP_MUL, a, ia));
     if (EL::is_zero(a) ? (w[0] | w[1] | w[2] | w[3]) != 0 : memcmp(w, one_w, 16) != 0) bad++, printf("BAD inverse %s %d\n", field, i);
     // a * conj_times(a) = norm(a), as representatives
     T c;
