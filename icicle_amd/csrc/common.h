@@ -390,6 +390,19 @@ namespace icicle_hip {
   icicle_error_t poseidon_launch_leaves(PoseidonHasher& h, const uint8_t* leaves, uint64_t chunk, uint64_t first, uint64_t n, uint64_t valid, const uint8_t* last,
                                         uint64_t es, uint8_t* out, hipStream_t st);
 
+  // ---- what hash.hip reads from poseidon2_wide.hip ----
+  // A Poseidon2 hasher over a 256-bit scalar field: round constants and the diagonal of M_I, derived on the host when the first
+  // hasher of a (field, t) is made (no device needed), and their copy in device memory, uploaded and kept as Poseidon's tables are.
+  struct Poseidon2WideHasher;
+  // field 0 = bn254, 1 = bls12_381, 2 = bls12_377, 3 = grumpkin, 4 = stark252; tag: 8 words canonical, or nullptr; nullptr for a
+  // width outside 2, 3, 4, 8 and for a tag >= p
+  std::shared_ptr<Poseidon2WideHasher> poseidon2_wide_make(int field, unsigned t, const uint32_t* tag);
+  // n messages of `len` bytes at in + i * stride -> n digests of 32 bytes at out; len a multiple of 32, in, stride and out of 4
+  icicle_error_t poseidon2_wide_launch_batch(Poseidon2WideHasher& h, const uint8_t* in, uint64_t len, uint64_t stride, uint64_t n, uint8_t* out, hipStream_t st);
+  // layer-0 chunks [first, first + n) of a tree whose leaves end inside or in front of them (ReadPadded of hash_readers.hpp)
+  icicle_error_t poseidon2_wide_launch_leaves(Poseidon2WideHasher& h, const uint8_t* leaves, uint64_t chunk, uint64_t first, uint64_t n, uint64_t valid,
+                                              const uint8_t* last, uint64_t es, uint8_t* out, hipStream_t st);
+
   // ---- dominant-kernel timing with hipEvents on the launch stream (bench.py roofline figure) ----
   struct KernelTimer {
     static bool enabled();

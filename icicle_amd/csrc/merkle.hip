@@ -76,7 +76,7 @@ namespace icicle_hip {
                              out[0] + n_full * p.layers[0].out, st));
     int fuse_from = 1; // first layer with no multi-chunk Blake3 layer and no Poseidon2 or Poseidon layer (k_merkle_top has no case for them) at or above it
     for (int j = 1; j < upto; j++)
-      if (t.hashers[j].multi_chunk(p.layers[j].chunk) || t.hashers[j].kind == HASH_POSEIDON2 || t.hashers[j].kind == HASH_POSEIDON) fuse_from = j + 1;
+      if (t.hashers[j].multi_chunk(p.layers[j].chunk) || hash_kind_is_field(t.hashers[j].kind)) fuse_from = j + 1;
     uint64_t n = count;
     for (int i = 1; i < upto; i++) {
       n /= p.arity(i);

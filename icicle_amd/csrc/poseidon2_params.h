@@ -83,10 +83,11 @@ namespace icicle_hip {
       }
       return c * c > ((unsigned __int128)1 << m_minus_1);
     }
-    inline bool rounds_suffice(uint32_t p, int t, int alpha, int r_f, int r_p)
+    // p enters only as n, its bit length, and lg = log2 p: poseidon2_wide_params.h calls this for the 256-bit primes
+    inline bool rounds_suffice(int n, double lg, int t, int alpha, int r_f, int r_p)
     {
-      const int n = bit_length(p), M = SECURITY_BITS;
-      const double lg = std::log2((double)p), log_a_2 = std::log(2.0) / std::log((double)alpha);
+      const int M = SECURITY_BITS;
+      const double log_a_2 = std::log(2.0) / std::log((double)alpha);
       int ceil_log_a_t = 0; // smallest k with alpha^k >= t
       for (int v = 1; v < t; v *= alpha)
         ceil_log_a_t++;
@@ -104,19 +105,23 @@ namespace icicle_hip {
       const uint64_t r = (uint64_t)t / 3, under = r * (r_f / 2) + r_p + alpha, over = (uint64_t)(r_f - 1) * t + r_p + r + under;
       return binomial_squared_exceeds(over, under, M - 1);
     }
-    inline void round_numbers(uint32_t p, int t, int alpha, int* r_f_out, int* r_p_out)
+    inline void round_numbers(int n, double lg, int t, int alpha, int* r_f_out, int* r_p_out)
     {
       long best_cost = -1;
       int best_f = 0, best_p = 0;
       for (int r_p = 1; r_p < 500; r_p++)
         for (int r_f = 4; r_f < 100; r_f += 2) {
-          if (!rounds_suffice(p, t, alpha, r_f, r_p)) continue;
+          if (!rounds_suffice(n, lg, t, alpha, r_f, r_p)) continue;
           const int f = r_f + 2, q = (int)std::ceil(1.075 * r_p);
           const long cost = (long)t * f + q;
           if (best_cost < 0 || cost < best_cost || (cost == best_cost && f < best_f)) best_cost = cost, best_f = f, best_p = q;
           break; // more full rounds beside the same partial rounds only cost more
         }
       *r_f_out = best_f, *r_p_out = best_p;
+    }
+    inline void round_numbers(uint32_t p, int t, int alpha, int* r_f_out, int* r_p_out)
+    {
+      round_numbers(bit_length(p), std::log2((double)p), t, alpha, r_f_out, r_p_out);
     }
 
     // ---- Grain ------------------------------------------------------------------------------------------------------------------------

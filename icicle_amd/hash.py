@@ -5,7 +5,7 @@ import ctypes
 
 import numpy as np
 
-from ._lib import lib, check, HashConfig, POSEIDON2_FIELDS, POSEIDON_FIELDS
+from ._lib import lib, check, HashConfig, POSEIDON2_FIELDS, POSEIDON2_WIDE_FIELDS, POSEIDON_FIELDS
 from .runtime import DeviceVec
 
 
@@ -19,9 +19,22 @@ def _ptr(x):
     return x.ctypes.data, False
 
 
+def _tag_words(domain_tag):
+    """a domain tag over a 256-bit field, an int or 8 words, as the 8 words the factories take; None stays None"""
+    if domain_tag is None:
+        return None
+    if isinstance(domain_tag, (int, np.integer)):
+        if not 0 <= int(domain_tag) < 1 << 256:
+            raise ValueError("a domain tag is one field element")
+        words = [int(domain_tag) >> (32 * i) & 0xFFFFFFFF for i in range(8)]
+    else:
+        words = [int(w) for w in np.asarray(domain_tag, dtype=np.uint32).reshape(8)]
+    return (ctypes.c_uint32 * 8)(*words)
+
+
 class Hasher:
-    """One of the four Keccak-f[1600] sponges, Blake2s-256, Blake3, Poseidon2 over a 31-bit field or Poseidon over a 256-bit scalar
-    field; `chunk` is the default message size in bytes (a Merkle layer's input size)."""
+    """One of the four Keccak-f[1600] sponges, Blake2s-256, Blake3, Poseidon2 over a 31-bit field or a 256-bit scalar field, or
+    Poseidon over a 256-bit scalar field; `chunk` is the default message size in bytes (a Merkle layer's input size)."""
 
     def __init__(self, handle, chunk):
         if not handle:
@@ -56,14 +69,19 @@ class Hasher:
     @classmethod
     def poseidon2(cls, field, t, domain_tag=None, input_size=0):
         """Poseidon2 of width t (2, 3, 4, 8, 12, 16, 20, 24) over "babybear" or "koalabear": messages and digests are uint32 canonical
-        residues, the digest one element. `input_size` is in elements, 0 = t (t - 1 beside a `domain_tag`, which is one element)."""
-        if field not in POSEIDON2_FIELDS:
-            raise ValueError(f"Poseidon2 is built over {POSEIDON2_FIELDS}, not {field!r}")
-        tag = None if domain_tag is None else ctypes.byref(ctypes.c_uint32(int(domain_tag)))
+        residues, the digest one element. `input_size` is in elements, 0 = t (t - 1 beside a `domain_tag`, which is one element).
+        Of width t (2, 3, 4, 8) over the scalar field of "bn254", "bls12_381", "bls12_377" or "grumpkin" or over "stark252": elements
+        are canonical residues of 8 little-endian uint32 words, the `domain_tag` an int or an array of 8 words."""
+        if field in POSEIDON2_WIDE_FIELDS:
+            es, tag = 32, _tag_words(domain_tag)
+        elif field in POSEIDON2_FIELDS:
+            es, tag = 4, None if domain_tag is None else ctypes.byref(ctypes.c_uint32(int(domain_tag)))
+        else:
+            raise ValueError(f"Poseidon2 is built over {POSEIDON2_FIELDS + POSEIDON2_WIDE_FIELDS}, not {field!r}")
         handle = getattr(lib, f"{field}_create_poseidon2_hasher")(t, tag, input_size)
         if not handle:
-            raise ValueError(f"Poseidon2 has no width {t}")
-        return cls(handle, 4 * (input_size or (t if domain_tag is None else t - 1)))
+            raise ValueError(f"Poseidon2 over {field} has no width {t}" + (" with this tag" if es == 32 and domain_tag is not None else ""))
+        return cls(handle, es * (input_size or (t if domain_tag is None else t - 1)))
 
     @classmethod
     def poseidon(cls, field, t, domain_tag=None, input_size=0):
@@ -72,15 +90,7 @@ class Hasher:
         the arity: t elements, or t - 1 beside a `domain_tag` (an int, or an array of 8 words); `input_size` is 0 or the arity."""
         if field not in POSEIDON_FIELDS:
             raise ValueError(f"Poseidon is built over {POSEIDON_FIELDS}, not {field!r}")
-        tag = None
-        if domain_tag is not None:
-            if isinstance(domain_tag, (int, np.integer)):
-                if not 0 <= int(domain_tag) < 1 << 256:
-                    raise ValueError("a domain tag is one field element")
-                words = [int(domain_tag) >> (32 * i) & 0xFFFFFFFF for i in range(8)]
-            else:
-                words = [int(w) for w in np.asarray(domain_tag, dtype=np.uint32).reshape(8)]
-            tag = (ctypes.c_uint32 * 8)(*words)
+        tag = _tag_words(domain_tag)
         handle = getattr(lib, f"{field}_create_poseidon_hasher")(t, tag, input_size)
         if not handle:
             raise ValueError(f"Poseidon over {field} has no width {t} with this tag and input size")

@@ -403,7 +403,8 @@ ICICLE_HIP_DECLARE_TRANSPOSE(stark252, matrix_transpose)
  * vectors, follows sumcheck.
  * Poseidon2 over BabyBear and KoalaBear hashes and builds trees through the same entry points (its factories follow the Blake ones).
  * Poseidon over the scalar fields of BN254, BLS12-381, BLS12-377 and Grumpkin does the same (its factories follow Poseidon2's).
- * Poseidon over the other fields and in sponge mode, Poseidon2 over the other fields, proof serialisation (Merkle, FRI and sumcheck) and the extension_ / rns_
+ * Poseidon2 over the same four fields and stark252, of width 2, 3, 4, 8, does the same (its factories follow Poseidon's).
+ * Poseidon over the other fields and in sponge mode, Poseidon2 over Goldilocks and M31, proof serialisation (Merkle, FRI and sumcheck) and the extension_ / rns_
  * variants of execute_program are not built.
  * ====================================================================================== */
 typedef struct {
@@ -464,6 +465,22 @@ icicle_hasher_handle_t bn254_create_poseidon_hasher(unsigned t, const uint32_t* 
 icicle_hasher_handle_t bls12_381_create_poseidon_hasher(unsigned t, const uint32_t* domain_tag, unsigned input_size);
 icicle_hasher_handle_t bls12_377_create_poseidon_hasher(unsigned t, const uint32_t* domain_tag, unsigned input_size);
 icicle_hasher_handle_t grumpkin_create_poseidon_hasher(unsigned t, const uint32_t* domain_tag, unsigned input_size);
+/* Poseidon2 (the same entry of the reference, built per field) of width t in {2, 3, 4, 8} over the scalar field of BN254, BLS12-381,
+ * BLS12-377 or Grumpkin or over stark252; NULL for any other width (the reference's tables for these fields end at 8) and for a
+ * tag >= p. S-box x^5 (x^11 for BLS12-377, x^3 for stark252), 8 full rounds, 56 / 56 / 56 / 57 partial rounds (37 for BLS12-377,
+ * 83 / 83 / 84 / 84 for stark252). Elements are 8 little-endian 32-bit words, canonical; the digest is one element (32 bytes:
+ * state[1]). domain_tag: NULL, or one element (8 words) that becomes state[0]. input_size and the exact-arity / sponge rule are
+ * those of the 31-bit factories above, counted in elements of 32 bytes. icicle_hasher_hash wants input_len % 32 == 0
+ * (INVALID_ARGUMENT otherwise, before the device is touched) and device operands 4-aligned; proof_of_work and
+ * proof_of_work_verify refuse these hashers (INVALID_ARGUMENT). alpha, the round numbers, the round constants and the internal
+ * matrix are derived from the specification when the first hasher of a (field, t) is created
+ * (icicle_amd/csrc/poseidon2_wide_params.h), on the host, and kept for the process; they are uploaded when a hasher of that
+ * pair first hashes on a device. */
+icicle_hasher_handle_t bn254_create_poseidon2_hasher(unsigned t, const uint32_t* domain_tag, unsigned input_size);
+icicle_hasher_handle_t bls12_381_create_poseidon2_hasher(unsigned t, const uint32_t* domain_tag, unsigned input_size);
+icicle_hasher_handle_t bls12_377_create_poseidon2_hasher(unsigned t, const uint32_t* domain_tag, unsigned input_size);
+icicle_hasher_handle_t grumpkin_create_poseidon2_hasher(unsigned t, const uint32_t* domain_tag, unsigned input_size);
+icicle_hasher_handle_t stark252_create_poseidon2_hasher(unsigned t, const uint32_t* domain_tag, unsigned input_size);
 /* config->batch messages of input_len bytes each, back to back (input_len = 0: the hasher's default chunk size; both 0:
  * INVALID_ARGUMENT); digests of 32 / 64 bytes back to back. Any length, any pointer alignment (Poseidon2: see its factories). */
 icicle_error_t icicle_hasher_hash(icicle_hasher_handle_t h, const uint8_t* input, uint64_t input_len, const icicle_hash_config_t* config, uint8_t* output); /* :22 */

@@ -21,6 +21,11 @@ messages of one permutation at t = 16 and t = 24, device to device, beside a dev
 over the same input, in interleaved rounds; and the build of a binary tree (leaf layer: a t = 16 sponge over 8 elements, upper layers:
 t = 2 compressions) beside a Blake3 tree over the same leaves. The registers and scratch of every kernel come from the library
 (tools/kernel_regs.py).
+--poseidon2 --p2-fields bn254 bls12_381 bls12_377 grumpkin stark252 times Poseidon2 over the 256-bit fields instead: per field batches of
+2^--log-batch (at most 2^18) two-to-one hashes at t = 3 beside a domain tag and of one permutation at t = 4, device to device, and the
+build of a binary tree of 2^--p2w-log-leaves leaves of 32 bytes with tagged t = 3 layers; in the same interleaved rounds Poseidon t = 3
+beside the same tag over the same input and the same leaves (where Poseidon is built: not over BLS12-381 at t = 3, not over
+stark252) and a device-to-device copy of the same input bytes. With --notes the lines go to that file as one code block.
 --poseidon times Poseidon over the scalar fields of BN254, BLS12-381, BLS12-377 and Grumpkin (profiles/poseidon_notes.md): batches of
 2^--log-batch messages of one permutation per built (field, t), device to device, as hashes/s and as Montgomery products/s beside two
 yardsticks of the same run -- the register-resident product rate behind icicle_hip_ubench_mixed_add and the plain 256-bit vector_mul;
@@ -31,6 +36,7 @@ usage: tools/hash_merkle_bench.py [--hash keccak256 [blake2s blake3]] [--log-bat
                                         [--fri-log-n 20 24] [--reps 5]
        tools/hash_merkle_bench.py --openings [--open-log-leaves 20] [--open-counts 200 4000] [--reps 5]
        tools/hash_merkle_bench.py --poseidon2 [--log-batch 20] [--p2-log-leaves 18] [--reps 5] [--notes profiles/poseidon2_notes.md]
+       tools/hash_merkle_bench.py --poseidon2 --p2-fields bn254 .. [--log-batch 18] [--p2w-log-leaves 14] [--reps 5] [--notes <file>]
        tools/hash_merkle_bench.py --poseidon [--log-batch 18] [--p1-log-leaves 16] [--reps 5] [--notes <file>]"""
 import argparse
 import ctypes
@@ -266,7 +272,7 @@ def openings_bench(a):
 
 def poseidon2_kernel_rows():
     """name -> (VGPRs, SGPRs, scratch bytes per lane) of every Poseidon2 kernel in the library"""
-    return kernel_rows("k_poseidon2_")
+    return kernel_rows(("k_poseidon2_batch<", "k_poseidon2_leaves<"))
 
 
 def kernel_rows(prefix):
@@ -291,7 +297,95 @@ def kernel_rows(prefix):
     return out
 
 
+def poseidon2_products(t, r_f, r_p, sbox):
+    """Montgomery products of one permutation as poseidon2_wide.hpp computes it: `sbox` per S-box (2, 3, 5 for x^3, x^5, x^11), t per
+    full round, one per partial round; at t = 4, 8 one more per element in M_I"""
+    return sbox * (t * r_f + r_p) + (t * r_p if t >= 4 else 0)
+
+
+def poseidon2_wide_bench(a, fields):
+    from icicle_amd import MerkleTreeConfig, runtime
+    from icicle_amd._lib import lib, check
+    from icicle_amd.hash import Hasher
+    from icicle_amd.merkle import MerkleTree
+    from icicle_amd.runtime import DeviceVec
+
+    runtime.set_device(0)
+    rng = np.random.default_rng(1)
+    logb, logl = min(a.log_batch, 18), a.p2w_log_leaves
+    n = 1 << logb
+    med = lambda t: t[len(t) // 2]
+    lines = []
+
+    def say(line):
+        print(line, flush=True)
+        lines.append(line)
+
+    # alpha's product count and the partial rounds at t = 3, 4 (tests/poseidon2_model_wide.py EXPECTED_ROUNDS)
+    rounds = {"bn254": (3, 56, 56), "grumpkin": (3, 56, 56), "bls12_381": (3, 56, 56), "bls12_377": (5, 37, 37), "stark252": (2, 83, 84)}
+    cfg = MerkleTreeConfig.default()
+    cfg.is_tree_on_device = True
+    for field in fields:
+        sbox, rp3, rp4 = rounds[field]
+        has_p1 = field in ("bn254", "bls12_377", "grumpkin")  # Poseidon t = 3 is built over these
+        d_in = DeviceVec.from_host(rng.integers(0, 1 << 26, 8 * 4 * n, dtype=np.uint64).astype(np.uint32))  # canonical: below 2^250
+        d_out, d_out1, d_copy = DeviceVec(32 * n), DeviceVec(32 * n), DeviceVec(32 * 4 * n)
+        h3, h4 = Hasher.poseidon2(field, 3, domain_tag=0), Hasher.poseidon2(field, 4)
+        p3 = Hasher.poseidon(field, 3, domain_tag=0) if has_p1 else None
+
+        def copy(nbytes):
+            check(lib.icicle_copy(d_copy.ptr, d_in.ptr, nbytes))
+            runtime.device_synchronize()
+
+        fns = [lambda: h3.hash(d_in, size=64, batch=n, out=d_out), lambda: copy(64 * n), lambda: h4.hash(d_in, size=128, batch=n, out=d_out), lambda: copy(128 * n)]
+        if p3:
+            fns.append(lambda: p3.hash(d_in, size=64, batch=n, out=d_out1))
+        ts = all_interleaved(fns, a.reps)
+        for t, size, hs, cp, rp in ((3, 64, ts[0], ts[1], rp3), (4, 128, ts[2], ts[3], rp4)):
+            prods = poseidon2_products(t, 8, rp, sbox)
+            say(f"poseidon2 {field} t={t} batch 2^{logb} x {size} B device->device: median {med(hs):.3f} ms ({hs[0]:.3f} .. {hs[-1]:.3f}), "
+                f"{n / med(hs) * 1e3:.3e} hashes/s, {prods} products per permutation | copy of the same bytes {med(cp):.3f} ms, poseidon2 / copy {med(hs) / med(cp):.1f}")
+        if p3:
+            say(f"poseidon {field} t=3 over the same 2^{logb} x 64 B: median {med(ts[4]):.3f} ms ({ts[4][0]:.3f} .. {ts[4][-1]:.3f}), "
+                f"{n / med(ts[4]) * 1e3:.3e} hashes/s | poseidon2 t=3 / poseidon t=3 {med(ts[0]) / med(ts[4]):.2f}")
+        else:
+            say(f"poseidon {field} t=3: not built, nothing to compare with")
+        p2_layers = [h3] * logl
+        p1_layers = [p3] * logl if p3 else None
+
+        def build(layers):
+            tree = MerkleTree(layers, 32)
+            tree.build(d_in, size=32 << logl, cfg=cfg)
+            tree.close()
+
+        fns = [lambda: build(p2_layers)] + ([lambda: build(p1_layers)] if p3 else [])
+        ts = all_interleaved(fns, a.reps)
+        hashes = (1 << logl) - 1
+        say(f"poseidon2 {field} merkle build 2^{logl} leaves x 32 B (t=3 with a tag, arity 2), {logl} layers, {hashes} hashes: median {med(ts[0]):.3f} ms "
+            f"({ts[0][0]:.3f} .. {ts[0][-1]:.3f}), {hashes / med(ts[0]) * 1e3:.3e} hashes/s"
+            + (f" | poseidon t=3 tree over the same leaves {med(ts[1]):.3f} ms, poseidon2 / poseidon {med(ts[0]) / med(ts[1]):.2f}" if p3 else ""))
+        for v in (d_in, d_out, d_out1, d_copy):
+            v.free()
+        for h in (h3, h4, p3):
+            if h:
+                h.close()
+    regs = kernel_rows("k_poseidon2_wide_")
+    for name in sorted(regs, key=lambda k: (k.split("<")[0], k.split("<")[1].split(",")[0], int(k.split(", ")[1].rstrip(">")))):
+        v, sg, scratch = regs[name]
+        say(f"{name}: {v} VGPRs, {sg} SGPRs, {scratch} B of scratch per lane")
+    if a.notes:
+        with open(a.notes, "w") as f:
+            f.write("```\n" + "\n".join(lines) + "\n```\n")
+
+
 def poseidon2_bench(a):
+    from icicle_amd._lib import POSEIDON2_WIDE_FIELDS
+
+    wide = [f for f in a.p2_fields if f in POSEIDON2_WIDE_FIELDS]
+    if wide:
+        if len(wide) != len(a.p2_fields):
+            sys.exit("--p2-fields: the 31-bit and the 256-bit fields are timed in runs of their own")
+        return poseidon2_wide_bench(a, wide)
     from icicle_amd import MerkleTreeConfig, runtime
     from icicle_amd._lib import lib, check
     from icicle_amd.hash import Hasher
@@ -311,6 +405,8 @@ def poseidon2_bench(a):
 
     primes = {"babybear": 0x78000001, "koalabear": 0x7F000001}
     for field, p in primes.items():
+        if field not in a.p2_fields:
+            continue
         for t in (16, 24):
             d_in = DeviceVec.from_host(rng.integers(0, p, t * n, dtype=np.uint64).astype(np.uint32))
             d_out, d_out32, d_copy = DeviceVec(4 * n), DeviceVec(32 * n), DeviceVec(4 * t * n)
@@ -442,6 +538,9 @@ def main():
     ap.add_argument("--poseidon", action="store_true")
     ap.add_argument("--p1-log-leaves", type=int, default=16)
     ap.add_argument("--p2-log-leaves", type=int, default=18)
+    ap.add_argument("--p2-fields", nargs="+", default=["babybear", "koalabear"],
+                    choices=["babybear", "koalabear", "bn254", "bls12_381", "bls12_377", "grumpkin", "stark252"])
+    ap.add_argument("--p2w-log-leaves", type=int, default=14)
     ap.add_argument("--notes", default=None)
     ap.add_argument("--openings", action="store_true")
     ap.add_argument("--open-log-leaves", type=int, default=20)
