@@ -362,7 +362,8 @@ API_SYMBOLS = (
     + ["icicle_hip_merkle_tree_get_proofs", "icicle_hip_merkle_tree_verify_batch"]
     + ["proof_of_work", "proof_of_work_verify"]
     + [f"{p}_{s}" for p in FRI_PREFIXES + FRI_WIDE_PREFIXES for s in FRI_FUNCTIONS]
-    + [f"{p}_{s}" for p in SUMCHECK_FIELDS for s in SUMCHECK_FUNCTIONS] + ["delete_program", "icicle_hip_sumcheck_time_rounds", "icicle_hip_sumcheck_round_times"]
+    + [f"{p}_{s}" for p in SUMCHECK_FIELDS for s in SUMCHECK_FUNCTIONS] + ["delete_program", "icicle_hip_sumcheck_time_rounds", "icicle_hip_sumcheck_round_times",
+                                                                         "icicle_hip_sumcheck_launch_info"]
     + [f"{p}_{s}" for p in SUMCHECK_FIELDS for s in PROGRAM_FUNCTIONS]
 )
 # hash / Merkle functions that return a handle, a size or a byte pointer (tests/test_abi.py's header scan sees only the return types
@@ -566,6 +567,7 @@ _void_pp = ctypes.POINTER(ctypes.c_void_p)
 lib.delete_program.argtypes = [ctypes.c_void_p]
 lib.icicle_hip_sumcheck_time_rounds.argtypes = [ctypes.c_bool]
 lib.icicle_hip_sumcheck_round_times.argtypes = [ctypes.POINTER(ctypes.c_double), ctypes.c_int, ctypes.POINTER(ctypes.c_int)]
+lib.icicle_hip_sumcheck_launch_info.argtypes = [ctypes.c_int, ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_int)]
 for _p in SUMCHECK_FIELDS:
     _prove_args = [ctypes.c_void_p, _void_pp, ctypes.c_uint64, ctypes.c_uint64, ctypes.c_void_p, ctypes.c_void_p, ctypes.POINTER(FFISumcheckTranscriptConfig),
                    ctypes.POINTER(SumcheckConfig)]

@@ -465,6 +465,10 @@ namespace icicle_hip {
     const uint32_t L = sumcheck_log2(n);
     ICICLE_TRY(bind_current_device());
     hipStream_t st = (hipStream_t)cfg->stream;
+    // ext "hip_sumcheck_max_grid" (int): fewer blocks per round launch, so that small sizes walk the grid more than once (a test
+    // hook). Absent or <= 0: SC_MAX_GRID, which is also the most, as the partials are sized by it.
+    const int grid_key = cfg->ext ? reinterpret_cast<const ConfigExt*>(cfg->ext)->get_int("hip_sumcheck_max_grid", 0) : 0;
+    const unsigned max_grid = grid_key <= 0 ? SC_MAX_GRID : std::min<unsigned>((unsigned)grid_key, SC_MAX_GRID);
 
     // T_0 where the caller has it when that is 16-byte aligned device memory, else a copy; T_r alternates between two scratch
     // tables of n / 2 and n / 4 elements per polynomial. The caller's polynomials are never written.
@@ -533,7 +537,7 @@ namespace icicle_hip {
         p.out[j] = !store ? nullptr : (r % 2 == 1 ? ta.out[j] : tb.out[j]);
       }
       const uint64_t items = (FA::W == 1 && r == 0 && g.predefined >= 0 && pairs > 1) ? pairs / 2 : pairs;
-      const unsigned grid = (unsigned)std::min<uint64_t>((items + block - 1) / block, SC_MAX_GRID);
+      const unsigned grid = (unsigned)std::min<uint64_t>((items + block - 1) / block, max_grid);
       elem* partials = d_partials.as<elem>();
       timer.begin(st);
       if (r == 0)
@@ -627,6 +631,14 @@ extern "C" icicle_error_t icicle_hip_sumcheck_round_times(double* ms, int capaci
   *rounds = (int)g_round_times.size();
   for (int i = 0; i < capacity && i < *rounds; i++)
     ms[i] = g_round_times[i];
+  return ICICLE_SUCCESS;
+}
+
+extern "C" icicle_error_t icicle_hip_sumcheck_launch_info(int predefined, int* block, int* max_grid)
+{
+  if (!block || !max_grid) return ICICLE_INVALID_POINTER;
+  *block = predefined ? SC_BLOCK : SC_INTERP_BLOCK;
+  *max_grid = (int)SC_MAX_GRID;
   return ICICLE_SUCCESS;
 }
 

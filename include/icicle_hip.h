@@ -742,6 +742,10 @@ ICICLE_HIP_DECLARE_SUMCHECK(bls12_381)
  * copies the last proof's times (milliseconds, at most `capacity` of them) and stores the number of rounds it has in *rounds */
 icicle_error_t icicle_hip_sumcheck_time_rounds(bool enable);
 icicle_error_t icicle_hip_sumcheck_round_times(double* ms, int capacity, int* rounds);
+/* backend-specific, for tests: a round launch has min(ceil(items / *block), *max_grid) blocks of *block lanes, which walk on over the
+ * items beyond; `predefined` non-zero for the predefined programs, 0 for user programs. SumcheckConfig.ext int
+ * "hip_sumcheck_max_grid" lowers the cap for one prove (absent or <= 0: *max_grid, larger values are clamped to it). Needs no device. */
+icicle_error_t icicle_hip_sumcheck_launch_info(int predefined, int* block, int* max_grid);
 
 /* ---- execute_program: include/icicle/vec_ops.h:404, src/vec_ops.cpp:566, src/program/program_c_api.cpp:35, :48. Over the fields that
  * have the symbol functions above. A program has nof_parameters parameters, each a vector of size * batch_size canonical elements

@@ -5,7 +5,8 @@ The method of mint_fri_vectors.py: the reference's sources are compiled where th
 is deleted afterwards -- the recipe of oracle/build_ref.sh (device + field library against oracle/shim) with -DSUMCHECK=ON and the
 program, symbol, hash and sumcheck sources, one library per field. Only data is recorded, per case: the polynomials, labels, seed,
 claimed sum and a description of the program (tests/sumcheck_model.py Program), and from the reference the round polynomials and the
-challenge vector. User programs are built through the reference's symbol ABI from that description. Needs the reference tree
+challenge vector. With --large: tests/golden/sumcheck_vectors_large.json, the cases of sumcheck_model.LARGE_CASES (2^20 and 2^21
+elements), whose inputs come from sumcheck_model.large_inputs and are recorded by seed and sha256 only. User programs are built through the reference's symbol ABI from that description. Needs the reference tree
 ($ICICLE_REFERENCE_DIR, default /root/reference), gcc and a C++17 compiler; the tests read only the JSON.
 """
 import ctypes
@@ -14,6 +15,7 @@ import os
 import subprocess
 import sys
 import tempfile
+import time
 
 import numpy as np
 
@@ -36,6 +38,7 @@ HASHERS = {"keccak256": "icicle_create_keccak_256", "keccak512": "icicle_create_
            "sha3_512": "icicle_create_sha3_512", "blake2s": "icicle_create_blake2s", "blake3": "icicle_create_blake3"}
 DEFAULT_LABELS = ["domain_separator_label", "round_poly_label", "round_challenge_label"]
 EMPTY_LABELS = ["", "", ""]
+LARGE_HASHER, LARGE_SEED, MODEL_CHECKED = "keccak256", 5, "bb_eq_l21"  # --large: transcript of every case of sm.LARGE_CASES
 
 AB, EQ = sm.Program(3, predefined=sm.AB_MINUS_C), sm.Program(4, predefined=sm.EQ_X_AB_MINUS_C)
 DEG1 = sm.Program(3, [["in", 0], ["in", 1], ["in", 2], ["add", 0, 1], ["sub", 3, 2]])  # x0 + x1 - x2
@@ -128,17 +131,10 @@ def reference_program(lib, field, program):
     return prog
 
 
-def run_case(lib, case, index):
-    name, field, program, L, hasher, labels, seed, fill = case
-    p, w = sm.FIELDS[field]
-    n, m = 1 << L, program.nof_inputs
-    rng = np.random.default_rng(2000 + index)
-    if fill is None:
-        polys = [[int.from_bytes(rng.bytes(40), "little") % p for _ in range(n)] for _ in range(m)]
-        polys[0][0], polys[-1][-1] = 0, p - 1
-    else:
-        polys = [[p - 1 if fill == "p-1" else 0] * n for _ in range(m)]
-    claimed = sm.claimed_sum(field, polys, program)
+def reference_proof(lib, name, field, program, arrays, n, claimed, hasher, labels, seed):
+    """(round polynomials, challenge vector) as ints from the reference's prover, which its own verifier accepts; arrays: flat uint32 words"""
+    w = sm.FIELDS[field][1]
+    m, L = program.nof_inputs, n.bit_length() - 1
     for f in list(HASHERS.values()) + [f"{field}_{s}" for s in ("sumcheck_create", "sumcheck_get_proof", "sumcheck_proof_get_round_poly_at",
                                                                 "create_predefined_returning_value_program", "create_input_symbol", "create_scalar_symbol")]:
         getattr(lib, f).restype = ctypes.c_void_p
@@ -146,7 +142,6 @@ def run_case(lib, case, index):
         getattr(lib, f).argtypes = [ctypes.c_uint64]
     th = ctypes.c_void_p(getattr(lib, HASHERS[hasher])(0))
     prog = reference_program(lib, field, program)
-    arrays = [words_of(field, t) for t in polys]
     table = (ctypes.c_void_p * m)(*[a.ctypes.data for a in arrays])
     seed_arr, claimed_arr = words_of(field, [seed]), words_of(field, [claimed])
     lab = [s.encode() for s in labels]
@@ -172,15 +167,76 @@ def run_case(lib, case, index):
     assert getattr(lib, f"{field}_sumcheck_proof_delete")(proof) == 0 and getattr(lib, f"{field}_sumcheck_delete")(sc) == 0
     lib.delete_program(prog)
     lib.icicle_hasher_delete(th)
+    return rps, ints_of(field, cvec)
+
+
+def run_case(lib, case, index):
+    name, field, program, L, hasher, labels, seed, fill = case
+    p, w = sm.FIELDS[field]
+    n, m = 1 << L, program.nof_inputs
+    rng = np.random.default_rng(2000 + index)
+    if fill is None:
+        polys = [[int.from_bytes(rng.bytes(40), "little") % p for _ in range(n)] for _ in range(m)]
+        polys[0][0], polys[-1][-1] = 0, p - 1
+    else:
+        polys = [[p - 1 if fill == "p-1" else 0] * n for _ in range(m)]
+    claimed = sm.claimed_sum(field, polys, program)
+    rps, challenges = reference_proof(lib, name, field, program, [words_of(field, t) for t in polys], n, claimed, hasher, labels, seed)
     hexes = lambda row: [f"{v:x}" for v in row]
     return {"name": name, "field": field, "log_n": L, "transcript_hash": hasher, "labels": labels, "seed": f"{seed:x}", "claimed_sum": f"{claimed:x}",
             "program": program.description(), "degree": program.degree(), "polys": [hexes(t) for t in polys], "round_polys": [hexes(r) for r in rps],
-            "challenges": hexes(ints_of(field, cvec))}
+            "challenges": hexes(challenges)}
+
+
+def run_large_case(lib, case):
+    """A case of sm.LARGE_CASES: the inputs come from sm.large_inputs and are recorded by their sha256 only."""
+    name, field, program, L, input_seed, _ = case
+    p, w = sm.FIELDS[field]
+    n = 1 << L
+    arrays = sm.large_inputs(field, program.nof_inputs, n, input_seed)
+    polys = [sm.ints_of_array(a, w) for a in arrays]
+    claimed = sm.claimed_sum(field, polys, program)
+    rps, challenges = reference_proof(lib, name, field, program, [np.ascontiguousarray(a).reshape(-1) for a in arrays], n, claimed, LARGE_HASHER, sm.LARGE_LABELS,
+                                      LARGE_SEED)
+    if name == MODEL_CHECKED:  # the model once at a large size: it and the reference agree, or nothing is written
+        t = time.time()
+        want = sm.prove(field, polys, claimed, program, LARGE_HASHER, tuple(s.encode() for s in sm.LARGE_LABELS), LARGE_SEED)
+        assert want == {"round_polys": rps, "challenges": challenges}, f"{name}: the model and the reference disagree"
+        print(f"{name}: the model agrees ({time.time() - t:.1f} s)")
+    hexes = lambda row: [f"{v:x}" for v in row]
+    return {"name": name, "field": field, "log_n": L, "transcript_hash": LARGE_HASHER, "labels": sm.LARGE_LABELS, "seed": f"{LARGE_SEED:x}", "input_seed": input_seed,
+            "input_sha256": sm.sha256_of(arrays), "claimed_sum": f"{claimed:x}", "program": program.description(), "degree": program.degree(),
+            "round_polys": [hexes(r) for r in rps], "challenges": hexes(challenges)}
+
+
+def mint_large():
+    cases, start = [], time.time()
+    with tempfile.TemporaryDirectory() as tmp:
+        for field in FIELD_IDS:
+            todo = [c for c in sm.LARGE_CASES if c[1] == field]
+            if not todo:
+                continue
+            lib = ctypes.CDLL(build(field, tmp))
+            for case in todo:
+                t = time.time()
+                cases.append(run_large_case(lib, case))
+                print(f"{case[0]} ok ({time.time() - t:.1f} s)")
+            del lib
+    order = [c[0] for c in sm.LARGE_CASES]
+    doc = {"source": "reference CPU backend through its C ABI (tests/golden/mint_sumcheck_vectors.py --large); inputs: tests/sumcheck_model.py large_inputs",
+           "cases": sorted(cases, key=lambda c: order.index(c["name"]))}
+    out = os.path.join(HERE, "sumcheck_vectors_large.json")
+    with open(out, "w") as f:
+        json.dump(doc, f, separators=(",", ":"))
+        f.write("\n")
+    print(f"{len(cases)} large cases, {os.path.getsize(out)} bytes, {time.time() - start:.1f} s with the builds")
 
 
 def main():
     if not os.path.isdir(REF):
         sys.exit(f"reference tree not found ({REF}): nothing minted")
+    if "--large" in sys.argv[1:]:
+        return mint_large()
     cases = []
     with tempfile.TemporaryDirectory() as tmp:
         for field in FIELD_IDS:

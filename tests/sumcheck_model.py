@@ -1,8 +1,12 @@
 """Python model of sumcheck as the reference's CPU backend computes it (backend/cpu/include/cpu_sumcheck.h, include/icicle/sumcheck/
 sumcheck.h, sumcheck_transcript.h, include/icicle/program/*.h): programs with their degree and variable count, the transcript bytes,
-the prover and the verifier. Elements are Python ints; tests/golden/sumcheck_vectors.json holds the reference's own proofs."""
+the prover and the verifier. Elements are Python ints; tests/golden/sumcheck_vectors.json holds the reference's own proofs, and
+tests/golden/sumcheck_vectors_large.json those of LARGE_CASES, whose inputs large_inputs() makes again from a seed (NumPy arrays)."""
+import hashlib
 import json
 import os
+
+import numpy as np
 
 from tests import blake_model as bm
 
@@ -201,3 +205,82 @@ def unhex(rows):
 
 def case_labels(case):
     return tuple(s.encode() for s in case["labels"])
+
+
+# ---- the large cases (tests/golden/sumcheck_vectors_large.json): inputs from a seed, recorded by their sha256 -------------------------
+# t = x0 + 5 used twice, and two more constants: (t t x1 - 7 t) + 0x77ffffff x2
+CONSTANTS = Program(3, [["in", 0], ["in", 1], ["in", 2], ["const", 5], ["add", 0, 3], ["mul", 4, 4], ["mul", 5, 1], ["const", 7], ["mul", 7, 4], ["sub", 6, 8],
+                        ["const", 0x77FFFFFF], ["mul", 10, 2], ["add", 9, 11]])
+LARGE_LABELS = ["domain_separator_label", "round_poly_label", "round_challenge_label"]
+# name, field, program, L, input seed, the rounds that walk: the smallest sizes at which a round launch without a forced cap (2048 blocks
+# of 128 lanes, of 64 for a user program) walks its grid a second time. Round 1 of bn254_eq_l20 has 2^18 pairs, exactly one full grid.
+LARGE_CASES = [
+    ("bb_eq_l21", "babybear", Program(4, predefined=EQ_X_AB_MINUS_C), 21, 2101, (0, 1)),
+    ("bn254_eq_l20", "bn254", Program(4, predefined=EQ_X_AB_MINUS_C), 20, 2102, (0,)),
+    ("bb_constants_l20", "babybear", CONSTANTS, 20, 2103, (0, 1)),
+]
+
+
+def round_items(field, predefined, L, r):
+    """what the lanes of round r's launch share out among them: the pairs of T_r, n / 2^(r+1) -- but half as many in round 0 of a predefined
+    program over a one-word field, where a lane takes two pairs with one 16-byte load"""
+    pairs = (1 << L) >> (r + 1)
+    return pairs // 2 if predefined and FIELDS[field][1] == 1 and r == 0 and pairs > 1 else pairs
+
+
+def large_inputs(field, nof_polys, n, seed):
+    """nof_polys uint32 arrays [n] (one word) or [n, 8] of uniform canonical elements from one generator, without a Python loop over the
+    elements; then polys[0][0] = 0 and polys[-1][-1] = p - 1. The mint script and the tests share it."""
+    p, w = FIELDS[field]
+    rng = np.random.default_rng(seed)
+    polys = []
+    for _ in range(nof_polys):
+        if w == 1:
+            polys.append(rng.integers(0, p, n, dtype=np.uint32))
+        else:
+            a = rng.integers(0, 1 << 32, size=(n, w), dtype=np.uint32)
+            a[:, w - 1] %= np.uint32(p >> (32 * (w - 1)))  # top word below p's top word: the value is below p
+            polys.append(a)
+    polys[0][0] = 0
+    polys[-1][-1] = p - 1 if w == 1 else np.array([((p - 1) >> (32 * i)) & 0xFFFFFFFF for i in range(w)], dtype=np.uint32)
+    return polys
+
+
+def sha256_of(arrays):
+    return [hashlib.sha256(np.ascontiguousarray(a, dtype="<u4").tobytes()).hexdigest() for a in arrays]
+
+
+def ints_of_array(a, w):
+    """a uint32 array [n] or [n, w] as Python ints"""
+    if w == 1:
+        return [int(v) for v in a.tolist()]
+    raw = np.ascontiguousarray(a, dtype="<u4").tobytes()
+    return [int.from_bytes(raw[i:i + 4 * w], "little") for i in range(0, len(raw), 4 * w)]
+
+
+def claimed_sum_u64(p, polys, program):
+    """sum of program(polys[..][i]) mod p for p < 2^31 in uint64 arithmetic: every product of two reduced values fits in 64 bits"""
+    assert p < 1 << 31
+    P = np.uint64(p)
+    x = [np.asarray(t, dtype=np.uint64) for t in polys]
+    if program.predefined is not None:
+        g = (x[0] * x[1] % P + P - x[2]) % P
+        if program.predefined == EQ_X_AB_MINUS_C:
+            g = g * x[3] % P
+    else:
+        v = []
+        for n in program.nodes:
+            if n[0] == "in":
+                v.append(x[n[1]])
+            elif n[0] == "const":
+                v.append(np.uint64(n[1] % p))
+            else:
+                a, b = v[n[1]], v[n[2]]
+                v.append((a + b if n[0] == "add" else a + P - b if n[0] == "sub" else a * b) % P)
+        g = v[-1]
+    return int(g.sum(dtype=np.uint64) % P)  # fewer than 2^33 terms below 2^31
+
+
+def load_large_fixtures():
+    with open(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "sumcheck_vectors_large.json")) as f:
+        return json.load(f)["cases"]

@@ -165,6 +165,21 @@ def test_montgomery_conversion_and_vector_ops(hip):
             assert np.array_equal(V.bit_reverse(FNAME, b, cfg), _ref_vec2(FNAME, "bit_reverse", None, b, size, batch, columns))
 
 
+@pytest.mark.parametrize("extension", [False, True], ids=["goldilocks", "goldilocks_extension"])
+def test_montgomery_conversion_beyond_the_capped_grid(hip, extension):
+    """k_convert_gold past its capped grid (tests/test_gpu_vecops.py states the cap of convert_small / convert_gold): the lanes' second
+    trip with a partial block at its end, both directions, host operands and a device operand in place"""
+    from tests.test_gpu_vecops import CONVERT_PAST_GRID, check_convert_past_the_grid, convert_edges
+
+    degree = 2 if extension else 1
+    count = -(-CONVERT_PAST_GRID // degree)
+    n = count * degree
+    x = rand_elems(np.random.default_rng(37), n)
+    for i, which in convert_edges(n):
+        x.view("<u8")[i] = (0, 1, F.p - 1)[which]
+    check_convert_past_the_grid(FNAME, x, count, extension)
+
+
 def test_golden(hip):
     import os
 

@@ -13,6 +13,7 @@ from tests import poly_ref as R
 
 pytestmark = pytest.mark.gpu
 INVALID_POINTER, INVALID_ARGUMENT = 3, 11
+GRID_Y_MAX = 65535  # k_hnz and k_poly_eval_point: one row of blocks per entry, at most this many (the most a launch can have); a block walks on
 HNZ_GRID = 1024 * 4096  # poly_plan.h: at most POLY_HNZ_MAX_CHUNKS blocks of POLY_HNZ_PER_BLOCK elements along an entry, longer chunks beyond
 
 
@@ -141,6 +142,34 @@ def test_highest_non_zero_idx_beyond_a_whole_grid_of_blocks(hip, f):
     assert list(R.ref_hnz(f, a, n)) == [HNZ_GRID]
 
 
+@pytest.mark.parametrize("size", [3, 65])
+@pytest.mark.parametrize("f", ["babybear", "bn254"])
+def test_highest_non_zero_idx_of_more_entries_than_rows_of_blocks(hip, f, size):
+    """GRID_Y_MAX + 4 entries: blocks 0 to 3 scan a second entry each, through the same LDS slots. Every answer from -1 to size - 1
+    occurs; entries 0, GRID_Y_MAX - 1, GRID_Y_MAX and the last have four different ones, -1 among them."""
+    from icicle_amd import vecops as V
+    from icicle_amd.runtime import DeviceVec
+
+    w = R.FIELDS[f]
+    batch = GRID_Y_MAX + 4
+    assert batch > GRID_Y_MAX
+    rng = np.random.default_rng(3331 + size)
+    deg = np.arange(batch, dtype=np.int64) % (size + 1) - 1
+    deg[[0, GRID_Y_MAX - 1, GRID_Y_MAX, batch - 1]] = [size - 1, 0, -1, 1]
+    j = np.arange(size)
+    below = (j[None, :] < deg[:, None]) & (rng.integers(0, 2, size=(batch, size)) == 1)  # some non-zero elements below the answer
+    arr = np.zeros((batch, size, w), np.uint32)
+    arr[:, :, w - 1] = (below | (j[None, :] == deg[:, None])).astype(np.uint32)  # multi-word fields: the low words are zero, the element is not
+    for columns in (False, True):
+        a = np.ascontiguousarray(arr.transpose(1, 0, 2) if columns else arr).reshape(-1, w)
+        assert np.array_equal(R.ref_hnz(f, a, size, batch, columns), deg)
+        got = V.highest_non_zero_idx(f, a, cfg_of(hip, batch, columns), size=size)
+        assert got.dtype == np.int64 and np.array_equal(got, deg), (f, size, columns, "host")
+        do = DeviceVec(8 * batch)
+        V.highest_non_zero_idx(f, DeviceVec.from_host(a), cfg_of(hip, batch, columns), size=size, out=do)
+        assert np.array_equal(do.to_host(dtype=np.int64), deg), (f, size, columns, "device")
+
+
 # ---- poly_eval -----------------------------------------------------------------------------------------------------------------------
 CHUNK = 16  # the forced chunk length of the split route
 
@@ -233,6 +262,30 @@ def test_poly_eval_one_point_of_a_long_polynomial(hip, f):
     dc = DeviceVec.from_host(coeffs)
     assert np.array_equal(V.poly_eval(f, dc, domain, coeffs_size=n), want)
     assert np.array_equal(V.poly_eval(f, dc, domain, coeffs_size=n, chunk=-1), want)
+
+
+@pytest.mark.parametrize("m", [1, 65])
+@pytest.mark.parametrize("f", ["babybear", "bn254"])
+def test_poly_eval_of_more_polynomials_than_rows_of_blocks(hip, f, m):
+    """the point route over GRID_Y_MAX + 4 polynomials of 3 coefficients: blocks of rows 0 to 3 evaluate a second polynomial each, at one
+    point (one wave per block) and at 65 (four waves, the last lanes idle)"""
+    from icicle_amd import vecops as V
+
+    p, w = R.modulus(f), R.FIELDS[f]
+    batch, n = GRID_Y_MAX + 4, 3
+    assert batch > GRID_Y_MAX
+    rng = np.random.default_rng(3343 + m)
+    coeffs = rand_words(rng, n * batch, f)
+    domain = rand_words(rng, m, f)
+    for columns in (False, True):
+        want = R.ref_eval(f, coeffs, n, domain, batch, columns)
+        got = V.poly_eval(f, coeffs, domain, cfg_of(hip, batch, columns), chunk=-1)
+        assert got.shape == want.shape and np.array_equal(got, want), (f, m, columns)
+        ci, di = R.ints(coeffs, w), R.ints(domain, w)
+        for k in (0, 3, 4, GRID_Y_MAX - 1, GRID_Y_MAX, batch - 1):  # and without the reference, where the trips meet
+            c = ci[k::batch][:n] if columns else ci[k * n:(k + 1) * n]
+            for e in (0, m - 1):
+                assert R.ints(got[e * batch + k if columns else k * m + e], w) == [M.horner(c, di[e], p)], (f, m, columns, k, e)
 
 
 # ---- poly_division -------------------------------------------------------------------------------------------------------------------

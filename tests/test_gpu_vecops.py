@@ -10,6 +10,9 @@ from tests.util import cached_points, points_to_array, rand_scalars, to_words
 
 pytestmark = pytest.mark.gpu
 BIG = ("bn254", "bls12_381", "bls12_377", "grumpkin", "stark252")  # 8-word scalars
+CONVERT_MAX_GRID, CONVERT_BLOCK = 8192, 256  # convert_small / convert_gold (csrc/vecops.hip) launch at most this many blocks of this many lanes, one
+#                                              field element (an extension element's component) per lane, and a lane walks on beyond them
+CONVERT_PAST_GRID = CONVERT_MAX_GRID * CONVERT_BLOCK + 257  # field elements: one full and one partial block of the second trip
 
 
 def directed_scalars(field):
@@ -67,6 +70,48 @@ def test_scalar_convert_montgomery(hip, field):
         xe = rng.integers(0, p, size=4 * 300, dtype=np.uint32)
         ge = V.scalar_convert_montgomery(field, xe, True, size=300, extension=True)
         assert np.array_equal(ge, ref.ref_convert_montgomery(field, f"{field}_extension_scalar_convert_montgomery", xe, 300, True))
+
+
+def convert_edges(n):
+    """(index, which of 0, 1, p - 1) around the first and the last element of either trip: every one of the four indices sees all three"""
+    cap = CONVERT_MAX_GRID * CONVERT_BLOCK
+    assert n > cap + CONVERT_BLOCK, "no second trip"
+    return [(0, 0), (1, 1), (2, 2), (cap - 3, 0), (cap - 2, 2), (cap - 1, 1), (cap, 2), (cap + 1, 0), (cap + 2, 1), (n - 3, 1), (n - 2, 0), (n - 1, 2)]
+
+
+def check_convert_past_the_grid(field, x, count, extension):
+    """both directions against the reference byte for byte, host operands and a device operand in place, and the round trip"""
+    from icicle_amd import vecops as V
+    from icicle_amd.runtime import DeviceVec
+
+    sym = f"{field}_extension_scalar_convert_montgomery" if extension else f"{field}_scalar_convert_montgomery"
+    to_ref = ref.ref_convert_montgomery(field, sym, x, count, True)
+    from_ref = ref.ref_convert_montgomery(field, sym, x, count, False)
+    assert np.array_equal(ref.ref_convert_montgomery(field, sym, to_ref, count, False), x)
+    got = V.scalar_convert_montgomery(field, x, True, size=count, extension=extension)
+    assert np.array_equal(got, to_ref)
+    assert np.array_equal(V.scalar_convert_montgomery(field, got, False, size=count, extension=extension), x)  # the round trip
+    assert np.array_equal(V.scalar_convert_montgomery(field, x, False, size=count, extension=extension), from_ref)
+    d = DeviceVec.from_host(x)
+    V.scalar_convert_montgomery(field, d, True, out=d, size=count, extension=extension)
+    assert np.array_equal(d.to_host(shape=x.shape), to_ref)
+    V.scalar_convert_montgomery(field, d, False, out=d, size=count, extension=extension)
+    assert np.array_equal(d.to_host(shape=x.shape), x)
+    V.scalar_convert_montgomery(field, d, False, out=d, size=count, extension=extension)
+    assert np.array_equal(d.to_host(shape=x.shape), from_ref)
+
+
+@pytest.mark.parametrize("field, extension", [("babybear", False), ("koalabear", False), ("babybear", True)], ids=["babybear", "koalabear", "babybear_extension"])
+def test_scalar_convert_beyond_the_capped_grid(hip, field, extension):
+    """k_convert_small past CONVERT_MAX_GRID blocks: the lanes' second trip, with a partial block at its end"""
+    p = pyref.NTT_FIELDS[field].p
+    degree = 4 if extension else 1
+    count = -(-CONVERT_PAST_GRID // degree)  # elements; rounded up, so that the components stay above the cap
+    n = count * degree
+    x = np.random.default_rng(31).integers(0, p, size=n, dtype=np.uint32)
+    for i, which in convert_edges(n):
+        x[i] = (0, 1, p - 1)[which]
+    check_convert_past_the_grid(field, x, count, extension)
 
 
 @pytest.mark.parametrize("cname", ["bn254", "bls12_381", "bls12_377", "grumpkin"])

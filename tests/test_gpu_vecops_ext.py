@@ -18,6 +18,7 @@ pytestmark = pytest.mark.gpu
 HERE = os.path.dirname(os.path.abspath(__file__))
 ALL = list(M.FIELDS)
 REDUCES = ("vector_sum", "vector_product")
+GRID_Y_MAX = 65535  # reduce_run launches at most this many rows of blocks (one per entry; per 64 entries in the along_k form); a block walks on
 INV_MAX_GRID = 2048  # k_vec_inv launches at most this many blocks of four waves (one tile per wave at a time) and loops beyond
 
 
@@ -263,6 +264,32 @@ def test_sum_and_product(hip, f):
         ea = M.from_words(f, a)
         for op in REDUCES:
             assert M.from_words(f, hip_op(f, op, a, size=7, batch=3, columns=columns)) == M.run(f, op, ea, None, 7, 3, columns)
+
+
+@pytest.mark.parametrize("size", [3, 65])
+def test_sum_and_product_over_more_entries_than_rows_of_blocks(hip, size):
+    """GRID_Y_MAX + 4 entries of the babybear extension, rows layout (blocks 0 to 3 reduce a second entry; four waves and the LDS buffer at
+    size 65) and columns layout (the along_k form), host input and device input with a device result: every entry against the model in
+    its vectorised form (M.reduce_np), those where the trips meet against the model itself"""
+    from icicle_amd.runtime import DeviceVec
+
+    f = "babybear"
+    batch = GRID_Y_MAX + 4
+    assert batch > GRID_Y_MAX
+    a = rand_ext(np.random.default_rng(2243 + size), size * batch, f, nonzero=True)
+    d = DeviceVec.from_host(a)
+    spots = (0, 3, 4, GRID_Y_MAX - 1, GRID_Y_MAX, batch - 1)
+    for columns in (False, True):
+        for op in REDUCES:
+            want = M.reduce_np(f, op, a, size, batch, columns)
+            got = hip_op(f, op, a, size=size, batch=batch, columns=columns)
+            assert got.shape == (batch, 4) and np.array_equal(got, want), (op, size, columns, "host")
+            o = DeviceVec(16 * batch)
+            hip_op(f, op, d, size=size, batch=batch, columns=columns, out=o)
+            assert np.array_equal(o.to_host(shape=(batch, 4)), want), (op, size, columns, "device")
+            for k in spots:
+                entry = M.from_words(f, a[k::batch][:size] if columns else a[k * size:(k + 1) * size])
+                assert M.from_words(f, got[k]) == M.run(f, op, entry, None, size, 1, False), (op, size, columns, k)
 
 
 # ---- 6. one size past the grid cap ---------------------------------------------------------------------------------------------------

@@ -17,6 +17,8 @@ from oracle import pyref
 pytestmark = pytest.mark.gpu
 FIELDS = {"babybear": 1, "koalabear": 1, "goldilocks": 2, "bn254": 8, "bls12_381": 8, "bls12_377": 8, "stark252": 8, "grumpkin": 8}  # words
 ALL = list(FIELDS)
+GRID_Y_MAX = 65535  # reduce_run launches one row of blocks per entry (per group of 64 entries in the along_k form), at most this many (the
+#                     most a launch can have), and a block walks on from entry k to entry k + gridDim.y
 INV_MAX_GRID = 2048  # k_vec_inv launches at most this many blocks of four waves (one tile per wave at a time) and loops beyond
 
 
@@ -353,3 +355,46 @@ def test_reductions_beyond_one_block_of_partials(hip, f):
     assert ints(V.vector_product(f, y), w) == [prod(yi)]
     assert ints(V.vector_product(f, y, batch_cfg(hip, 4), size=m // 4), w) == [prod(yi[k * (m // 4):(k + 1) * (m // 4)]) for k in range(4)]
     assert ints(V.vector_product(f, y, batch_cfg(hip, 4, True), size=m // 4), w) == [prod(yi[k::4]) for k in range(4)]
+
+
+# ---- 7. more entries than the launch has rows of blocks -----------------------------------------------------------------------------
+@pytest.mark.parametrize("size", [3, 65])
+@pytest.mark.parametrize("f", ["babybear", "goldilocks", "bn254"])
+def test_reductions_over_more_entries_than_rows_of_blocks(hip, f, size):
+    """GRID_Y_MAX + 4 entries: the blocks of rows 0 to 3 reduce a second entry each. Rows layout: size 3 with one wave per block, size 65
+    with four waves, which share the LDS buffer between the two syncs inside the loop over the entries. Columns layout: the along_k form,
+    a lane per entry (its groups of 64 entries stay below the cap at this batch; the test below walks them)."""
+    from icicle_amd import vecops as V
+    from icicle_amd.runtime import DeviceVec
+
+    p, w = modulus(f), FIELDS[f]
+    batch = GRID_Y_MAX + 4
+    assert batch > GRID_Y_MAX  # a second trip, for entries 0 to 3
+    a = rand_words_nonzero(np.random.default_rng(1171 + size), size * batch, f)
+    d = DeviceVec.from_host(a)
+    for columns in (False, True):
+        for op, fn in (("vector_sum", V.vector_sum), ("vector_product", V.vector_product)):
+            want = ref_op(f, op, a, size=size, batch=batch, columns=columns)
+            got = fn(f, a, batch_cfg(hip, batch, columns), size=size)
+            assert got.shape == (batch, w) and np.array_equal(got, want), (f, op, size, columns, "host")
+            o = DeviceVec(4 * w * batch)
+            fn(f, d, batch_cfg(hip, batch, columns), size=size, out=o)
+            assert np.array_equal(o.to_host(shape=(batch, w)), want), (f, op, size, columns, "device")
+            if op == "vector_sum":  # and without the reference, where the trips meet
+                for k in (0, 3, 4, GRID_Y_MAX - 1, GRID_Y_MAX, batch - 1):
+                    entry = a[k::batch][:size] if columns else a[k * size:(k + 1) * size]
+                    assert ints(got[k], w) == [_column_sum(entry, p)], (f, size, columns, k)
+
+
+def test_column_reductions_over_more_groups_than_rows_of_blocks(hip):
+    """the along_k form past the cap: GRID_Y_MAX * 64 + 1 entries in columns layout, so group 0's block (four waves, the LDS buffer)
+    walks on to the group that holds the last entry alone; the second launch walks its own grid of 2^20 blocks as well"""
+    from icicle_amd import vecops as V
+
+    f, size = "babybear", 3
+    batch = GRID_Y_MAX * 64 + 1
+    assert (batch + 63) // 64 > GRID_Y_MAX
+    a = rand_words_nonzero(np.random.default_rng(1181), size * batch, f)
+    for op, fn in (("vector_sum", V.vector_sum), ("vector_product", V.vector_product)):
+        got = fn(f, a, batch_cfg(hip, batch, True), size=size)
+        assert np.array_equal(got, ref_op(f, op, a, size=size, batch=batch, columns=True)), op

@@ -2,7 +2,9 @@
 sumcheck_vectors.json) byte for byte, the host-only protocol code (icicle_amd/csrc/sumcheck_plan.h and program_plan.h through
 tests/sumcheck_host_harness.cpp, built with g++ plainly and with -fsanitize=address,undefined as a program of its own) against the
 model, and the C ABI's surface: header, library and binding agree, both structs have the reference's layout as the C compiler lays
-them out, and every argument error is returned before the device is touched."""
+them out, and every argument error is returned before the device is touched. The large fixtures (tests/golden/
+sumcheck_vectors_large.json): the generator reproduces the recorded inputs, every proof passes the model's verifier, and the claimed
+sums of the babybear cases are recomputed in 64-bit arithmetic."""
 import ctypes
 import os
 import random
@@ -390,3 +392,90 @@ def test_argument_errors_need_no_gpu(field):
     with pytest.raises(icicle_amd.IcicleError):
         sc.prove([p[: 6 * w] for p in polys[:4]], 0, eq, tcfg)
     del keep
+
+
+# ---- the large fixtures (tests/golden/sumcheck_vectors_large.json) and the launch figures ------------------------------------------
+LARGE = sm.load_large_fixtures()
+
+
+@pytest.fixture(scope="module")
+def large_inputs():
+    """the regenerated inputs of every large case, made once"""
+    return {c["name"]: sm.large_inputs(c["field"], sm.Program.from_description(c["program"]).nof_inputs, 1 << c["log_n"], c["input_seed"]) for c in LARGE}
+
+
+def test_large_fixtures_are_the_listed_cases():
+    assert [(c["name"], c["field"], c["log_n"], c["input_seed"]) for c in LARGE] == [(name, field, L, seed) for name, field, _, L, seed, _ in sm.LARGE_CASES]
+    for c, (_, _, program, _, _, _) in zip(LARGE, sm.LARGE_CASES):
+        assert c["program"] == program.description() and c["degree"] == program.degree() and c["labels"] == sm.LARGE_LABELS
+        assert len(c["round_polys"]) == c["log_n"] == len(c["challenges"]) and all(len(r) == c["degree"] + 1 for r in c["round_polys"])
+    assert os.path.getsize(os.path.join(HERE, "golden", "sumcheck_vectors_large.json")) < 64 * 1024
+
+
+@pytest.mark.parametrize("case", LARGE, ids=[c["name"] for c in LARGE])
+def test_large_generator_reproduces_the_recorded_inputs(case, large_inputs):
+    polys = large_inputs[case["name"]]
+    p, w = sm.FIELDS[case["field"]]
+    assert sm.sha256_of(polys) == case["input_sha256"]
+    assert all(a.dtype == np.uint32 and a.shape == ((1 << case["log_n"],) if w == 1 else (1 << case["log_n"], w)) for a in polys)
+    assert sm.ints_of_array(polys[0][:1], w) == [0] and sm.ints_of_array(polys[-1][-1:], w) == [p - 1]
+    if w == 1:
+        assert all(int(a.max()) < p for a in polys)
+    else:
+        assert all(int(a[:-1, w - 1].max()) < p >> (32 * (w - 1)) for a in polys)  # canonical; the last row of the last one is p - 1
+
+
+@pytest.mark.parametrize("case", LARGE, ids=[c["name"] for c in LARGE])
+def test_large_proofs_pass_the_models_verifier(case):
+    field, claimed, hasher, labels, seed = case_args(case)
+    p = sm.FIELDS[field][0]
+    rps = sm.unhex(case["round_polys"])
+    assert sm.verify(field, rps, claimed, hasher, labels, seed)
+    assert not sm.verify(field, rps, (claimed + 1) % p, hasher, labels, seed)
+    # the recorded challenges are the transcript's
+    tr = sm.Transcript(field, hasher, labels, seed, case["log_n"], case["degree"], claimed)
+    alphas = [0]
+    for r in range(case["log_n"] - 1):
+        alphas.append(tr.alpha(r, alphas[-1], rps[r]))
+    assert alphas == [int(v, 16) for v in case["challenges"]]
+
+
+@pytest.mark.parametrize("case", [c for c in LARGE if c["field"] == "babybear"], ids=[c["name"] for c in LARGE if c["field"] == "babybear"])
+def test_large_claimed_sums_recomputed_in_64_bits(case, large_inputs):
+    """R_0[0] + R_0[1] and the claimed sum against a sum over the regenerated inputs in uint64 arithmetic (p < 2^31)"""
+    p = sm.FIELDS["babybear"][0]
+    program = sm.Program.from_description(case["program"])
+    total = sm.claimed_sum_u64(p, large_inputs[case["name"]], program)
+    r0 = sm.unhex(case["round_polys"])[0]
+    assert total == int(case["claimed_sum"], 16) and (r0[0] + r0[1]) % p == total
+
+
+def test_claimed_sum_in_64_bits_equals_the_model():
+    p = sm.FIELDS["babybear"][0]
+    for _, _, program, _, seed, _ in sm.LARGE_CASES:
+        polys = sm.large_inputs("babybear", program.nof_inputs, 64, seed)
+        assert sm.claimed_sum_u64(p, polys, program) == sm.claimed_sum("babybear", [sm.ints_of_array(a, 1) for a in polys], program)
+
+
+def test_launch_info_is_declared_exported_and_bound():
+    from icicle_amd import _lib
+
+    text = re.sub(r"\s+", " ", subprocess.check_output(["gcc", "-E", "-P", os.path.join(ROOT, "include", "icicle_hip.h")], text=True))
+    m = re.search(r"icicle_error_t icicle_hip_sumcheck_launch_info\s*\(([^)]*)\)\s*;", text)
+    assert m and len(m.group(1).split(",")) == 3
+    assert "icicle_hip_sumcheck_launch_info" in _lib.API_SYMBOLS and len(_lib.lib.icicle_hip_sumcheck_launch_info.argtypes) == 3
+    figures = {}
+    for predefined in (0, 1, 2):
+        block, grid = ctypes.c_int(), ctypes.c_int()
+        assert _lib.lib.icicle_hip_sumcheck_launch_info(predefined, ctypes.byref(block), ctypes.byref(grid)) == 0
+        assert block.value >= 64 and block.value % 64 == 0 and grid.value >= 1
+        figures[predefined] = (block.value, grid.value)
+    assert figures[1] == figures[2] and figures[0][1] == figures[1][1]  # any non-zero value means predefined; one cap for both
+    assert _lib.lib.icicle_hip_sumcheck_launch_info(1, None, ctypes.byref(grid)) == INVALID_POINTER
+    assert _lib.lib.icicle_hip_sumcheck_launch_info(1, ctypes.byref(block), None) == INVALID_POINTER
+    # the large cases are large enough for these figures: more items than a full grid has lanes in the rounds that are to walk
+    for c, (_, _, _, _, _, walking) in zip(LARGE, sm.LARGE_CASES):
+        predefined = "predefined" in c["program"]
+        block, grid = figures[int(predefined)]
+        for r in walking:
+            assert sm.round_items(c["field"], predefined, c["log_n"], r) > block * grid, (c["name"], r)

@@ -228,3 +228,17 @@ def test_no_gpu_means_loud_failure_not_fallback():
                 fn(f, a, extension=True)
         with pytest.raises(icicle_amd.IcicleError):
             V.vector_mixed_mul(f, a, base)
+
+
+@pytest.mark.parametrize("f", ["babybear", "koalabear"])
+def test_the_vectorised_reductions_equal_the_model(f):
+    """M.reduce_np, which the GPU tests of 65539 entries compare with, against vsum / vproduct on small shapes, p - 1 and 0 among the values"""
+    p = M.modulus(f)
+    rng = np.random.default_rng(2251)
+    for size, batch in ((1, 1), (3, 5), (65, 3), (2, 70)):
+        a = rng.integers(0, p, size=(size * batch, 4), dtype=np.uint32)
+        a[0], a[-1] = p - 1, (0, p - 1, 0, 1)
+        ea = M.from_words(f, a)
+        for columns in (False, True):
+            for op in ("vector_sum", "vector_product"):
+                assert M.from_words(f, M.reduce_np(f, op, a, size, batch, columns)) == M.run(f, op, ea, None, size, batch, columns), (f, op, size, batch, columns)

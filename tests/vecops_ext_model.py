@@ -119,6 +119,30 @@ def vproduct(f, elems):
     return r
 
 
+def reduce_np(f, op, a, size, batch, columns):
+    """vector_sum / vector_product of `batch` entries of `size` elements each, given as [size * batch, 4] words of a field with a one-word
+    base field: vsum / vproduct above in uint64 arithmetic (p < 2^31, every product reduced before it is added), all entries at once.
+    Returns [batch, 4] words."""
+    assert BASE_WORDS[f] == 1 and op in ("vector_sum", "vector_product")
+    p, w, d = np.uint64(modulus(f)), np.uint64(NONRES[f]), DEGREE[f]
+    x = np.ascontiguousarray(a, np.uint32).reshape((size, batch, d) if columns else (batch, size, d)).astype(np.uint64)
+    rows = x.transpose(1, 0, 2) if columns else x  # [batch, size, d]
+    if op == "vector_sum":
+        return (rows.sum(axis=1) % p).astype(np.uint32)  # size < 2^33
+    acc = rows[:, 0, :].copy()
+    for j in range(1, size):
+        r = np.zeros_like(acc)
+        for i in range(d):
+            for k in range(d):
+                t = acc[:, i] * rows[:, j, k] % p
+                if i + k < d:
+                    r[:, i + k] += t
+                else:
+                    r[:, i + k - d] += w * t % p
+        acc = r % p
+    return acc.astype(np.uint32)
+
+
 # ---- memory layout ------------------------------------------------------------------------------------------------------------------
 def to_words(f, elems):
     """[n, 4] uint32"""
