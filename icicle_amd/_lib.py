@@ -386,6 +386,9 @@ POSEIDON2_HANDLE_SYMBOLS = {f"{f}_create_poseidon2_hasher": ctypes.c_void_p for 
 # the same entry over the 256-bit fields (elements of 32 bytes, widths 2, 3, 4, 8): a list of its own, POSEIDON2_FIELDS means 4-byte elements
 POSEIDON2_WIDE_FIELDS = ["bn254", "bls12_381", "bls12_377", "grumpkin", "stark252"]
 POSEIDON2_WIDE_HANDLE_SYMBOLS = {f"{f}_create_poseidon2_hasher": ctypes.c_void_p for f in POSEIDON2_WIDE_FIELDS}
+# and over Goldilocks (elements of 8 bytes, the eight widths of the 31-bit fields): again a list of its own
+POSEIDON2_GOLD_FIELDS = ["goldilocks"]
+POSEIDON2_GOLD_HANDLE_SYMBOLS = {f"{f}_create_poseidon2_hasher": ctypes.c_void_p for f in POSEIDON2_GOLD_FIELDS}
 # the Poseidon factories (poseidon_c_api.cpp), per scalar field: name -> restype
 POSEIDON_FIELDS = ["bn254", "bls12_381", "bls12_377", "grumpkin"]
 POSEIDON_HANDLE_SYMBOLS = {f"{f}_create_poseidon_hasher": ctypes.c_void_p for f in POSEIDON_FIELDS}
@@ -515,7 +518,7 @@ lib.icicle_hip_test_inject_failure.argtypes = [ctypes.c_int, ctypes.c_int]
 _size_p = ctypes.POINTER(ctypes.c_size_t)
 for _n in ("icicle_create_keccak_256", "icicle_create_keccak_512", "icicle_create_sha3_256", "icicle_create_sha3_512"):
     getattr(lib, _n).argtypes = [ctypes.c_uint64]
-for _s, _r in {**POSEIDON2_HANDLE_SYMBOLS, **POSEIDON2_WIDE_HANDLE_SYMBOLS, **POSEIDON_HANDLE_SYMBOLS}.items():
+for _s, _r in {**POSEIDON2_HANDLE_SYMBOLS, **POSEIDON2_WIDE_HANDLE_SYMBOLS, **POSEIDON2_GOLD_HANDLE_SYMBOLS, **POSEIDON_HANDLE_SYMBOLS}.items():
     getattr(lib, _s).restype = _r
     getattr(lib, _s).argtypes = [ctypes.c_uint, ctypes.POINTER(ctypes.c_uint32), ctypes.c_uint]
 lib.icicle_hasher_hash.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64, ctypes.POINTER(HashConfig), ctypes.c_void_p]

@@ -403,6 +403,18 @@ namespace icicle_hip {
   icicle_error_t poseidon2_wide_launch_leaves(Poseidon2WideHasher& h, const uint8_t* leaves, uint64_t chunk, uint64_t first, uint64_t n, uint64_t valid,
                                               const uint8_t* last, uint64_t es, uint8_t* out, hipStream_t st);
 
+  // ---- what hash.hip reads from poseidon2_gold.hip ----
+  // A Poseidon2 hasher over Goldilocks: parameters derived on the host when the first hasher of a width is made (no device
+  // needed), and their copy in device memory, uploaded and freed as a Poseidon2 hasher's is.
+  struct Poseidon2GoldHasher;
+  // tag: 2 words canonical, or nullptr; nullptr for a width outside 2, 3, 4, 8, 12, 16, 20, 24 and for a tag >= p
+  std::shared_ptr<Poseidon2GoldHasher> poseidon2_gold_make(unsigned t, const uint32_t* tag);
+  // n messages of `len` bytes at in + i * stride -> n digests of 8 bytes at out; in, stride, len and out multiples of 8
+  icicle_error_t poseidon2_gold_launch_batch(Poseidon2GoldHasher& h, const uint8_t* in, uint64_t len, uint64_t stride, uint64_t n, uint8_t* out, hipStream_t st);
+  // layer-0 chunks [first, first + n) of a tree whose leaves end inside or in front of them (ReadPadded of hash_readers.hpp)
+  icicle_error_t poseidon2_gold_launch_leaves(Poseidon2GoldHasher& h, const uint8_t* leaves, uint64_t chunk, uint64_t first, uint64_t n, uint64_t valid,
+                                              const uint8_t* last, uint64_t es, uint8_t* out, hipStream_t st);
+
   // ---- dominant-kernel timing with hipEvents on the launch stream (bench.py roofline figure) ----
   struct KernelTimer {
     static bool enabled();

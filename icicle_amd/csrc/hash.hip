@@ -2,7 +2,8 @@
 // runs (the tree itself is merkle.hip, which reaches this file through hash_merkle.h). The Blake compression and
 // absorb code is blake.hpp, the four message readers hash_readers.hpp (both also compile for the host); the kernels over them are below.
 // Poseidon2 over BabyBear and KoalaBear hashes through the same hasher and tree paths; its kernels and its state are poseidon2.hip.
-// Poseidon over the 256-bit scalar fields does the same through poseidon.hip, Poseidon2 over them through poseidon2_wide.hip.
+// Poseidon over the 256-bit scalar fields does the same through poseidon.hip, Poseidon2 over them through poseidon2_wide.hip,
+// Poseidon2 over Goldilocks through poseidon2_gold.hip.
 //
 // C ABI of the reference: icicle/src/hash/hash_c_api.cpp (icicle_create_keccak_256 .. icicle_create_blake3, icicle_hasher_hash),
 // include/icicle/hash/pow.h (proof_of_work, proof_of_work_verify); configs include/icicle/hash/hash_config.h, pow.h.
@@ -453,6 +454,7 @@ namespace icicle_hip {
     if (((uintptr_t)out & 7) == 0) flags |= HASH_OUT_ALIGNED8;
     if (h.kind == HASH_POSEIDON2) return poseidon2_launch_batch(*h.p2, in, len, stride, n, out, st);
     if (h.kind == HASH_POSEIDON2_WIDE) return poseidon2_wide_launch_batch(*h.p2w, in, len, stride, n, out, st);
+    if (h.kind == HASH_POSEIDON2_GOLD) return poseidon2_gold_launch_batch(*h.p2g, in, len, stride, n, out, st);
     if (h.kind == HASH_POSEIDON) return len == h.chunk ? poseidon_launch_batch(*h.p1, in, len, stride, n, out, st) : ICICLE_INVALID_ARGUMENT;
     if (h.kind != HASH_KECCAK) return launch_blake_batch(h, in, len, stride, n, a8, flags, out, st);
     if (h.rate_words == 17 && a8)
@@ -473,6 +475,7 @@ namespace icicle_hip {
     if (n == 0) return ICICLE_SUCCESS;
     if (h.kind == HASH_POSEIDON2) return poseidon2_launch_leaves(*h.p2, leaves, chunk, first, n, valid, last, es, out, st);
     if (h.kind == HASH_POSEIDON2_WIDE) return poseidon2_wide_launch_leaves(*h.p2w, leaves, chunk, first, n, valid, last, es, out, st);
+    if (h.kind == HASH_POSEIDON2_GOLD) return poseidon2_gold_launch_leaves(*h.p2g, leaves, chunk, first, n, valid, last, es, out, st);
     if (h.kind == HASH_POSEIDON) return chunk == h.chunk ? poseidon_launch_leaves(*h.p1, leaves, chunk, first, n, valid, last, es, out, st) : ICICLE_INVALID_ARGUMENT;
     if (h.kind != HASH_KECCAK) return launch_blake_leaves(h, leaves, chunk, first, n, valid, last, es, out, st);
     if (h.rate_words == 17)
@@ -506,6 +509,15 @@ namespace icicle_hip {
     return new (std::nothrow) Hasher{HASH_POSEIDON2_WIDE, 0, 0, 0, 32 * elems, nullptr, nullptr, std::move(p2w)};
   }
 
+  // the same over Goldilocks (poseidon2_gold.hip): elements of 8 bytes, the tag one element of two little-endian words
+  static Hasher* make_poseidon2_gold(unsigned t, const uint32_t* domain_tag, unsigned input_size)
+  {
+    std::shared_ptr<Poseidon2GoldHasher> p2g = poseidon2_gold_make(t, domain_tag);
+    if (!p2g) return nullptr;
+    const uint64_t elems = input_size ? input_size : (domain_tag ? t - 1 : t);
+    return new (std::nothrow) Hasher{HASH_POSEIDON2_GOLD, 0, 0, 0, 8 * elems, nullptr, nullptr, nullptr, std::move(p2g)};
+  }
+
   // <field>_create_poseidon_hasher: one permutation per message, so input_size is 0 or the arity (t, or t - 1 beside a domain tag)
   static Hasher* make_poseidon(int field, unsigned t, const uint32_t* domain_tag, unsigned input_size)
   {
@@ -523,6 +535,7 @@ namespace icicle_hip {
     if (len == 0) return ICICLE_INVALID_ARGUMENT;
     if (h->kind == HASH_POSEIDON2 && len % 4 != 0) return ICICLE_INVALID_ARGUMENT; // whole field elements
     if (h->kind == HASH_POSEIDON2_WIDE && len % 32 != 0) return ICICLE_INVALID_ARGUMENT;
+    if (h->kind == HASH_POSEIDON2_GOLD && len % 8 != 0) return ICICLE_INVALID_ARGUMENT;
     if (h->kind == HASH_POSEIDON && len != h->chunk) return ICICLE_INVALID_ARGUMENT; // one permutation: exactly the arity
     const uint64_t batch = cfg->batch;
     if (batch == 0) return ICICLE_SUCCESS;
@@ -732,6 +745,10 @@ icicle_hasher_handle_t babybear_create_poseidon2_hasher(unsigned t, const uint32
 icicle_hasher_handle_t koalabear_create_poseidon2_hasher(unsigned t, const uint32_t* domain_tag, unsigned input_size)
 {
   HASH_GUARDED((icicle_hasher_handle_t)make_poseidon2(1, t, domain_tag, input_size), nullptr)
+}
+icicle_hasher_handle_t goldilocks_create_poseidon2_hasher(unsigned t, const uint32_t* domain_tag, unsigned input_size)
+{
+  HASH_GUARDED((icicle_hasher_handle_t)make_poseidon2_gold(t, domain_tag, input_size), nullptr)
 }
 icicle_hasher_handle_t bn254_create_poseidon2_hasher(unsigned t, const uint32_t* domain_tag, unsigned input_size)
 {

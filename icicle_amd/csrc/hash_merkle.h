@@ -9,12 +9,13 @@
 
 namespace icicle_hip {
 
-  // Poseidon2: kernels and state in poseidon2.hip (31-bit fields) and poseidon2_wide.hip (256-bit fields), Poseidon: poseidon.hip
-  enum : int { HASH_KECCAK = 0, HASH_BLAKE2S = 1, HASH_BLAKE3 = 2, HASH_POSEIDON2 = 3, HASH_POSEIDON = 4, HASH_POSEIDON2_WIDE = 5 };
-  inline bool hash_kind_is_field(int kind) { return kind == HASH_POSEIDON2 || kind == HASH_POSEIDON || kind == HASH_POSEIDON2_WIDE; }
+  // Poseidon2: kernels and state in poseidon2.hip (31-bit fields), poseidon2_gold.hip (Goldilocks) and poseidon2_wide.hip (256-bit
+  // fields), Poseidon: poseidon.hip
+  enum : int { HASH_KECCAK = 0, HASH_BLAKE2S = 1, HASH_BLAKE3 = 2, HASH_POSEIDON2 = 3, HASH_POSEIDON = 4, HASH_POSEIDON2_WIDE = 5, HASH_POSEIDON2_GOLD = 6 };
+  inline bool hash_kind_is_field(int kind) { return kind == HASH_POSEIDON2 || kind == HASH_POSEIDON || kind == HASH_POSEIDON2_WIDE || kind == HASH_POSEIDON2_GOLD; }
 
   struct Hasher {
-    int kind;       // HASH_KECCAK, HASH_BLAKE2S, HASH_BLAKE3, HASH_POSEIDON2, HASH_POSEIDON, HASH_POSEIDON2_WIDE
+    int kind;       // HASH_KECCAK, HASH_BLAKE2S, HASH_BLAKE3, HASH_POSEIDON2, HASH_POSEIDON, HASH_POSEIDON2_WIDE, HASH_POSEIDON2_GOLD
     int rate_words; // Keccak only -- 17: 256-bit digest, 9: 512-bit digest
     int out_words;
     uint32_t suffix; // Keccak only -- 0x01 Keccak, 0x06 SHA3
@@ -22,7 +23,8 @@ namespace icicle_hip {
     std::shared_ptr<Poseidon2Hasher> p2; // Poseidon2 only -- field, width, tag and constants, shared with the trees that copy this hasher
     std::shared_ptr<PoseidonHasher> p1;  // Poseidon only -- the same; `chunk` is the only message length it hashes
     std::shared_ptr<Poseidon2WideHasher> p2w; // Poseidon2 over a 256-bit field only -- as p2, with elements and a digest of 32 bytes
-    uint64_t out_bytes() const { return kind == HASH_POSEIDON2 ? 4 : kind == HASH_KECCAK ? 8ull * out_words : 32; }
+    std::shared_ptr<Poseidon2GoldHasher> p2g; // Poseidon2 over Goldilocks only -- as p2, with elements and a digest of 8 bytes
+    uint64_t out_bytes() const { return kind == HASH_POSEIDON2 ? 4 : kind == HASH_POSEIDON2_GOLD ? 8 : kind == HASH_KECCAK ? 8ull * out_words : 32; }
     // Blake3 over more than one chunk: several launches and a buffer of chaining values; not for the fused top kernel
     bool multi_chunk(uint64_t len) const { return kind == HASH_BLAKE3 && len > BLAKE3_CHUNK; }
   };

@@ -5,17 +5,17 @@ import ctypes
 
 import numpy as np
 
-from ._lib import lib, check, HashConfig, POSEIDON2_FIELDS, POSEIDON2_WIDE_FIELDS, POSEIDON_FIELDS
+from ._lib import lib, check, HashConfig, POSEIDON2_FIELDS, POSEIDON2_WIDE_FIELDS, POSEIDON2_GOLD_FIELDS, POSEIDON_FIELDS
 from .runtime import DeviceVec
 
 
 def _ptr(x):
-    """(address, on device): NumPy uint8 / uint32 arrays are host memory, DeviceVec and raw addresses device memory"""
+    """(address, on device): NumPy uint8 / uint32 / uint64 arrays are host memory, DeviceVec and raw addresses device memory"""
     if isinstance(x, DeviceVec):
         return x.ptr, True
     if isinstance(x, int):
         return x, True
-    assert isinstance(x, np.ndarray) and x.dtype in (np.uint8, np.uint32) and x.flags["C_CONTIGUOUS"]
+    assert isinstance(x, np.ndarray) and x.dtype in (np.uint8, np.uint32, np.uint64) and x.flags["C_CONTIGUOUS"]
     return x.ctypes.data, False
 
 
@@ -33,8 +33,8 @@ def _tag_words(domain_tag):
 
 
 class Hasher:
-    """One of the four Keccak-f[1600] sponges, Blake2s-256, Blake3, Poseidon2 over a 31-bit field or a 256-bit scalar field, or
-    Poseidon over a 256-bit scalar field; `chunk` is the default message size in bytes (a Merkle layer's input size)."""
+    """One of the four Keccak-f[1600] sponges, Blake2s-256, Blake3, Poseidon2 over a 31-bit field, Goldilocks or a 256-bit scalar
+    field, or Poseidon over a 256-bit scalar field; `chunk` is the default message size in bytes (a Merkle layer's input size)."""
 
     def __init__(self, handle, chunk):
         if not handle:
@@ -71,17 +71,35 @@ class Hasher:
         """Poseidon2 of width t (2, 3, 4, 8, 12, 16, 20, 24) over "babybear" or "koalabear": messages and digests are uint32 canonical
         residues, the digest one element. `input_size` is in elements, 0 = t (t - 1 beside a `domain_tag`, which is one element).
         Of width t (2, 3, 4, 8) over the scalar field of "bn254", "bls12_381", "bls12_377" or "grumpkin" or over "stark252": elements
-        are canonical residues of 8 little-endian uint32 words, the `domain_tag` an int or an array of 8 words."""
+        are canonical residues of 8 little-endian uint32 words, the `domain_tag` an int or an array of 8 words.
+        "goldilocks" is refused here: its elements are a third size, and its call is `Hasher.poseidon2_goldilocks`."""
         if field in POSEIDON2_WIDE_FIELDS:
             es, tag = 32, _tag_words(domain_tag)
         elif field in POSEIDON2_FIELDS:
             es, tag = 4, None if domain_tag is None else ctypes.byref(ctypes.c_uint32(int(domain_tag)))
         else:
-            raise ValueError(f"Poseidon2 is built over {POSEIDON2_FIELDS + POSEIDON2_WIDE_FIELDS}, not {field!r}")
+            hint = "; Goldilocks has Hasher.poseidon2_goldilocks" if field in POSEIDON2_GOLD_FIELDS else ""
+            raise ValueError(f"Poseidon2 is built over {POSEIDON2_FIELDS + POSEIDON2_WIDE_FIELDS}, not {field!r}{hint}")
         handle = getattr(lib, f"{field}_create_poseidon2_hasher")(t, tag, input_size)
         if not handle:
             raise ValueError(f"Poseidon2 over {field} has no width {t}" + (" with this tag" if es == 32 and domain_tag is not None else ""))
         return cls(handle, es * (input_size or (t if domain_tag is None else t - 1)))
+
+    @classmethod
+    def poseidon2_goldilocks(cls, t, domain_tag=None, input_size=0):
+        """Poseidon2 of width t (2, 3, 4, 8, 12, 16, 20, 24) over Goldilocks, p = 2^64 - 2^32 + 1: messages and digests are uint64
+        canonical residues (or pairs of little-endian uint32 words), the digest one element of 8 bytes. `input_size` is in elements,
+        0 = t (t - 1 beside a `domain_tag`, which is one element: an int below p). A call of its own, not a field name of
+        `Hasher.poseidon2`: that one keeps refusing "goldilocks", as it did before this hash existed."""
+        tag = None
+        if domain_tag is not None:
+            if not 0 <= int(domain_tag) < 1 << 64:
+                raise ValueError("a domain tag is one field element")
+            tag = (ctypes.c_uint32 * 2)(int(domain_tag) & 0xFFFFFFFF, int(domain_tag) >> 32)
+        handle = lib.goldilocks_create_poseidon2_hasher(t, tag, input_size)
+        if not handle:
+            raise ValueError(f"Poseidon2 over goldilocks has no width {t}" + (" with this tag" if domain_tag is not None else ""))
+        return cls(handle, 8 * (input_size or (t if domain_tag is None else t - 1)))
 
     @classmethod
     def poseidon(cls, field, t, domain_tag=None, input_size=0):

@@ -80,7 +80,7 @@ def _leaves(leaves, size):
 
 class MerkleTree:
     """layer_hashers: one Hasher per layer, leaf layer first, each created with its layer's input chunk size; the layers may mix all
-    six byte hashers (Keccak / SHA3 256 and 512, Blake2s, Blake3); Poseidon2 layers (leaf elements of 4 bytes, digests of one
+    six byte hashers (Keccak / SHA3 256 and 512, Blake2s, Blake3); Poseidon2 layers (leaf elements of 4 bytes, 8 over Goldilocks, digests of one
     element) build, open and verify the same way, and so do Poseidon layers over the 256-bit scalar fields (leaf elements and
     digests of 32 bytes, arity t, or t - 1 beside a domain tag)"""
 

@@ -481,6 +481,17 @@ icicle_hasher_handle_t bls12_381_create_poseidon2_hasher(unsigned t, const uint3
 icicle_hasher_handle_t bls12_377_create_poseidon2_hasher(unsigned t, const uint32_t* domain_tag, unsigned input_size);
 icicle_hasher_handle_t grumpkin_create_poseidon2_hasher(unsigned t, const uint32_t* domain_tag, unsigned input_size);
 icicle_hasher_handle_t stark252_create_poseidon2_hasher(unsigned t, const uint32_t* domain_tag, unsigned input_size);
+/* Poseidon2 (the same entry of the reference, built for Goldilocks) of width t in {2, 3, 4, 8, 12, 16, 20, 24} over p = 2^64 - 2^32 + 1;
+ * NULL for any other width and for a tag >= p. S-box x^7, 8 full rounds, 27 / 23 / 21 partial rounds at t = 2, 3, 4 and 22 from
+ * t = 8 on. Elements are 8-byte canonical residues (two little-endian 32-bit words; an input word in [p, 2^64) is brought below
+ * p), the digest is one element (8 bytes: state[1]). domain_tag: NULL, or one element (2 words) that becomes state[0]. input_size
+ * and the exact-arity / sponge rule are those of the 31-bit factories above, counted in elements of 8 bytes. icicle_hasher_hash
+ * wants input_len % 8 == 0 (INVALID_ARGUMENT otherwise, before the device is touched) and device operands 8-aligned;
+ * proof_of_work and proof_of_work_verify refuse these hashers (INVALID_ARGUMENT). alpha, the round numbers, the round constants
+ * and the internal matrix are derived from the specification when the first hasher of a width is created
+ * (icicle_amd/csrc/poseidon2_gold_params.h), on the host, and kept for the process; they are uploaded when the hasher first
+ * hashes on a device and freed with the hasher and the trees that copied it. */
+icicle_hasher_handle_t goldilocks_create_poseidon2_hasher(unsigned t, const uint32_t* domain_tag, unsigned input_size);
 /* config->batch messages of input_len bytes each, back to back (input_len = 0: the hasher's default chunk size; both 0:
  * INVALID_ARGUMENT); digests of 32 / 64 bytes back to back. Any length, any pointer alignment (Poseidon2: see its factories). */
 icicle_error_t icicle_hasher_hash(icicle_hasher_handle_t h, const uint8_t* input, uint64_t input_len, const icicle_hash_config_t* config, uint8_t* output); /* :22 */

@@ -26,6 +26,11 @@ t = 2 compressions) beside a Blake3 tree over the same leaves. The registers and
 build of a binary tree of 2^--p2w-log-leaves leaves of 32 bytes with tagged t = 3 layers; in the same interleaved rounds Poseidon t = 3
 beside the same tag over the same input and the same leaves (where Poseidon is built: not over BLS12-381 at t = 3, not over
 stark252) and a device-to-device copy of the same input bytes. With --notes the lines go to that file as one code block.
+--poseidon2 --p2-fields goldilocks times Poseidon2 over Goldilocks: per width (2, 3, 4, 8, 12, 16, 20, 24) batches of 2^--log-batch (at
+most 2^20) messages of t elements, device to device; the build of a binary tree of 2^--p2-log-leaves leaves of 8 bytes (leaves t = 2
+with input_size 1, nodes t = 2) and of a tree whose leaves are rows of 8 elements (leaves t = 12 with input_size 8, nodes t = 8 with
+input_size 2); in the same interleaved rounds the Keccak-256 and the Blake3 tree over the same leaves -- what Goldilocks FRI commits
+with otherwise -- and a device-to-device copy of the same bytes. With --notes the lines go to that file as one code block.
 --poseidon times Poseidon over the scalar fields of BN254, BLS12-381, BLS12-377 and Grumpkin (profiles/poseidon_notes.md): batches of
 2^--log-batch messages of one permutation per built (field, t), device to device, as hashes/s and as Montgomery products/s beside two
 yardsticks of the same run -- the register-resident product rate behind icicle_hip_ubench_mixed_add and the plain 256-bit vector_mul;
@@ -37,6 +42,7 @@ usage: tools/hash_merkle_bench.py [--hash keccak256 [blake2s blake3]] [--log-bat
        tools/hash_merkle_bench.py --openings [--open-log-leaves 20] [--open-counts 200 4000] [--reps 5]
        tools/hash_merkle_bench.py --poseidon2 [--log-batch 20] [--p2-log-leaves 18] [--reps 5] [--notes profiles/poseidon2_notes.md]
        tools/hash_merkle_bench.py --poseidon2 --p2-fields bn254 .. [--log-batch 18] [--p2w-log-leaves 14] [--reps 5] [--notes <file>]
+       tools/hash_merkle_bench.py --poseidon2 --p2-fields goldilocks [--log-batch 20] [--p2-log-leaves 18] [--reps 5] [--notes <file>]
        tools/hash_merkle_bench.py --poseidon [--log-batch 18] [--p1-log-leaves 16] [--reps 5] [--notes <file>]"""
 import argparse
 import ctypes
@@ -378,9 +384,85 @@ def poseidon2_wide_bench(a, fields):
             f.write("```\n" + "\n".join(lines) + "\n```\n")
 
 
-def poseidon2_bench(a):
-    from icicle_amd._lib import POSEIDON2_WIDE_FIELDS
+def poseidon2_gold_bench(a):
+    from icicle_amd import MerkleTreeConfig, runtime
+    from icicle_amd._lib import lib, check
+    from icicle_amd.hash import Hasher
+    from icicle_amd.merkle import MerkleTree
+    from icicle_amd.runtime import DeviceVec
 
+    runtime.set_device(0)
+    rng = np.random.default_rng(1)
+    logb, logl = min(a.log_batch, 20), a.p2_log_leaves
+    n, p = 1 << logb, (1 << 64) - (1 << 32) + 1
+    med = lambda t: t[len(t) // 2]
+    lines = []
+
+    def say(line):
+        print(line, flush=True)
+        lines.append(line)
+
+    r_p = {2: 27, 3: 23, 4: 21}  # 22 from t = 8 on; R_F = 8 (tests/poseidon2_model_gold.py EXPECTED_ROUNDS)
+    d_in = DeviceVec.from_host(rng.integers(0, p, 24 * n, dtype=np.uint64))
+    d_out, d_copy = DeviceVec(8 * n), DeviceVec(8 * 24 * n)
+    for t in (2, 3, 4, 8, 12, 16, 20, 24):
+        h = Hasher.poseidon2_goldilocks(t)
+
+        def copy():
+            check(lib.icicle_copy(d_copy.ptr, d_in.ptr, 8 * t * n))
+            runtime.device_synchronize()
+
+        ts = all_interleaved([lambda: h.hash(d_in, size=8 * t, batch=n, out=d_out), copy], a.reps)
+        prods = 4 * t * 8 + (4 + t) * r_p.get(t, 22)
+        say(f"poseidon2 goldilocks t={t} batch 2^{logb} x {8 * t} B device->device: median {med(ts[0]):.3f} ms ({ts[0][0]:.3f} .. {ts[0][-1]:.3f}), "
+            f"{n / med(ts[0]) * 1e3:.3e} hashes/s, {prods} products per permutation, {prods * n / med(ts[0]) * 1e3:.3e} products/s | "
+            f"copy of the same bytes {med(ts[1]):.3f} ms, poseidon2 / copy {med(ts[0]) / med(ts[1]):.1f}")
+        h.close()
+    cfg = MerkleTreeConfig.default()
+    cfg.is_tree_on_device = True
+    trees = (("leaves of 8 B (t=2 with input_size 1, then t=2)", 1, [Hasher.poseidon2_goldilocks(2, input_size=1)] + [Hasher.poseidon2_goldilocks(2)] * logl),
+             ("leaves of 8 elements (t=12 with input_size 8, then t=8 with input_size 2)", 8,
+              [Hasher.poseidon2_goldilocks(12, input_size=8)] + [Hasher.poseidon2_goldilocks(8, input_size=2)] * logl))
+    for what, elems, p2_layers in trees:
+        nbytes = 8 * elems << logl
+        k_layers = [Hasher.keccak256(8 * elems)] + [Hasher.keccak256(64)] * logl
+        b3_layers = [Hasher.blake3(8 * elems)] + [Hasher.blake3(64)] * logl
+
+        def build(layers):
+            tree = MerkleTree(layers, 8)
+            tree.build(d_in, size=nbytes, cfg=cfg)
+            tree.close()
+
+        def copy():
+            check(lib.icicle_copy(d_copy.ptr, d_in.ptr, nbytes))
+            runtime.device_synchronize()
+
+        ts = all_interleaved([lambda: build(p2_layers), lambda: build(k_layers), lambda: build(b3_layers), copy], a.reps)
+        hashes = (2 << logl) - 1
+        say(f"poseidon2 goldilocks merkle build 2^{logl} {what}, {logl + 1} layers, {hashes} hashes: median {med(ts[0]):.3f} ms "
+            f"({ts[0][0]:.3f} .. {ts[0][-1]:.3f}), {hashes / med(ts[0]) * 1e3:.3e} hashes/s | keccak256 tree over the same leaves {med(ts[1]):.3f} ms "
+            f"({ts[1][0]:.3f} .. {ts[1][-1]:.3f}) | blake3 tree {med(ts[2]):.3f} ms ({ts[2][0]:.3f} .. {ts[2][-1]:.3f}) | copy of the leaves {med(ts[3]):.3f} ms "
+            f"({ts[3][0]:.3f} .. {ts[3][-1]:.3f}) | poseidon2 / keccak256 {med(ts[0]) / med(ts[1]):.2f}, poseidon2 / blake3 {med(ts[0]) / med(ts[2]):.2f}")
+        for h in set(p2_layers + k_layers + b3_layers):
+            h.close()
+    for v in (d_in, d_out, d_copy):
+        v.free()
+    regs = kernel_rows("k_poseidon2_gold_")
+    for name in sorted(regs, key=lambda k: (k.split("<")[0], int(k.split("<")[1].rstrip(">")))):
+        v, sg, scratch = regs[name]
+        say(f"{name}: {v} VGPRs, {sg} SGPRs, {scratch} B of scratch per lane")
+    if a.notes:
+        with open(a.notes, "w") as f:
+            f.write("```\n" + "\n".join(lines) + "\n```\n")
+
+
+def poseidon2_bench(a):
+    from icicle_amd._lib import POSEIDON2_GOLD_FIELDS, POSEIDON2_WIDE_FIELDS
+
+    if any(f in POSEIDON2_GOLD_FIELDS for f in a.p2_fields):
+        if len(a.p2_fields) != 1:
+            sys.exit("--p2-fields: goldilocks is timed in a run of its own")
+        return poseidon2_gold_bench(a)
     wide = [f for f in a.p2_fields if f in POSEIDON2_WIDE_FIELDS]
     if wide:
         if len(wide) != len(a.p2_fields):
@@ -539,7 +621,7 @@ def main():
     ap.add_argument("--p1-log-leaves", type=int, default=16)
     ap.add_argument("--p2-log-leaves", type=int, default=18)
     ap.add_argument("--p2-fields", nargs="+", default=["babybear", "koalabear"],
-                    choices=["babybear", "koalabear", "bn254", "bls12_381", "bls12_377", "grumpkin", "stark252"])
+                    choices=["babybear", "koalabear", "bn254", "bls12_381", "bls12_377", "grumpkin", "stark252", "goldilocks"])
     ap.add_argument("--p2w-log-leaves", type=int, default=14)
     ap.add_argument("--notes", default=None)
     ap.add_argument("--openings", action="store_true")
