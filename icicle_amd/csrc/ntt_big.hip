@@ -498,20 +498,14 @@ namespace icicle_hip {
     for (int p = 0; p < P; p++) {
       const uint32_t* src = (p == 0) ? d_in : Wk;
       uint32_t* dst = (p == P - 1) ? d_out : Wk;
-      const uint64_t L = (uint64_t)1 << parts[p];
-      // tile of L x T elements (36 B each in LDS for the 256-bit fields), <= 72 KiB so that two blocks share a CU; runs
-      // of T elements are >= 128 B in HBM: T = 4 of 32 B, 16 of 8 B
-      uint32_t tmax = std::max(4, 32 / PR::NL32);
-      while (tmax > 1 && L * tmax * sizeof(fe) > 72 * 1024)
-        tmax >>= 1;
-      const PassDesc pd = make_pass(parts, P, p, n, dom.log_max, tmax);
-      const uint32_t tot = (uint32_t)(L * pd.T);
-      // one thread per 4-element group of a stage pair; goldilocks: per 16-element group of four stages (when the pass has four)
-      const unsigned threads = std::max(64u, std::min(512u, tot / ((PR::NL32 == 2 && parts[p] >= 4) ? 16 : 4)));
+      // tile width, block size and LDS bytes: ntt_plan.h (36 B per element in LDS for the 256-bit fields; runs of T elements are
+      // >= 128 B in HBM: T = 4 of 32 B, 16 of 8 B)
+      const BigPass bp = big_pass_geometry(parts, P, p, n, dom.log_max, (uint32_t)sizeof(fe), (uint32_t)std::max(4, 32 / PR::NL32), PR::NL32 == 2);
+      const PassDesc& pd = bp.pd;
       for (uint32_t r0 = 0; r0 < nl.nbatch; r0 += 65535) {
         NttLaunch ns = nl;
         ns.row0 = r0;
-        k_big_ntt_pass<PR><<<dim3(pd.ntiles, std::min<uint32_t>(65535, nl.nbatch - r0)), threads, (size_t)tot * sizeof(fe), st>>>(src, dst, dom.tw, d_pw.as<uint32_t>(), pd, ns, ninv);
+        k_big_ntt_pass<PR><<<dim3(pd.ntiles, std::min<uint32_t>(65535, nl.nbatch - r0)), bp.threads, (size_t)bp.lds_bytes, st>>>(src, dst, dom.tw, d_pw.as<uint32_t>(), pd, ns, ninv);
       }
       LAUNCH_CHECK("k_big_ntt_pass", st);
     }

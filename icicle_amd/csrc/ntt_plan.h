@@ -181,6 +181,33 @@ namespace icicle_hip {
     return pd;
   }
 
+  // ---- launch geometry of one pass of the 256-bit / Goldilocks NTT (ntt_big.hip big_ntt_run), host-callable so that
+  // tests/plan_harness.cpp checks the very same code. elem_bytes: an element in LDS (36 B: 9 limbs of a 256-bit field, 8 B: goldilocks);
+  // tcap: the widest tile (runs of >= 128 B in HBM: 4 elements of 32 B, 16 of 8 B); radix16: goldilocks' four stages per LDS trip.
+  struct BigPass {
+    PassDesc pd;
+    uint32_t tmax;      // widest tile the LDS budget allows for 2^parts[p] rows
+    uint32_t tot;       // elements of a tile, L * pd.T
+    uint32_t threads;   // blockDim.x
+    uint64_t lds_bytes; // dynamic LDS of the launch
+  };
+  static inline BigPass big_pass_geometry(const int* parts, int P, int p, uint64_t n, int log_max, uint32_t elem_bytes, uint32_t tcap, bool radix16)
+  {
+    BigPass bp{};
+    const uint64_t L = (uint64_t)1 << parts[p];
+    // tile of L x T elements, <= 72 KiB so that two blocks share a CU
+    uint32_t tmax = tcap;
+    while (tmax > 1 && L * tmax * elem_bytes > 72 * 1024)
+      tmax >>= 1;
+    bp.tmax = tmax;
+    bp.pd = make_pass(parts, P, p, n, log_max, tmax);
+    bp.tot = (uint32_t)(L * bp.pd.T);
+    // one thread per 4-element group of a stage pair; goldilocks: per 16-element group of four stages (when the pass has four)
+    bp.threads = std::max(64u, std::min(512u, bp.tot / ((radix16 && parts[p] >= 4) ? 16u : 4u)));
+    bp.lds_bytes = (uint64_t)bp.tot * elem_bytes;
+    return bp;
+  }
+
   // ---- the 31-bit NTT's plan (ntt.hip ntt_run), host-callable so that tests/plan_harness.cpp checks the very same code ----------
   // Pass lengths: split_logn, then which pass takes the extra bit of a size that is not a multiple of three (`order` =
   // ICICLE_HIP_NTT_PARTS_ORDER, -1 = default). Measured (profiles/r05_ntt_big_parts.txt, 0 / 1 / 2 = first / last / middle): at 2^25

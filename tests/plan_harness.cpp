@@ -4,11 +4,15 @@
 #include "../icicle_amd/csrc/ntt_plan.h"
 #include "../icicle_amd/csrc/msm_plan.h"
 #include <cstdio>
+#include <future>
 #include <vector>
 #include <algorithm>
 using namespace icicle_hip;
 
-static int check(int logn, int smax, uint32_t tmax_cap, bool ntt31)
+// big_elem_bytes = 0: the 31-bit NTT (tile width by k_ntt_fast's rule, at most tmax_cap columns). Otherwise the pass geometry of
+// ntt_big.hip, from the function big_ntt_run launches with (ntt_plan.h big_pass_geometry): big_elem_bytes per element in LDS, tiles of at
+// most tmax_cap columns, radix16 for goldilocks' four stages per LDS trip. walk = false: the geometry assertions only, no bijection walk.
+static int check(int logn, int smax, uint32_t tmax_cap, bool ntt31, uint32_t big_elem_bytes = 0, bool radix16 = false, bool walk = true)
 {
   int parts[3], P;
   if (ntt31)
@@ -22,12 +26,35 @@ static int check(int logn, int smax, uint32_t tmax_cap, bool ntt31)
   const uint64_t n = 1ull << logn;
   for (int p = 0; p < P; p++) {
     const uint64_t L = 1ull << parts[p];
-    const uint64_t epb = L >= 16 ? 16 : L;
-    uint32_t tmax = (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>(tmax_cap, 512 * epb / L));
-    while (tmax > 1 && 2 * L * (tmax + 1) * 4 > 160 * 1024)
-      tmax >>= 1;
-    const PassDesc pd = make_pass(parts, P, p, n, /*log_max=*/logn, tmax);
+    PassDesc pd;
+    if (big_elem_bytes) {
+      const BigPass bp = big_pass_geometry(parts, P, p, n, /*log_max=*/logn, big_elem_bytes, tmax_cap, radix16);
+      pd = bp.pd;
+      const int s = parts[p];
+      if (bp.tot != L * (uint64_t)pd.T || bp.lds_bytes != (uint64_t)bp.tot * big_elem_bytes) return 50 + p;
+      if (bp.lds_bytes > 72 * 1024 || (uint32_t)pd.T > tmax_cap) return 50 + p; // two blocks share a CU's 160 KiB
+      if (bp.threads < 64 || bp.threads > 512 || (bp.threads & (bp.threads - 1)) != 0) return 60 + p; // __launch_bounds__(512)
+      if (bp.threads % (uint32_t)pd.T != 0) return 60 + p; // the goldilocks store: a thread stays in its column from trip to trip
+      // k_big_ntt_pass's stage loops: groups of 16 elements (goldilocks, while four stages remain), then of 4 (two stages), then
+      // of 2 (an odd last stage); every element of the tile must belong to exactly one group of each loop that runs
+      int q = 0;
+      if (radix16)
+        for (; q + 3 < s; q += 4)
+          if (bp.tot % 16 != 0) return 70 + p;
+      for (; q + 1 < s; q += 2)
+        if (bp.tot % 4 != 0) return 70 + p;
+      if (q < s && bp.tot % 2 != 0) return 70 + p;
+      // load and store walk e = tid, tid + blockDim, ...: whole trips (and the store's progression advances once per trip)
+      if (bp.tot >= bp.threads && bp.tot % bp.threads != 0) return 80 + p;
+    } else {
+      const uint64_t epb = L >= 16 ? 16 : L;
+      uint32_t tmax = (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>(tmax_cap, 512 * epb / L));
+      while (tmax > 1 && 2 * L * (tmax + 1) * 4 > 160 * 1024)
+        tmax >>= 1;
+      pd = make_pass(parts, P, p, n, /*log_max=*/logn, tmax);
+    }
     if (pd.T < 1 || (uint64_t)pd.ntiles * pd.T * L != n) return 10 + p;
+    if (!walk) continue;
     std::vector<uint8_t> in(n, 0), out(n, 0);
     for (uint32_t tile = 0; tile < pd.ntiles; tile++) {
       const uint32_t a = tile / pd.tiles_per_a, ct = tile % pd.tiles_per_a;
@@ -50,16 +77,35 @@ static int check(int logn, int smax, uint32_t tmax_cap, bool ntt31)
   return 0;
 }
 
-// max_logn: the 31-bit fields (up to 2^27, BabyBear's two-adicity: the 512-row passes from 2^25 up); max_logn_big: the 256-bit ones
+// max_logn: the 31-bit fields (up to 2^27, BabyBear's two-adicity: the 512-row passes from 2^25 up); max_logn_big: ntt_big.hip's fields
+// (256-bit: 36-byte LDS elements, tiles of at most 4 columns; goldilocks: 8-byte elements, at most 16 columns, four stages per trip).
+// The bijection walk stops at 2^27 (a walk touches every element of every pass); 2^28 gets the geometry assertions.
+// Failures: logn * 100 + code (31-bit), + 1000000 (256-bit), + 2000000 (goldilocks).
 extern "C" int plan_check(int max_logn, int max_logn_big)
 {
-  for (int logn = 1; logn <= std::max(max_logn, max_logn_big); logn++) {
-    if (logn <= max_logn)
-      if (int rc = check(logn, 8, 32, true)) return logn * 100 + rc; // 31-bit fields
-    if (logn <= max_logn_big)
-      if (int rc = check(logn, 8, 4, false)) return logn * 100 + rc; // 256-bit fields: tiles of at most 4 columns
-  }
-  return 0;
+  // the three families are independent: one thread each (the walks of the large sizes are the whole cost)
+  auto family = [=](int which) -> int {
+    for (int logn = 1; logn <= (which == 0 ? max_logn : max_logn_big); logn++) {
+      const bool walk = logn <= 27;
+      const int rc = which == 0 ? check(logn, 8, 32, true) : which == 1 ? check(logn, 8, 4, false, 36, false, walk) : check(logn, 8, 16, false, 8, true, walk);
+      if (rc) return which * 1000000 + logn * 100 + rc;
+    }
+    return 0;
+  };
+  std::future<int> f1 = std::async(std::launch::async, family, 1), f2 = std::async(std::launch::async, family, 2);
+  const int rc0 = family(0), rc1 = f1.get(), rc2 = f2.get();
+  return rc0 ? rc0 : rc1 ? rc1 : rc2;
+}
+
+// the geometry big_ntt_run launches pass p of a 2^logn transform with: out = s, T, ntiles, tot, threads, LDS bytes; returns the pass count
+extern "C" int big_pass_probe(int logn, int p, int elem_bytes, int tcap, int radix16, int* out)
+{
+  int parts[3], P;
+  split_logn(logn, 8, parts, &P);
+  if (p < 0 || p >= P) return -1;
+  const BigPass bp = big_pass_geometry(parts, P, p, 1ull << logn, logn, (uint32_t)elem_bytes, (uint32_t)tcap, radix16 != 0);
+  out[0] = bp.pd.s, out[1] = bp.pd.T, out[2] = (int)bp.pd.ntiles, out[3] = (int)bp.tot, out[4] = (int)bp.threads, out[5] = (int)bp.lds_bytes;
+  return P;
 }
 
 // ---- lane-native launch geometry (ntt_plan.h fast_pass_geometry, the code ntt_run launches with) -----------------------------

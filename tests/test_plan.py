@@ -1,5 +1,6 @@
 """CPU: the NTT pass decomposition (icicle_amd/csrc/ntt_plan.h) compiled for the host -- every pass covers a row exactly
-once and the last pass's scatter is a permutation, for every size up to 2^27 (31-bit fields) / 2^22 (256-bit fields); the
+once and the last pass's scatter is a permutation, for every size up to 2^27 (31-bit fields, 256-bit fields, goldilocks), the latter two
+with the tile width and block size ntt_big.hip launches with (big_pass_geometry: LDS bytes, blockDim % T, whole stage groups, up to 2^28); the
 lane-native launch geometry of interleaved transforms (ntt_plan.h fast_pass_geometry, what ntt_run launches) maps every
 logical element to the same word with and without column / outer-index groups."""
 import ctypes
@@ -16,13 +17,26 @@ def _lib():
     src = os.path.join(HERE, "plan_harness.cpp")
     hdrs = [os.path.join(HERE, "..", "icicle_amd", "csrc", h) for h in ("ntt_plan.h", "msm_plan.h")]
     if not os.path.exists(so) or max([os.path.getmtime(src)] + [os.path.getmtime(h) for h in hdrs]) > os.path.getmtime(so):
-        subprocess.check_call(["g++", "-std=c++17", "-O2", "-fPIC", "-shared", src, "-o", so])
+        subprocess.check_call(["g++", "-std=c++17", "-O2", "-fPIC", "-shared", "-pthread", src, "-o", so])
     return ctypes.CDLL(so)
 
 
 def test_ntt_plan_covers_every_slot_once():
     lib = _lib()
-    assert lib.plan_check(27, 22) == 0
+    assert lib.plan_check(27, 28) == 0
+    # the geometry ntt_big.hip launches with (ntt_plan.h big_pass_geometry), at the sizes where a pass gains rows: (rows, T, threads, LDS bytes)
+    # per pass. 2^25: the first 512-row pass, for a 256-bit field exactly the 72 KiB bound with 512 threads; 2^28: 1024 rows, the tile halves.
+    for logn, elem, tcap, r16, want in ((24, 36, 4, 0, [(8, 4, 256, 36864)] * 3), (25, 36, 4, 0, [(9, 4, 512, 73728), (8, 4, 256, 36864), (8, 4, 256, 36864)]),
+                                        (27, 36, 4, 0, [(9, 4, 512, 73728)] * 3), (28, 36, 4, 0, [(10, 2, 512, 73728), (9, 4, 512, 73728), (9, 4, 512, 73728)]),
+                                        (25, 8, 16, 1, [(9, 16, 512, 65536), (8, 16, 256, 32768), (8, 16, 256, 32768)]),
+                                        (28, 8, 16, 1, [(10, 8, 512, 65536), (9, 16, 512, 65536), (9, 16, 512, 65536)]), (3, 8, 16, 1, [(3, 1, 64, 64)])):
+        out = (ctypes.c_int * 6)()
+        got = []
+        for p in range(len(want)):
+            assert lib.big_pass_probe(logn, p, elem, tcap, r16, out) == len(want)
+            assert out[3] == (1 << out[0]) * out[1] and out[2] * out[3] == 1 << logn
+            got.append((out[0], out[1], out[4], out[5]))
+        assert got == want, (logn, elem, got)
     assert lib.msm_groups_check() == 0  # window groups of the pipelined MSM schedule (msm_plan.h)
     assert lib.split_shape_check() == 0  # shapes of a transform split over device slots (ntt_plan.h)
     assert lib.msm_plan_check() == 0  # the window plan of msm() (msm_plan.h make_plan)
