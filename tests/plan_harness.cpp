@@ -517,3 +517,13 @@ extern "C" int msm_plan_probe(int n, int bits, int c, int* out)
   out[0] = pl.c, out[1] = pl.nwin, out[2] = pl.wpf, out[3] = (int)pl.nb, out[4] = pl.n_lo;
   return 0;
 }
+// the whole plan of one launch sequence, as msm() makes it: out = c, nwin, wpf, nb, n_lo, negate, seg. batch, pf, bitsize: MSMConfig's
+// batch_size, precompute_factor, bitsize; force_windows: MSMConfig.ext "hip_msm_windows"
+extern "C" int msm_plan_seg_probe(int n, int bits, int c, int batch, int pf, int bitsize, int force_windows, int* out)
+{
+  icicle_msm_config_t cfg{};
+  cfg.batch_size = batch, cfg.c = c, cfg.precompute_factor = pf, cfg.bitsize = bitsize;
+  const MsmPlan pl = make_plan(n, bits, cfg, force_windows);
+  out[0] = pl.c, out[1] = pl.nwin, out[2] = pl.wpf, out[3] = (int)pl.nb, out[4] = pl.n_lo, out[5] = pl.negate ? 1 : 0, out[6] = (int)pl.seg;
+  return 0;
+}

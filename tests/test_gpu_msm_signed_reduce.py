@@ -19,6 +19,8 @@ import numpy as np
 import pytest
 
 from oracle import pyref, ref
+from tests.msm_directed import (_plan_widths, in_all_scalars_equal, in_cancelling_pairs, in_equal_bases_under_scalars_k_and_k_plus_one,  # noqa: F401
+                                in_identity_bases, in_scalars_one_and_r_minus_one, in_top_bucket_only)
 from tests.util import cached_points, points_to_array, rand_scalars, to_words
 
 pytestmark = pytest.mark.gpu
@@ -64,84 +66,11 @@ def _neg_rows(C, arr):
     return out
 
 
-def _plan_widths(bits, nwin):
-    """(offset, width) of the windows of a forced mixed plan: the top x windows one bit wider (msm_plan.h make_plan)"""
-    clo, x = bits // nwin, bits - (bits // nwin) * nwin
-    out, off = [], 0
-    for w in range(nwin):
-        width = clo if w < nwin - x else clo + 1
-        out.append((off, width))
-        off += width
-    assert off == bits
-    return out
-
-
-# ---- the directed inputs, shared with tests/test_gpu_msm_quad_reduce.py (the same bucket patterns through the four-lane kernels).
+# ---- the directed inputs live in tests/msm_directed.py (in_*, _plan_widths), shared with tests/test_gpu_msm_quad_reduce.py (the same bucket
+# patterns through the four-lane kernels) and tests/test_gpu_msm_groups_directed.py (every group).
 # r: the scalar modulus; bases_fn(n, period=1024): n base rows; neg_fn(rows): the rows of the negated points. Each returns (scalars, bases).
 def _g1_fns(C):
     return C.r, functools.partial(_bases, C), functools.partial(_neg_rows, C)
-
-
-def in_all_scalars_equal(r, bases_fn, neg_fn):
-    """one full bucket per window, every other bucket the identity: line and tri0 stay the identity until that row"""
-    rng = np.random.default_rng(9102)
-    n = (1 << 10) + 1
-    s = rand_scalars(rng, 1, r)[0]
-    return [s] * n, bases_fn(n)
-
-
-def in_equal_bases_under_scalars_k_and_k_plus_one(r, bases_fn, neg_fn):
-    """every bucket holds a multiple of ONE point and neighbouring buckets are full: column sums and running sums that are equal
-    or negatives of each other meet in the lane scans (an addition that is a doubling, one that gives the identity)"""
-    rng = np.random.default_rng(9103)
-    n = 1 << 10
-    bases = np.ascontiguousarray(np.tile(bases_fn(1), (n, 1)))
-    vals = rand_scalars(rng, n, r)
-    for i in range(0, n, 2):
-        vals[i + 1] = (vals[i] + 1) % r
-    vals[0:64] = [5, 6] * 32  # the same number of points in buckets 5 and 6 of window 0: equal bucket sums side by side
-    return vals, bases
-
-
-def in_cancelling_pairs(r, bases_fn, neg_fn):
-    """cancelled buckets (the identity) between full ones"""
-    rng = np.random.default_rng(9104)
-    n = 1 << 12
-    half = bases_fn(n // 2)
-    bases = np.empty((n, half.shape[1]), dtype=np.uint32)
-    bases[0::2] = half
-    bases[1::2] = neg_fn(half)
-    vals = rand_scalars(rng, n, r)
-    for i in range(0, n // 2, 2):  # the first half of the pairs share a scalar: their buckets cancel where nothing else lands
-        vals[i + 1] = vals[i]
-    return vals, bases
-
-
-def in_scalars_one_and_r_minus_one(r, bases_fn, neg_fn):
-    """only bucket 1 of window 0 is populated, with both signs: every other chunk sums identities"""
-    n = (1 << 11) + 7
-    return [r - 1 if i % 3 else 1 for i in range(n)], bases_fn(n, period=300)
-
-
-def in_top_bucket_only(r, bases_fn, wins):
-    """every second window's digit is 2^(width - 1), the largest a signed digit takes; wins: (bit offset, width) of every window"""
-    bits = r.bit_length()
-    n = 1 << 10
-    s_even = sum(1 << (off + width - 1) for k, (off, width) in enumerate(wins) if k % 2 == 0 and off + width < bits)
-    s_odd = sum(1 << (off + width - 1) for k, (off, width) in enumerate(wins) if k % 2 == 1 and off + width < bits)
-    assert 0 < s_even < r and 0 < s_odd < r
-    return [s_even if i % 2 == 0 else s_odd for i in range(n)], bases_fn(n)
-
-
-def in_identity_bases(r, bases_fn, neg_fn):
-    rng = np.random.default_rng(9107)
-    n = 1 << 12
-    bases = bases_fn(n)
-    bases[0:3] = 0
-    bases[100:2000:2] = 0
-    bases[3000:3500] = 0
-    bases[-1] = 0
-    return rand_scalars(rng, n, r), bases
 
 
 @pytest.mark.parametrize("cname", SIGNED)
